@@ -9,18 +9,24 @@
 The JOB is BASELINE.json's metric and does not depend on the flags: IS* + FID of ONE set of 30 000 synthetic uint8
 256x256x3 images -- decoded pixels already resident in HBM (PNG decode and the host->device copy are NOT in the timed
 region; DESIGN.md section 6 gives the host-inclusive rates of the CLI) -- against pre-computed reference statistics.
-A STEP is 1/K of the job = the hot path over 30 000 / K images (500 at the default K = 60, 1 500 at --steps 20; the
-device runs them in batches of up to 5000, engine.DEVICE_BATCH_DEFAULT; the feed legs and the CLIs: 1000, engine.FEED_DEVICE_BATCH_DEFAULT; `--batch B` makes the job K*B images instead):
+A STEP is the whole job, run K times (--steps K) after W untimed ones (--warmup W); `ms_per_step` is the mean wall time
+of one timed step.  The image loop of a step runs the hot path in device batches of up to 5000 images
+(engine.DEVICE_BATCH_DEFAULT; the feed legs and the CLIs: 1000, engine.FEED_DEVICE_BATCH_DEFAULT; `--batch B` or
+`--images B` makes the job B images instead):
     resize 256->299 (PIL-exact, csrc/resize.hip) -> InceptionV3 trunk (hand-written split-fp16 MFMA convolutions,
     csrc/conv_split.hip / conv_pipe.hip / trunk_ops.hip) + fc -> fp64 covariance/mean accumulation (csrc/stats.hip)
     -> IS* split sums (csrc/is_score.hip).
 With N GPUs the SAME job is sharded (STRONG scaling, SURVEY.md section 8(d) "Config 3"): rank r takes the
 contiguous index range dist.shard_range(30 000, r, N) (3 750 images at N = 8) and runs it in device batches that
-divide its range (3000 / 3000 / 2500 / 1875 images at N = 1 / 2 / 4 / 8; a step stays 1/K of the job).  After the loop the timed region contains, once: the
+divide its range (5000 / 5000 / 3750 / 3750 images at N = 1 / 2 / 4 / 8).  After the loop a step contains, once: the
 all-reduce of the sufficient statistics over RCCL, the finalisation of (mu, sigma), the Frechet distance
-(csrc/frechet.hip, solved redundantly on every rank) and the IS* finalisation.  value = 30 000 / max-over-ranks
-seconds; `allreduce_ms` and `finalize_ms` are reported separately.  `--scaling weak` gives every rank its own
-30 000 images instead.
+(csrc/frechet.hip, solved redundantly on every rank) and the IS* finalisation.  value = 30 000 / (max-over-ranks
+seconds of the K steps / K); `allreduce_ms` and `finalize_ms` are reported separately (last step).  `--scaling weak`
+gives every rank its own 30 000 images instead.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the job receives it, to DIR/<name>.npy
+(float64, 33.6 MB in all): mu (2048,), sigma (2048, 2048), fid (1,), inception_score (2,) = [mean, std].  The inputs
+(synthetic images, seeded stand-in weights) depend on the flags only, so two builds can be compared file by file.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline      the dominant hand-written kernel of the step loop, timed with HIP events inside the timed region,
@@ -235,6 +241,16 @@ def cpu_reference_pass(gen_u8, ref_u8, n_job, dims=2048, workers=8):
     return base, out
 
 
+def dump_outputs(out_dir, mu, sigma, res, is_mean, is_std):
+    """What one step hands its caller, as float64 .npy files: mu (2048,), sigma (2048, 2048), fid (1,) and
+    inception_score (2,) = [mean, std].  33.6 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"mu": mu.double().cpu().numpy(), "sigma": sigma.double().cpu().numpy(),
+              "fid": np.array([res["fid"]], dtype=np.float64), "inception_score": np.array([is_mean, is_std], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -242,7 +258,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--images", type=int, default=JOB_IMAGES, help="images of the job (the metric's 30 000)")
     ap.add_argument("--batch", type=int, default=0,
-                    help="explicit images per step: the job becomes steps x batch images (0: the job is --images, a step = images / steps)")
+                    help="explicit images per step, i.e. per job (0: --images)")
     ap.add_argument("--device-batch", type=int, default=0, help="images per device batch (0: chosen by rank_batch)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
     ap.add_argument("--ref-images", type=int, default=JOB_IMAGES,
@@ -266,7 +282,11 @@ def main():
     ap.add_argument("--png-images", type=int, default=30000,
                     help="png_feed leg (N = 1, after the timed region, never `value`): this many images of the timed set are written as "
                          "PNG files and the job is run from the FILES through the CLIs' feed (png_ring.py); 0 skips the leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (mu, sigma, fid, inception_score) to DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args.gpus))                  # before anything touches the GPU in this process
     # The contract is ONE JSON line on stdout.  librccl prints a version banner ("RCCL version : ...", five lines) to the C
@@ -301,8 +321,7 @@ def main():
     cl = None if args.channels_last < 0 else bool(args.channels_last)
     eng = RealismEngine(dims=2048, device_index=local_rank, seed=0, with_logits=True, channels_last=cl)
     K, W = args.steps, args.warmup
-    n_job = K * args.batch if args.batch > 0 else args.images
-    B = n_job / K                                             # images per step (a step = 1/K of the job)
+    n_job = args.batch if args.batch > 0 else args.images      # images per step (a step = the whole job)
     if args.scaling == "strong":
         n_total = n_job
         lo, hi = tdist.shard_range(n_total, rank, world)
@@ -339,92 +358,99 @@ def main():
     solver = frechet_solver(2048, dev)
     solver.set_profiling(True)
 
-    # ---- warmup (allocator, clocks, RCCL communicator) ----------------------------------------------
-    eng.begin(n_total=max(W, 1) * rb)
-    for s in range(W):
-        a, b = chunks[s % len(chunks)]
-        eng.step_u8(data[a:b], s * rb)
-    if W > 0:
-        eng.reduce()                                # also brings up the RCCL communicator outside the timed region
-        mu_w, sig_w = eng.statistics()
-        solver.distance(mu_w, sig_w, mu_ref, sigma_ref)
-        eng.inception_score()
-    elif world > 1:
-        tdist.all_reduce_sum_(torch.zeros(1024, dtype=torch.float64, device=dev))
-    torch.cuda.synchronize()
-
-    # ---- timed region -------------------------------------------------------------------------------
+    # ---- one step = the whole job ----------------------------------------------------------------------
     nch = len(chunks)
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(nch)]
     ev_tail = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     from tise_toolbox_amd.conv_split import SplitConv as _SC
     # HIP events around every convolution launch cost ~1.5 % of a step (130 extra records per 65 launches), so they
-    # bracket the conv launches of at most three device batches -- first, middle, last: 195 launches, plenty for the
-    # average -- whatever the number of steps (measured: 0.8 % of the job with five of ten batches bracketed); the
-    # rocprofv3 summary of the same command is the cross-check.
+    # bracket the conv launches of at most three device batches of the LAST timed step -- first, middle, last: 195
+    # launches, plenty for the average -- whatever the number of steps (measured: 0.8 % of the job with five of ten
+    # batches bracketed); the rocprofv3 summary of the same command is the cross-check.
     # TISE_BENCH_MODE=noevents switches them off.
     mode = os.environ.get("TISE_BENCH_MODE", "events")
     conv_timer = [] if mode == "events" else None
     evented = {0, (nch - 1) // 2, nch - 1}
     _SC.timer = None
     u8_stem = getattr(eng, "_u8_stem", False)
-    eng.begin(n_total=n_total, temperature=T_COCO, splits=10, rule="coco")
     # after the second device batch when there are at least three (the host blocks until the side stream has the factor:
     # two batches are queued on the main stream by then); with one or two batches per rank (8 GPUs: 2 x 1875 images) after
     # the first, so that the factorisation still runs under a batch instead of in the tail
     prefactor_after = (1 if nch >= 3 else 0) if os.environ.get("TISE_BENCH_PREFACTOR", "1") != "0" else -1
-    tdist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for s, (a, b) in enumerate(chunks):
-        batch = data[a:b]
-        _SC.timer = conv_timer if (conv_timer is not None and s in evented) else None
-        ev[s][0].record()
-        if u8_stem:
-            x = device.resize_u8_only(batch, (299, 299))       # uint8 out; the stem conv applies the input table
-            ev[s][1].record()
-            feats, logits = eng._trunk_u8(x)
-        else:
-            x = device.resize_bilinear_u8(batch, (299, 299), eng.lut, channels_last=eng.channels_last)
-            ev[s][1].record()
-            feats, logits = eng._trunk(x, prenormalized=True)
-        ev[s][2].record()
-        eng.stats.update(feats)                              # ONE launch: fp64-MFMA S += X^T X, column sums, row count
-        ev[s][3].record()
-        eng.is_acc.update(logits, lo + a)
-        if s == prefactor_after:
-            # the reference statistics are an input: their pivoted Cholesky does not depend on the generated set, so it
-            # runs on a side stream under the network passes (the host waits for that stream only; two device batches
-            # are already queued on the main stream)
-            solver.prefactor(sigma_ref)
-    _SC.timer = None
-    ev_tail[0].record()
-    t_loop_host = time.perf_counter()
-    eng.reduce()                                             # RCCL all-reduce of {n, s, S} and the IS* sums
-    if backend is not None:
-        torch.cuda.current_stream().synchronize()            # so that allreduce_ms is the collective, not the queue
-    ev_tail[1].record()
-    t_reduce_host = time.perf_counter()
-    mu, sigma = eng.statistics()
-    ev_tail[2].record()
-    if prefactor_after >= 0:
-        res = solver.distance_prefactored(mu_ref, mu, sigma)  # GEMM + tridiagonalisation + bisection; one 8-double read
-        if res["flags"] & _lib.TISE_FLAG_NONFINITE:           # fid_score.py:156-160 rescue: full path with eps
-            res = solver.distance(mu, sigma, mu_ref, sigma_ref, 1e-6)
-    else:
-        res = solver.distance(mu, sigma, mu_ref, sigma_ref)
-    is_mean, is_std = eng.inception_score()
-    ev_tail[3].record()
-    tdist.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
 
-    elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
+    def run_step(timed_convs):
+        """The job once: image loop, all-reduce, finalize, Frechet distance, IS* finalize.  The accumulators are set up
+        before the clock starts.  Returns the host time stamps and what the job computed."""
+        eng.begin(n_total=n_total, temperature=T_COCO, splits=10, rule="coco")
+        tdist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for s, (a, b) in enumerate(chunks):
+            batch = data[a:b]
+            _SC.timer = conv_timer if (timed_convs and conv_timer is not None and s in evented) else None
+            ev[s][0].record()
+            if u8_stem:
+                x = device.resize_u8_only(batch, (299, 299))       # uint8 out; the stem conv applies the input table
+                ev[s][1].record()
+                feats, logits = eng._trunk_u8(x)
+            else:
+                x = device.resize_bilinear_u8(batch, (299, 299), eng.lut, channels_last=eng.channels_last)
+                ev[s][1].record()
+                feats, logits = eng._trunk(x, prenormalized=True)
+            ev[s][2].record()
+            eng.stats.update(feats)                              # ONE launch: fp64-MFMA S += X^T X, column sums, row count
+            ev[s][3].record()
+            eng.is_acc.update(logits, lo + a)
+            if s == prefactor_after:
+                # the reference statistics are an input: their pivoted Cholesky does not depend on the generated set, so it
+                # runs on a side stream under the network passes (the host waits for that stream only; two device batches
+                # are already queued on the main stream)
+                solver.prefactor(sigma_ref)
+        _SC.timer = None
+        ev_tail[0].record()
+        t_loop_host = time.perf_counter()
+        eng.reduce()                                             # RCCL all-reduce of {n, s, S} and the IS* sums
+        if backend is not None:
+            torch.cuda.current_stream().synchronize()            # so that allreduce_ms is the collective, not the queue
+        ev_tail[1].record()
+        t_reduce_host = time.perf_counter()
+        mu, sigma = eng.statistics()
+        ev_tail[2].record()
+        if prefactor_after >= 0:
+            res = solver.distance_prefactored(mu_ref, mu, sigma)  # GEMM + tridiagonalisation + bisection; one 8-double read
+            if res["flags"] & _lib.TISE_FLAG_NONFINITE:           # fid_score.py:156-160 rescue: full path with eps
+                res = solver.distance(mu, sigma, mu_ref, sigma_ref, 1e-6)
+        else:
+            res = solver.distance(mu, sigma, mu_ref, sigma_ref)
+        is_mean, is_std = eng.inception_score()
+        ev_tail[3].record()
+        tdist.barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        return (t0, t_loop_host, t_reduce_host, t1), (mu, sigma, res, is_mean, is_std)
+
+    # ---- warmup: W untimed steps (allocator, clocks, RCCL communicator) --------------------------------
+    for _ in range(W):
+        run_step(False)
+    if W == 0 and world > 1:
+        tdist.all_reduce_sum_(torch.zeros(1024, dtype=torch.float64, device=dev))
+    torch.cuda.synchronize()
+
+    # ---- timed region: K steps ------------------------------------------------------------------------
+    step_s = []
+    for k in range(K):
+        (t0, t_loop_host, t_reduce_host, t1), (mu, sigma, res, is_mean, is_std) = run_step(k == K - 1)
+        step_s.append(t1 - t0)
+
+    elapsed = torch.tensor([sum(step_s)], dtype=torch.float64, device=dev)
     if world > 1:
         torch.distributed.all_reduce(elapsed, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(elapsed.item())
-    # per-rank breakdown: with only the max-over-ranks time a straggler or a slow communicator cannot be
-    # told from a slow trunk.  loop_device = first launch of the image loop -> last (HIP events on this rank's stream);
+    rate = n_total * K / elapsed                                 # images/s: the job's images over the mean step time
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, mu, sigma, res, is_mean, is_std)
+    # per-rank breakdown of the last step (VERDICT r5 weak 6): with only the max-over-ranks time a straggler or a slow
+    # communicator cannot be told from a slow trunk.  loop_device = first launch of the image loop -> last (HIP events on this rank's stream);
     # reduce = host wall from the end of the loop's enqueue to the completed all-reduce (it contains the wait for the device
     # to finish the loop); first_collective = the reference side's all-reduce, communicator creation included
     mine = torch.tensor([float(rank), n_rank, ev[0][0].elapsed_time(ev_tail[0]) * 1e-3, t_loop_host - t0, t_reduce_host - t_loop_host,
@@ -512,15 +538,16 @@ def main():
         allreduce_ms = ev_tail[0].elapsed_time(ev_tail[1])
         out = {
             "metric": "images/sec through InceptionV3+FID on 30k 256x256 @1/2/4/8 GPU; |dFID| vs ref",
-            "value": n_total / elapsed, "unit": "images/sec", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "value": rate, "unit": "images/sec", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": elapsed / K * 1e3, "step_ms": [round(t * 1e3, 3) for t in step_s], "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": conv_dtype, "data": "synthetic",
             "config": {"workload": f"IS*+FID of ONE set of {n_total} synthetic 256x256 images (BASELINE configs[1]/[2]: 30k "
                                    f"images, InceptionV3 pool3 2048-d) sharded over {world} GPU(s): {n_rank} images per GPU in "
                                    f"device batches of {rb}; inputs are pre-decoded uint8 pixels resident in HBM (PNG decode and "
                                    f"host->device copy excluded from the timed region); seeded stand-in InceptionV3 weights, "
-                                   f"reference stats from {args.ref_images} images",
-                       "step_images": B, "images_per_gpu": n_rank, "images_total": n_total, "device_batch": rb,
+                                   f"reference stats from {args.ref_images} images; one step = this whole job, {K} timed "
+                                   f"steps after {W} untimed ones",
+                       "step_images": n_total, "images_per_gpu": n_rank, "images_total": n_total, "device_batch": rb,
                        "device_batches_per_gpu": nch, "dims": 2048, "trunk": trunk_desc, "parallelism": f"dp{world}",
                        "collective": {"world_size": world, "backend": backend,
                                       "forced_one_rank_group": bool(world == 1 and backend is not None),
@@ -550,7 +577,7 @@ def main():
         out["host_feed"] = None
         if world == 1 and not args.no_host_feed:
             out["host_feed"] = host_feed_leg(eng, data, lo, n_total, args.feed_batch, mu_ref, sigma_ref, solver, dev,
-                                             float(res["fid"]), n_total / elapsed)
+                                             float(res["fid"]), rate)
         out["png_feed"] = None
         out["cli_process"] = None
         if world == 1 and args.png_images > 0:
@@ -561,7 +588,7 @@ def main():
                 out["cli_process"] = out["png_feed"].pop("cli_process", None)
                 # the in-leg resident reference is ONE run of the same 30 000 images and moves by a few per cent between runs;
                 # the line's headline rate is K timed steps: the steadier denominator, reported beside it
-                out["png_feed"]["ratio_to_value"] = out["png_feed"]["images_per_s"] / (n_total / elapsed)
+                out["png_feed"]["ratio_to_value"] = out["png_feed"]["images_per_s"] / rate
             except Exception as e:                                       # noqa: BLE001
                 import traceback
                 traceback.print_exc()

@@ -104,7 +104,7 @@ def test_resize_full_batch_bit_exact_and_batch_invariant(cuda_device):
     assert torch.equal(sums, part)
 
 
-def test_bench_strong_scaling_two_ranks_on_one_gpu(cuda_device):
+def test_bench_strong_scaling_two_ranks_on_one_gpu(cuda_device, tmp_path):
     """`python bench.py --gpus 2` invoked DIRECTLY (no torchrun: bench.py starts its two ranks itself, both on THIS
     GPU over a gloo rendezvous -- TISE_DIST_BACKEND / TISE_FORCE_DEVICE0): the strong-scaling job -- one image set sharded by global index, one all-reduce of the statistics, Frechet solved on
     both ranks -- must print the same scores as the one-process run of the same job, report the sharding it used and
@@ -114,7 +114,9 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu(cuda_device):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--steps", "4", "--warmup", "1", "--images", "2000", "--no-cpu-baseline", "--no-cross-check", "--ref-images", "2200"]
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, cwd=root, capture_output=True, text=True, timeout=600)
+    dump = tmp_path / "dump"
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + ["--dump-outputs", str(dump)], cwd=root,
+                         capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads(one.stdout.strip().split("\n")[-1])
     env = dict(os.environ, TISE_DIST_BACKEND="gloo", TISE_FORCE_DEVICE0="1")
@@ -129,10 +131,18 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu(cuda_device):
     # the one-process run brings up a ONE-rank RCCL group so that the job's all-reduces really execute (round 5)
     assert (c1["world_size"], c1["backend"], c1["forced_one_rank_group"]) == (1, "nccl", True), c1
     assert d1["reference_side"]["images"] == 2200 and d2["reference_side"]["images_this_rank"] == 1100
-    assert d1["config"]["step_images"] == 500 and "resident in HBM" in d1["config"]["workload"]
+    assert d1["config"]["step_images"] == 2000 and "resident in HBM" in d1["config"]["workload"]     # a step = the whole job
     assert d2["config"]["images_total"] == d1["config"]["images_total"] == 2000 and d2["config"]["images_per_gpu"] == 1000
     # 2 000 images < d = 2 048: rank-deficient covariances, where the fp64 summation order of S -- one 2 000-image device batch
     # against two ranks' 1 000-image batches (bench.rank_batch: the largest divisor <= 3 000) -- moves the distance by ~2e-7
     assert abs(d2["scores"]["fid"] - d1["scores"]["fid"]) <= 1e-6 and abs(d2["scores"]["is_mean"] - d1["scores"]["is_mean"]) <= 1e-9
     assert d2["roofline"]["frac"] > 0.05 and d2["allreduce_ms"] >= 0.0 and d2["cpu_baseline"] is None
-    assert d2["value"] > 0 and abs(d2["ms_per_step"] * 4 / 1e3 * d2["value"] - 2000) < 1.0       # value = images / elapsed
+    assert d2["value"] > 0 and abs(d2["ms_per_step"] / 1e3 * d2["value"] - 2000) < 1.0       # value = images / step time
+    # --steps 4: four timed steps; ms_per_step is their mean (one process; with two ranks the slower rank's)
+    assert len(d1["step_ms"]) == len(d2["step_ms"]) == 4 and abs(sum(d1["step_ms"]) / 4 - d1["ms_per_step"]) <= 1e-3 * d1["ms_per_step"]
+    # --dump-outputs: the last step's outputs as float64 arrays, the same numbers as the result line
+    got = {n: np.load(dump / f"{n}.npy") for n in ("mu", "sigma", "fid", "inception_score")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["mu"].shape == (2048,) and got["sigma"].shape == (2048, 2048) and np.isfinite(got["sigma"]).all()
+    assert got["fid"].tolist() == [d1["scores"]["fid"]]
+    assert got["inception_score"].tolist() == [d1["scores"]["is_mean"], d1["scores"]["is_std"]]

@@ -226,7 +226,10 @@ class U8CacheLoader:
             for b in range(nb):
                 k = out.get()
                 if isinstance(k, BaseException):
-                    raise k
+                    try:
+                        raise k
+                    finally:
+                        k = None                                              # no cycle through this frame (png_ring.PngRingLoader.__iter__)
                 k, rows = k
                 cur = torch.cuda.current_stream(self.device)
                 if b == 1:
@@ -269,6 +272,14 @@ def worker_init(_worker_id):
     worker allocates itself is collected as usual.  (The handle classes of device.py also refuse to destroy from another pid.)"""
     import gc
     gc.freeze()
+
+
+# worker_init runs after the worker's own start-up code, and a collection can fire before it (the collector's counters come
+# with the copied heap): a forked child of this interpreter freezes at the fork itself (SIGSEGV in a DataLoader worker forked
+# right after a ring feed's RaggedImages fallback, tests/test_gpu_clip.py::test_rp_ring_feed_equals_dataloader_feed)
+if hasattr(os, "register_at_fork"):
+    import gc as _gc
+    os.register_at_fork(after_in_child=_gc.freeze)
 
 
 def collate_u8(samples):

@@ -463,7 +463,12 @@ class PngRingLoader:
             for b in range(nb):
                 item = out.get()
                 if isinstance(item, BaseException):
-                    raise item
+                    # the traceback keeps this frame: without the reset its locals (events, device buffers) and the exception
+                    # form a cycle that outlives a caller's fallback until some process collects it -- possibly a forked worker
+                    try:
+                        raise item
+                    finally:
+                        item = None
                 k, rows = item
                 cur = torch.cuda.current_stream(dev)
                 if b == 1:

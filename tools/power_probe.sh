@@ -1,7 +1,7 @@
 #!/bin/bash
 # Power draw and shader clock while the bench's image loop runs:  bash tools/power_probe.sh   (through gpurun)
-# rocm-smi is polled every ~0.3 s next to `bench.py --steps 240` (120 k images, ~6 s of image loop).
-python bench.py --steps 240 --warmup 4 --no-cpu-baseline --no-cross-check > /tmp/bench_power.json 2> /tmp/bench_power.err &
+# rocm-smi is polled every ~0.3 s next to `bench.py --steps 4` (4 jobs = 120 k images, ~6 s of image loop).
+python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-cross-check > /tmp/bench_power.json 2> /tmp/bench_power.err &
 BP=$!
 sleep 9         # imports, weights, resident image set
 for i in $(seq 1 40); do
