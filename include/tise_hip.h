@@ -279,12 +279,15 @@ int tise_cosine_top1(const void* img_emb_dev, const void* txt_emb_dev, const int
  * the fp16 model `clip.load` serves on a GPU.  Row-major matrices with explicit leading dimensions (elements).
  *   tise_gemm_f16        out[m][n] = act(sum_k a[m][k] w[n][k] + bias[n]) + residual[m][n]     (nn.Linear layout of w;
  *                        act 0 = none, 1 = QuickGELU x*sigmoid(1.702x); bias / residual nullable; k % 64 == 0,
- *                        n % 8 == 0, leading dimensions % 8 == 0)
- *   tise_layernorm_f16   per row over C <= 1024 columns (C, ldx, ldo multiples of 8; 16-byte aligned pointers), fp32 mean / variance (clip.model.LayerNorm)
+ *                        n % 8 == 0, leading dimensions % 8 == 0, lda / ldw >= k, ldo / ldr >= n; a / w / residual / out
+ *                        16-byte aligned, bias 8-byte aligned)
+ *   tise_layernorm_f16   per row over C <= 1024 columns (C, ldx, ldo multiples of 8, ldx / ldo >= C; 16-byte aligned pointers), fp32 mean / variance (clip.model.LayerNorm)
  *   tise_attention_f16   qkv [batch*seq][3*heads*64] (q | k | v) -> out [batch*seq][heads*64], softmax(q k^T / 8) v per
- *                        (sequence, head), optional causal mask (text tower); seq <= 80, head_dim == 64
+ *                        (sequence, head), optional causal mask (text tower); seq <= 96, head_dim == 64, qkv / out
+ *                        16-byte aligned
  *   tise_patchify_f16    image (batch, 3, res, res) NCHW -> [batch*(res/patch)^2][3*patch*patch], columns in the order of
- *                        conv1.weight.flatten(1): the patch embedding becomes one tise_gemm_f16
+ *                        conv1.weight.flatten(1): the patch embedding becomes one tise_gemm_f16 (patch % 8 == 0; image /
+ *                        out 16-byte aligned)
  *   tise_vit_tokens_f16  x[b][0] = class_emb + pos[0]; x[b][1+p] = patch_out[b*n_patches+p] + pos[1+p]
  *   tise_text_tokens_f16 x[r] = table[tokens[r]] + pos[r % seq]
  *   tise_gather_rows_f16 out[i] = x[index[i]]   (class token of every image / end-of-text token of every caption)

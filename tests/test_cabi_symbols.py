@@ -49,6 +49,47 @@ def test_argument_validation_without_a_gpu():
     assert lib.tise_resize_bilinear_u8(None, 1, 0, 5, None, 299, 299, 1, lut, None, None) == _lib.TISE_ERR_INVALID_ARG
 
 
+def test_clip_entries_reject_strides_and_misalignment_without_a_gpu():
+    """The CLIP tower entries (csrc/clip_ops.hip) refuse leading dimensions shorter than a row and pointers the kernels'
+    16-byte (8-byte: gemm bias) accesses cannot take, before any HIP call: fake device addresses, every call has exactly
+    one defect, and each must come back TISE_ERR_INVALID_ARG (a launch would need a device this test does not have)."""
+    from tise_toolbox_amd import _lib
+    lib = _lib.load()
+    bad = _lib.TISE_ERR_INVALID_ARG
+    A, W, B, R, O = 0x7f0000000000, 0x7f0000100000, 0x7f0000200000, 0x7f0000300000, 0x7f0000400000   # 16-byte aligned
+    m, n, k = 128, 256, 192
+
+    def gemm(a=A, lda=k, w=W, ldw=k, bias=B, res=R, ldr=n, out=O, ldo=n, mm=m, act=0):
+        return lib.tise_gemm_f16(a, lda, w, ldw, bias, res, ldr, out, ldo, mm, n, k, act, None)
+    assert gemm(mm=0) == _lib.TISE_OK                                 # M = 0: nothing to do, no launch
+    assert gemm(mm=0, lda=k - 8) == bad                               # arguments are checked before the M = 0 exit
+    for kw in (dict(lda=k - 8), dict(lda=8), dict(ldw=k - 8), dict(ldo=n - 8), dict(ldr=n - 8), dict(ldr=0),
+               dict(a=A + 8), dict(a=A + 2), dict(w=W + 8), dict(out=O + 8), dict(res=R + 8), dict(bias=B + 4),
+               dict(bias=B + 2), dict(act=2)):
+        assert gemm(**kw) == bad, kw
+    assert gemm(res=None, ldr=0, mm=0) == _lib.TISE_OK                # no residual: ldr is not read
+    assert gemm(bias=B + 8, mm=0) == _lib.TISE_OK                     # 8-byte aligned bias is enough
+
+    def ln(x=A, ldx=520, out=O, ldo=520, rows=4, c=520, g=W, b=B):
+        return lib.tise_layernorm_f16(x, ldx, g, b, out, ldo, rows, c, ctypes.c_float(1e-5), None)
+    assert ln(rows=0) == _lib.TISE_OK
+    for kw in (dict(ldx=512), dict(ldo=512), dict(ldx=8), dict(x=A + 8), dict(out=O + 8), dict(g=W + 8), dict(b=B + 8),
+               dict(c=1032, ldx=1032, ldo=1032), dict(c=12, ldx=16, ldo=16)):
+        assert ln(**kw) == bad, kw
+
+    def attn(qkv=A, out=O, batch=2, seq=77, heads=8, hd=64):
+        return lib.tise_attention_f16(qkv, batch, seq, heads, hd, 1, out, None)
+    assert attn(batch=0) == _lib.TISE_OK
+    for kw in (dict(qkv=A + 8), dict(qkv=A + 2), dict(out=O + 8), dict(seq=97), dict(seq=0), dict(hd=32), dict(hd=128)):
+        assert attn(**kw) == bad, kw
+
+    def patchify(img=A, out=O, batch=2, res=224, patch=32):
+        return lib.tise_patchify_f16(img, batch, res, patch, out, None)
+    assert patchify(batch=0) == _lib.TISE_OK
+    for kw in (dict(img=A + 8), dict(out=O + 8), dict(out=O + 2), dict(patch=12, res=48), dict(res=230)):
+        assert patchify(**kw) == bad, kw
+
+
 def test_product_refuses_to_run_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -202,3 +202,59 @@ def test_rp_ring_feed_equals_dataloader_feed(cuda_device, tmp_path):
     c = RP_coco.embed_paths(model, paths, dev, 16, workers=3, feed="ring", convert_first=False)      # PA's rule: RGBA -> DataLoader road
     d = RP_coco.embed_paths(model, paths, dev, 16, workers=2, feed="dataloader", convert_first=False)
     assert torch.equal(c, d)
+
+
+def test_towers_match_fp64_module_and_keep_rp_decisions(cuda_device, monkeypatch):
+    """The towers against clip_model.CLIP run in FLOAT64 on the same fp16-rounded (stand-in) parameters: 64 images and
+    100 captions of 2 .. 60 tokens, the captions through RP_coco.embed_texts (length-sorted batches encoded at their
+    longest caption, so both the NT = 1 (<= 32 tokens) and the NT = 2 (<= 64) attention instances serve them).  Every
+    embedding: cosine >= 0.9995 against fp64.  Decisions: with eps_i = |e^_i - e_i| (unit vectors, measured) a
+    similarity moves by at most eps_i + eps_j + tau (tau = 512 * 2^-23: the fp32 dot products of the retrieval kernel),
+    so the RP top-1 over the 100 candidates (device.cosine_top1, RP's own reduction) cannot differ from the fp64 model's
+    where the fp64 margin exceeds delta_i = 2 eps_i + 2 max_j eps_j + 2 tau; it must equal it there."""
+    from tise_toolbox_amd import RP_coco, clip_hip, clip_model, device
+    model_h = clip_model.build_clip().to(cuda_device).half()
+    ref = clip_model.build_clip().double().to(cuda_device)
+    ref.load_state_dict({k: v.double() for k, v in model_h.state_dict().items()})
+    towers = clip_hip.HipTowers(model_h)
+    g = torch.Generator(device="cpu").manual_seed(8)
+    img = torch.randn((64, 3, 224, 224), generator=g).half().to(cuda_device)
+    rng = np.random.default_rng(8)
+    words = [f"v{k}" for k in range(300)]
+    lengths = np.concatenate([[0, 58], rng.integers(0, 59, size=98)])          # + start and end token: 2 .. 60 tokens
+    caps = [" ".join(rng.choice(words, int(n))) for n in lengths]
+    tok = clip_model.HashTokenizer()
+    seen = []
+    orig = towers.encode_text
+
+    def spy(t):
+        seen.append(tuple(t.shape))
+        return orig(t)
+    monkeypatch.setattr(towers, "encode_text", spy)
+    with torch.no_grad():
+        fi = towers.encode_image(img)
+        fi = fi / fi.norm(dim=-1, keepdim=True)
+        ft = RP_coco.embed_texts(towers, tok, caps, cuda_device, 16)
+        ri = ref.encode_image(img.double())
+        rt = ref.encode_text(tok(caps).to(cuda_device))
+    assert min(s[1] for s in seen) <= 32 < max(s[1] for s in seen) <= 64, seen
+    ri, rt = ri / ri.norm(dim=-1, keepdim=True), rt / rt.norm(dim=-1, keepdim=True)
+    cos_i = (fi.double() * ri).sum(-1) / fi.double().norm(dim=-1)
+    cos_t = (ft.double() * rt).sum(-1) / ft.double().norm(dim=-1)
+    print("hip vs fp64: image cos min", cos_i.min().item(), "text cos min", cos_t.min().item())
+    assert cos_i.min().item() >= 0.9995 and cos_t.min().item() >= 0.9995
+    unit = lambda t: t.double() / t.double().norm(dim=-1, keepdim=True)
+    eps_i, eps_t = (unit(fi) - ri).norm(dim=-1), (unit(ft) - rt).norm(dim=-1)
+    tau = 512 * 2.0 ** -23
+    delta = 2 * eps_i + 2 * eps_t.max() + 2 * tau
+    sim = ri @ rt.t()
+    top2 = sim.topk(2, dim=-1)
+    want = top2.indices[:, 0]
+    margin = top2.values[:, 0] - top2.values[:, 1]
+    idx = torch.arange(100, dtype=torch.int32, device=cuda_device).repeat(64, 1)
+    top1, _ = device.cosine_top1(fi.half().contiguous(), ft.contiguous(), idx, want_p0=False)
+    decided = margin > delta
+    print(f"RP top-1: delta max {delta.max().item():.2e} (eps image max {eps_i.max().item():.2e}, text max "
+          f"{eps_t.max().item():.2e}); {int(decided.sum())} of 64 items decided by more than delta, "
+          f"{int((top1.long() == want).sum())} of 64 equal overall")
+    assert torch.equal(top1.long()[decided], want[decided])

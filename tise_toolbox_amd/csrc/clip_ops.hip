@@ -746,8 +746,14 @@ extern "C" {
 
 int tise_gemm_f16(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* res_dev,
                   int64_t ldr, void* out_dev, int64_t ldo, int m, int n, int k, int act, void* stream) {
+    // the kernels move a / w rows by 16-byte LDS-DMA, res / out in 16-byte pieces and bias in 8-byte pieces: strides
+    // below the row length and misaligned pointers are refused here, before anything reaches the device
     if (!a_dev || !w_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || k % GM_BK != 0 || n % 8 != 0 || lda % 8 != 0 || ldw % 8 != 0 ||
-        ldo % 8 != 0 || (res_dev && ldr % 8 != 0) || (act != 0 && act != 1))
+        ldo % 8 != 0 || (res_dev && ldr % 8 != 0) || (act != 0 && act != 1) || lda < k || ldw < k || ldo < n ||
+        (res_dev && ldr < n) ||
+        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev) | reinterpret_cast<uintptr_t>(out_dev) |
+          reinterpret_cast<uintptr_t>(res_dev)) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(bias_dev) & 7) != 0)
         return TISE_ERR_INVALID_ARG;
     if (m == 0) return TISE_OK;
     GemmArgs p;
@@ -801,6 +807,7 @@ int tise_gemm_f16(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw
 int tise_layernorm_f16(const void* x_dev, int64_t ldx, const void* gamma_dev, const void* beta_dev, void* out_dev, int64_t ldo,
                        int64_t rows, int C, float eps, void* stream) {
     if (!x_dev || !gamma_dev || !beta_dev || !out_dev || rows < 0 || C <= 0 || C > 1024 || C % 8 != 0 || ldx % 8 != 0 || ldo % 8 != 0 ||
+        ldx < C || ldo < C ||
         ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(gamma_dev) |
           reinterpret_cast<uintptr_t>(beta_dev)) & 15) != 0)
         return TISE_ERR_INVALID_ARG;
@@ -814,7 +821,9 @@ int tise_layernorm_f16(const void* x_dev, int64_t ldx, const void* gamma_dev, co
 }
 
 int tise_attention_f16(const void* qkv_dev, int batch, int seq, int heads, int head_dim, int causal, void* out_dev, void* stream) {
-    if (!qkv_dev || !out_dev || batch < 0 || seq <= 0 || seq > 96 || heads <= 0 || head_dim != 64) return TISE_ERR_INVALID_ARG;
+    if (!qkv_dev || !out_dev || batch < 0 || seq <= 0 || seq > 96 || heads <= 0 || head_dim != 64 ||
+        ((reinterpret_cast<uintptr_t>(qkv_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15) != 0)    // 16-byte q / k / v loads
+        return TISE_ERR_INVALID_ARG;
     if (batch == 0) return TISE_OK;
     const long long bh = (long long)batch * heads;
     if ((bh + 3) / 4 > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
@@ -829,7 +838,9 @@ int tise_attention_f16(const void* qkv_dev, int batch, int seq, int heads, int h
 }
 
 int tise_patchify_f16(const void* img_dev, int batch, int res, int patch, void* out_dev, void* stream) {
-    if (!img_dev || !out_dev || batch < 0 || res <= 0 || patch <= 0 || res % patch != 0 || patch % 8 != 0) return TISE_ERR_INVALID_ARG;
+    if (!img_dev || !out_dev || batch < 0 || res <= 0 || patch <= 0 || res % patch != 0 || patch % 8 != 0 ||
+        ((reinterpret_cast<uintptr_t>(img_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15) != 0)    // 16-byte loads / stores
+        return TISE_ERR_INVALID_ARG;
     if (batch == 0) return TISE_OK;
     const long long total = (long long)batch * (res / patch) * (res / patch) * 3 * patch * patch / 8;
     hipLaunchKernelGGL(patchify_f16_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)stream,
