@@ -251,17 +251,20 @@ class StatsAccumulator:
     def reset(self):
         _lib.call("tise_stats_reset", self._h, _stream())
 
-    def update(self, feats):
-        """feats: (rows, dims) fp32 CUDA tensor (row stride may exceed dims)."""
+    def _check_feats(self, feats):
         _require_cuda(feats)
         if feats.dim() != 2 or feats.shape[1] != self.dims or feats.dtype != torch.float32:
             raise ValueError(f"feats must be (rows,{self.dims}) float32")
-        if feats.stride(1) != 1:
-            feats = feats.contiguous()
+        return feats if feats.stride(1) == 1 else feats.contiguous()
+
+    def update(self, feats):
+        """feats: (rows, dims) fp32 CUDA tensor (row stride may exceed dims)."""
+        feats = self._check_feats(feats)
         _lib.call("tise_stats_update", self._h, _ptr(feats), feats.shape[0], feats.stride(0), _stream())
 
     def update_parts(self, feats, cov=True, col_sum=True):
-        """The two kernels of update() separately (bench.py brackets the MFMA one with HIP events)."""
+        """The two kernels of update() separately (bench.py brackets the MFMA one with HIP events); same checks as update()."""
+        feats = self._check_feats(feats)
         if cov:
             _lib.call("tise_stats_update_cov", self._h, _ptr(feats), feats.shape[0], feats.stride(0), _stream())
         if col_sum:
