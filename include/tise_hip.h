@@ -198,6 +198,26 @@ int tise_is_finalize(const double* acc_dev, int C_eff, int64_t n_total, int spli
                      double* out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * IS* temperature calibration (csrc/calibrate.hip).  One evaluation of the reference's
+ * CrossEntropyLoss(logits / T, labels), its derivative in T and _ECELoss's bins on cached logits
+ * (classifier_calibration/temperature_scaling.py:41,64-67,80-119); the LBFGS loop is the caller's.
+ *   logits_dev  rows x ld fp32; the classes of row i are logits_dev[i*ld + c0 .. i*ld + c0 + C)
+ *               (c0 = 1: the bird rule's dropped background class)
+ *   labels_dev  rows int32 class indices in [0, C)
+ *   edges_dev   n_bins + 1 ascending fp32 bin edges (torch.linspace(0, 1, n_bins + 1)); 1 <= n_bins <= 64
+ *   out_dev     4 + 3 n_bins doubles: [sum nll, sum dnll/dT, rows with a non-finite logit, rows with a label
+ *               outside [0, C), count[b], sum confidence[b], sum correct[b] (b < n_bins)]; flagged rows enter
+ *               no sum.  Bitwise reproducible (fixed summation order, no atomics).
+ *   ws_dev      ws_bytes >= tise_calib_workspace_bytes(rows, C, n_bins) of device scratch
+ * Rejected before any HIP call (TISE_ERR_INVALID_ARG): a NULL pointer, rows < 0, C < 1, c0 < 0,
+ * ld < c0 + C, n_bins outside 1..64, T <= 0 or not finite, a workspace too small.
+ * ------------------------------------------------------------------------------------------ */
+int tise_calib_workspace_bytes(int64_t rows, int C, int n_bins, size_t* bytes);
+int tise_calib_eval(const float* logits_dev, int64_t rows, int64_t ld, int c0, int C, const int32_t* labels_dev,
+                    double temperature, const float* edges_dev, int n_bins, double* out_dev, void* ws_dev,
+                    size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a5, epilogues) Fused channels-last fp32 epilogues around the MIOpen convolutions of the
  * InceptionV3 trunk (image_realism/FID/inception.py:59-95 via torchvision BasicConv2d = conv ->
  * BatchNorm(eval) -> ReLU, InceptionA/C/E branch_pool = avg_pool2d(3,1,1) -> 1x1 conv,

@@ -77,6 +77,9 @@ SIGNATURES = {
     "tise_is_update": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_int, c_int64, c_int64, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p]),
     "tise_is_finalize": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "tise_calib_workspace_bytes": (c_int, [c_int64, c_int, c_int, POINTER(c_size_t)]),
+    "tise_calib_eval": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_double, c_void_p, c_int, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
     "tise_bias_relu_nhwc": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "tise_avgpool3_bias_relu_nhwc": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                               c_int64, c_int, c_void_p]),

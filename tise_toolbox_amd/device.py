@@ -462,6 +462,53 @@ class InceptionScoreAccumulator:
         return float(o[0]), float(o[1]), o[2:].copy()
 
 
+class CalibrationEvaluator:
+    """NLL / dNLL/dT / ECE bins of temperature-scaled logits (tise_calib_eval): one pass over resident logits per call.
+
+    logits: (rows, ld) fp32 CUDA tensor (row stride ld, unit column stride); the classes are columns [c0, c0 + C) with
+    C = ld - c0 unless given.  labels: (rows,) integer class indices, kept on the device as int32."""
+
+    def __init__(self, logits, labels, c0=0, num_classes=None, n_bins=15):
+        _require_cuda(logits)
+        if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+            raise ValueError("logits must be a (rows, C) float32 tensor with unit column stride")
+        self.logits = logits
+        self.rows = int(logits.shape[0])
+        self.c0 = int(c0)
+        self.C = int(num_classes) if num_classes is not None else int(logits.shape[1]) - self.c0
+        if self.C < 1 or self.c0 < 0 or self.c0 + self.C > logits.shape[1]:
+            raise ValueError(f"classes [{self.c0}, {self.c0 + self.C}) do not fit a row of {logits.shape[1]} logits")
+        labels = torch.as_tensor(labels)
+        if labels.shape != (self.rows,):
+            raise ValueError(f"labels must have shape ({self.rows},), not {tuple(labels.shape)}")
+        self.labels = labels.to(logits.device, torch.int32).contiguous()
+        self.n_bins = int(n_bins)
+        # the reference's bin edges: torch.linspace(0, 1, n_bins + 1) in fp32 on the CPU (temperature_scaling.py:96)
+        self.edges = torch.linspace(0, 1, self.n_bins + 1).to(logits.device)
+        nbytes = ctypes.c_size_t()
+        _lib.call("tise_calib_workspace_bytes", self.rows, self.C, self.n_bins, ctypes.byref(nbytes))
+        self._ws = torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=logits.device)
+        self._out = torch.empty(4 + 3 * self.n_bins, dtype=torch.float64, device=logits.device)
+
+    def raw(self, temperature):
+        """One evaluation -> the 4 + 3 n_bins fp64 sums of tise_calib_eval (numpy)."""
+        _lib.call("tise_calib_eval", _ptr(self.logits), self.rows, self.logits.stride(0), self.c0, self.C,
+                  _ptr(self.labels), float(temperature), _ptr(self.edges), self.n_bins, _ptr(self._out),
+                  _ptr(self._ws), self._ws.numel(), _stream())
+        return self._out.cpu().numpy()
+
+    def __call__(self, temperature):
+        """-> dict(nll_sum, grad_sum, count, conf_sum, correct_sum); raises ValueError on a non-finite logit or a label
+        outside [0, C) (the device counts such rows and leaves them out of every sum)."""
+        o = self.raw(temperature)
+        nb = self.n_bins
+        if o[2] or o[3]:
+            raise ValueError(f"calibration input: {int(o[2])} row(s) with a non-finite logit, {int(o[3])} row(s) with a "
+                             f"label outside [0, {self.C})")
+        return {"nll_sum": float(o[0]), "grad_sum": float(o[1]), "count": o[4:4 + nb].copy(),
+                "conf_sum": o[4 + nb:4 + 2 * nb].copy(), "correct_sum": o[4 + 2 * nb:4 + 3 * nb].copy()}
+
+
 def gemm_f64(a, b):
     """C = A @ B in fp64 through the MFMA tile kernel (any strides); test/bench helper."""
     _require_cuda(a, b)

@@ -92,17 +92,12 @@ def preprocess(img):
     return np.expand_dims(img.astype(np.float32), 0)
 
 
-def get_inception_score(images, splits=10):
-    """inception_score_star_coco.py:32-60: list of image file names -> (mean, std).
-
-    Batched on the device instead of one ``sess.run`` per image (:34,:50); split membership is by
-    global index in the given order (:55).  Under torchrun every rank takes a contiguous index range.
-    """
-    eng = _engine()
-    n = len(images)
+def feed_images(eng, images, lo, hi, begin):
+    """Run ``images[lo:hi]`` through ``eng`` (global indices lo..hi-1) the way IS* does: ``begin()`` opens the image set
+    (called again when the feed falls back to the DataLoader path), then every device batch goes through
+    ``eng.step_u8`` / ``eng.step_u8_list``.  The PNG ring feed by default, the DataLoader for images of mixed sizes."""
     bs = _CONFIG["batch_size"]
-    rank, world, _ = tdist.env_world()
-    lo, hi = tdist.shard_range(n, rank, world)
+    _, world, _ = tdist.env_world()
     # --batch-size is the loader's batch; a trunk pass takes up to engine.device_batch_images of them (split membership
     # is by global index, so batching changes nothing: tests/test_gpu_kernels.py batch invariance)
     from . import png_ring
@@ -110,8 +105,7 @@ def get_inception_score(images, splits=10):
     workers = _CONFIG["num_workers"] if _CONFIG["num_workers"] and _CONFIG["num_workers"] > 0 else png_ring.auto_workers(world)
 
     def run(feed):
-        eng.begin(n_total=n, temperature=_CONFIG["temperature"], splits=splits, rule=_CONFIG["rule"],
-                  drop_first_class=_CONFIG["drop_first_class"])
+        begin()
         eng.reserve_activations(min(hi - lo, device_batch_images(bs)))     # one allocation of the passes' peak (engine.reserve_activations)
         base = lo
         for batch in feed:
@@ -144,6 +138,21 @@ def get_inception_score(images, splits=10):
             ring.close()
     else:
         run(dataloader_feed())
+
+
+def get_inception_score(images, splits=10):
+    """inception_score_star_coco.py:32-60: list of image file names -> (mean, std).
+
+    Batched on the device instead of one ``sess.run`` per image (:34,:50); split membership is by
+    global index in the given order (:55).  Under torchrun every rank takes a contiguous index range.
+    """
+    eng = _engine()
+    n = len(images)
+    rank, world, _ = tdist.env_world()
+    lo, hi = tdist.shard_range(n, rank, world)
+    feed_images(eng, images, lo, hi,
+                lambda: eng.begin(n_total=n, temperature=_CONFIG["temperature"], splits=splits, rule=_CONFIG["rule"],
+                                  drop_first_class=_CONFIG["drop_first_class"]))
     eng.reduce()
     return eng.inception_score()
 
