@@ -28,9 +28,16 @@ gives every rank its own 30 000 images instead.
 (float64, 33.6 MB in all): mu (2048,), sigma (2048, 2048), fid (1,), inception_score (2,) = [mean, std].  The inputs
 (synthetic images, seeded stand-in weights) depend on the flags only, so two builds can be compared file by file.
 
+A plain run does only what the headline needs: set-up, the W + K steps, --dump-outputs, the result line.  `--full` adds
+the legs that run after the timed region and never change `value` (hbm_kernel_probe, host_feed, png_feed, cli_process,
+cpu_baseline, parity, cross_check); their `--no-...` / `--png-images 0` switches still skip single ones.  Without
+`--full` those objects are null.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline      the dominant hand-written kernel of the step loop, timed with HIP events inside the timed region,
-                against its gfx950 bound (DESIGN.md "Measurement")
+                against its gfx950 bound (DESIGN.md "Measurement"); with --full, `kernels` also holds the HBM-bound
+                kernels, each timed alone after the timed region (hbm_kernel_probe)
+  startup_s     seconds from process start to the first warm-up step, by phase
   parity        |dFID|, |dIS| of the device path against the CPU oracle on the first images of the timed set
                 (outside the timed region; N = 1 only)
   cross_check   the whole timed set again through exact-fp32 MIOpen convolutions: |dFID|, |dIS|, max feature error
@@ -241,6 +248,16 @@ def cpu_reference_pass(gen_u8, ref_u8, n_job, dims=2048, workers=8):
     return base, out
 
 
+def _process_age():
+    """Seconds since this process started, from the kernel's clocks (start ticks in /proc/self/stat against /proc/uptime,
+    as fid_score's TISE_TIMING stamps); None where /proc is not there."""
+    try:
+        start_ticks = int(open("/proc/self/stat").read().rsplit(")", 1)[1].split()[19])
+        return float(open("/proc/uptime").read().split()[0]) - start_ticks / os.sysconf("SC_CLK_TCK")
+    except Exception:                                                  # noqa: BLE001
+        return None
+
+
 def dump_outputs(out_dir, mu, sigma, res, is_mean, is_std):
     """What one step hands its caller, as float64 .npy files: mu (2048,), sigma (2048, 2048), fid (1,) and
     inception_score (2,) = [mean, std].  33.6 MB in all."""
@@ -284,6 +301,10 @@ def main():
                          "PNG files and the job is run from the FILES through the CLIs' feed (png_ring.py); 0 skips the leg")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's outputs (mu, sigma, fid, inception_score) to DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs after the timed region that the headline does not need: the HBM kernel probe, "
+                         "host_feed, png_feed + cli_process, cpu_baseline + parity, cross_check (the --no-... switches above "
+                         "skip single ones)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -296,6 +317,8 @@ def main():
     json_fd = os.dup(1)
     os.dup2(2, 1)
 
+    age_main = _process_age()                       # interpreter start + numpy / torch imports
+    t_main = time.perf_counter()
     from tise_toolbox_amd import _lib, device, dist as tdist, fid_score
     from tise_toolbox_amd.engine import RealismEngine, T_COCO, frechet_solver
     coll_note = None
@@ -319,7 +342,9 @@ def main():
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     cl = None if args.channels_last < 0 else bool(args.channels_last)
+    t_eng0 = time.perf_counter()
     eng = RealismEngine(dims=2048, device_index=local_rank, seed=0, with_logits=True, channels_last=cl)
+    t_eng1 = time.perf_counter()
     K, W = args.steps, args.warmup
     n_job = args.batch if args.batch > 0 else args.images      # images per step (a step = the whole job)
     if args.scaling == "strong":
@@ -357,6 +382,15 @@ def main():
                 "note": "sharded over the ranks and all-reduced like the generated side; outside the timed region"}
     solver = frechet_solver(2048, dev)
     solver.set_profiling(True)
+    torch.cuda.synchronize()
+    t_setup = time.perf_counter()
+    age_setup = _process_age()
+    startup = {"process_start_to_warmup": age_setup,
+               "interpreter_and_imports": None if age_main is None else age_main + (t_init0 - t_main),
+               "process_group": t_group_init, "engine": t_eng1 - t_eng0, "inputs": t_ref0 - t_eng1,
+               "reference_side": t_ref2 - t_ref0, "rest": t_setup - t_ref2,
+               "note": "engine includes the stand-in weights (calibrated on the host unless inception.py's cache has them); "
+                       "reference_side includes the communicator's creation"}
 
     # ---- one step = the whole job ----------------------------------------------------------------------
     nch = len(chunks)
@@ -517,7 +551,7 @@ def main():
                 "launches_per_batch": n_launch / timed_steps, "algorithmic_flop_per_batch": conv_flop / timed_steps,
                 "batches_with_events": timed_steps,
                 "mfma_tflops_f16": 3.0 * conv_flop / (conv_ms * 1e-3) / 1e12, "mfma_peak_f16": PEAK_F16_MFMA_TFLOPS}
-        if not args.no_kernel_probe:
+        if args.full and not args.no_kernel_probe:
             kern.update(hbm_kernel_probe(eng, data[chunks[0][0]:chunks[0][1]], dev))
         for k in kern.values():
             k["frac"] = k["achieved"] / k["peak"]
@@ -558,6 +592,7 @@ def main():
                                       "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"),
                                       "launcher": os.environ.get("TISE_BENCH_LAUNCHER", "external" if world > 1 else "none")}},
             "reference_side": ref_side,
+            "full": bool(args.full), "startup_s": startup,
             "ranks": rank_rows,
             "roofline": roofline,
             "stage_ms_per_device_batch": {"resize": resize_ms, "trunk": trunk_ms, "cov_syrk": syrk_ms},
@@ -575,12 +610,12 @@ def main():
         out["cpu_baseline"] = None
         out["cross_check"] = None
         out["host_feed"] = None
-        if world == 1 and not args.no_host_feed:
+        if args.full and world == 1 and not args.no_host_feed:
             out["host_feed"] = host_feed_leg(eng, data, lo, n_total, args.feed_batch, mu_ref, sigma_ref, solver, dev,
                                              float(res["fid"]), rate)
         out["png_feed"] = None
         out["cli_process"] = None
-        if world == 1 and args.png_images > 0:
+        if args.full and world == 1 and args.png_images > 0:
             # the extra legs must never cost the line its headline: a failure is recorded, not raised
             try:
                 out["png_feed"] = png_feed_leg(eng, data, lo, min(args.png_images, n_rank), args.feed_batch, mu_ref, sigma_ref, solver, dev,
@@ -593,7 +628,7 @@ def main():
                 import traceback
                 traceback.print_exc()
                 out["png_feed"] = {"error": f"{type(e).__name__}: {e}"[:400]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # ---- CPU oracle on the first images of the timed set: the baseline AND the parity figures --------
             n_cpu = max(50, (min(args.cpu_sample, n_rank) // 50) * 50)
             gen_u8 = data[:n_cpu].cpu().numpy()
@@ -626,7 +661,7 @@ def main():
                 "dis_std": abs(is_dev[1] - is_cpu[1]),
                 "max_feature_err_rel": float(np.abs(fg.cpu().numpy() - fg_c).max() / np.abs(fg_c).max()),
                 "tolerance": {"dfid": 1e-3, "dis": 1e-4}}
-        if world == 1 and not args.no_cross_check and isinstance(eng.fused, SplitTrunk):
+        if args.full and world == 1 and not args.no_cross_check and isinstance(eng.fused, SplitTrunk):
             cc_chunks = [(a, min(a + 1000, n_rank)) for a in range(0, n_rank, 1000)]      # MIOpen's fp32 activations: 1000 images at a time
             out["cross_check"] = cross_check_fp32(eng, data, cc_chunks, lo, n_total, mu, sigma, mu_ref, sigma_ref,
                                                   float(res["fid"]), (is_mean, is_std), solver, dev)

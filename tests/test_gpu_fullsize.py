@@ -115,7 +115,8 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu(cuda_device, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--steps", "4", "--warmup", "1", "--images", "2000", "--no-cpu-baseline", "--no-cross-check", "--ref-images", "2200"]
     dump = tmp_path / "dump"
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + ["--dump-outputs", str(dump)], cwd=root,
+    # the one-process run also takes the --full legs after its timed region (kernel probe, host_feed, png_feed + cli_process)
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + ["--full", "--dump-outputs", str(dump)], cwd=root,
                          capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads(one.stdout.strip().split("\n")[-1])
@@ -138,6 +139,9 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu(cuda_device, tmp_path):
     assert abs(d2["scores"]["fid"] - d1["scores"]["fid"]) <= 1e-6 and abs(d2["scores"]["is_mean"] - d1["scores"]["is_mean"]) <= 1e-9
     assert d2["roofline"]["frac"] > 0.05 and d2["allreduce_ms"] >= 0.0 and d2["cpu_baseline"] is None
     assert d2["value"] > 0 and abs(d2["ms_per_step"] / 1e3 * d2["value"] - 2000) < 1.0       # value = images / step time
+    assert d1["full"] and not d2["full"] and d2["startup_s"]["process_start_to_warmup"] > 0
+    assert d1["host_feed"]["images"] == 2000 and d1["png_feed"] is not None
+    assert any("probe" in k for k in d1["roofline"]["kernels"].values())
     # --steps 4: four timed steps; ms_per_step is their mean (one process; with two ranks the slower rank's)
     assert len(d1["step_ms"]) == len(d2["step_ms"]) == 4 and abs(sum(d1["step_ms"]) / 4 - d1["ms_per_step"]) <= 1e-3 * d1["ms_per_step"]
     # --dump-outputs: the last step's outputs as float64 arrays, the same numbers as the result line
