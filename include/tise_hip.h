@@ -172,6 +172,11 @@ int tise_eigvalsh(tise_frechet_t* h, const double* a_dev, int n, double* w_dev, 
  * of L, rows >= rank zero); rank_host receives the numerical rank.  Synchronises the stream. */
 int tise_pivoted_cholesky(tise_frechet_t* h, const double* sigma_dev, double* lt_dev,
                           int* rank_host, void* stream);
+/* Test hook: the factor tise_frechet_prefactor left (whichever factorisation produced it).  lt_dev receives
+ * L^T (d x d, row k = column k of L, rows >= rank zero); rank_host the numerical rank; unpivoted_host 1 when
+ * the unpivoted factorisation produced it (L^T upper triangular, natural order), 0 for the pivoted one.
+ * TISE_ERR_INVALID_ARG when nothing is prefactored.  Synchronises the stream. */
+int tise_frechet_factor(tise_frechet_t* h, double* lt_dev, int* rank_host, int* unpivoted_host, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a8, a8', a8'') IS* reduction with temperature.

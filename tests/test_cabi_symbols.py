@@ -42,6 +42,8 @@ def test_argument_validation_without_a_gpu():
     h = ctypes.c_void_p()
     assert lib.tise_stats_create(0, ctypes.byref(h)) == _lib.TISE_ERR_INVALID_ARG
     assert lib.tise_frechet_create(-3, ctypes.byref(h)) == _lib.TISE_ERR_INVALID_ARG
+    r, unpivoted = ctypes.c_int(), ctypes.c_int()
+    assert lib.tise_frechet_factor(None, 0x7f0000000000, ctypes.byref(r), ctypes.byref(unpivoted), None) == _lib.TISE_ERR_INVALID_ARG
     assert lib.tise_stats_update(None, None, 4, 4, None) == _lib.TISE_ERR_INVALID_ARG
     assert lib.tise_is_finalize(None, 10, 10, 10, 0, None, None) == _lib.TISE_ERR_INVALID_ARG
     assert lib.tise_is_update(None, 4, 8, 8, 0.0, 0, 0, 4, 10, 0, None, None, None) == _lib.TISE_ERR_INVALID_ARG

@@ -74,6 +74,7 @@ SIGNATURES = {
     "tise_frechet_phase_ms": (c_int, [c_void_p, POINTER(c_double), POINTER(c_int)]),
     "tise_eigvalsh": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "tise_pivoted_cholesky": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int), c_void_p]),
+    "tise_frechet_factor": (c_int, [c_void_p, c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
     "tise_is_update": (c_int, [c_void_p, c_int64, c_int64, c_int, c_double, c_int, c_int64, c_int64, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p]),
     "tise_is_finalize": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),

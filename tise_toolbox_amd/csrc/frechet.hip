@@ -1356,6 +1356,22 @@ int tise_pivoted_cholesky(tise_frechet_t* h, const double* sigma_dev, double* lt
     return TISE_OK;
 }
 
+int tise_frechet_factor(tise_frechet_t* h, double* lt_dev, int* rank_host, int* unpivoted_host, void* stream) {
+    if (!h || !lt_dev || !rank_host || !unpivoted_host || !h->prefactored) return TISE_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int d = h->d, r = h->pf_rank;
+    TISE_HIP_CHECK(hipStreamWaitEvent(st, h->evp[1], 0));     // the factor was produced on another stream
+    TISE_HIP_CHECK(hipMemcpyAsync(lt_dev, h->lt, (size_t)d * d * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (r < d) {                                               // rows >= r of h->lt are stale scratch
+        hipLaunchKernelGGL(zero_rows_kernel, dim3(256), dim3(256), 0, st, lt_dev, d, r);
+        TISE_LAUNCH_CHECK();
+    }
+    TISE_HIP_CHECK(hipStreamSynchronize(st));
+    *rank_host = r;
+    *unpivoted_host = h->lt_tri;
+    return TISE_OK;
+}
+
 int tise_eigvalsh(tise_frechet_t* h, const double* a_dev, int n, double* w_dev, void* stream) {
     if (!h || !a_dev || !w_dev || n <= 0 || n > h->d) return TISE_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;

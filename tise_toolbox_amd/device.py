@@ -421,6 +421,16 @@ class FrechetSolver:
         _lib.call("tise_pivoted_cholesky", self._h, _ptr(sigma), _ptr(lt), ctypes.byref(r), _stream())
         return lt, r.value
 
+    def factor(self):
+        """The factor prefactor() left: (L^T (d,d) fp64 CUDA tensor, rows >= rank zero; rank; unpivoted) where
+        unpivoted tells which factorisation produced it (True: natural order, L^T upper triangular)."""
+        if getattr(self, "_pf_sigma", None) is None:
+            raise RuntimeError("prefactor() has not been called")
+        lt = torch.empty((self.dims, self.dims), dtype=torch.float64, device=self.device)
+        r, unpivoted = ctypes.c_int(), ctypes.c_int()
+        _lib.call("tise_frechet_factor", self._h, _ptr(lt), ctypes.byref(r), ctypes.byref(unpivoted), _stream())
+        return lt, r.value, bool(unpivoted.value)
+
 
 class InceptionScoreAccumulator:
     """Per-split additive IS* sums on the device (tise_is_update / tise_is_finalize)."""
