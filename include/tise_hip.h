@@ -243,6 +243,13 @@ int tise_avgpool3_bias_relu_nhwc(const float* x_dev, int64_t x_ld, int x_off, in
  * conv output and max(. + bias, 0) is applied (ReLU and max commute). */
 int tise_maxpool3s2_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C,
                          const float* bias_dev, float* out_dev, int64_t out_ld, int out_off, void* stream);
+/* Inception-2015 graph (TensorFlow SAME pools): as tise_avgpool3_bias_relu_nhwc with count_include_pad=False -- the
+ * divisor is the number of taps inside the map (4 at corners, 6 on edges, 9 inside). */
+int tise_avgpool3_excl_bias_relu_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C,
+                                      const float* bias_dev, float* out_dev, int64_t out_ld, int out_off, void* stream);
+/* out (n, h, w) = maxpool3x3(stride 1, pad 1)(x), padding acting as -inf (Inception-2015 Mixed_7c pool branch). */
+int tise_maxpool3s1p1_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, float* out_dev,
+                           int64_t out_ld, int out_off, void* stream);
 
 /* Split-fp16 activations (v ~= hi + lo * 2^-11, the format tise_conv_split_f16 consumes and produces).
  * LAYOUT of a split tensor of C channels (C % 16 == 0): NHWC; inside a pixel the channels come in blocks of 32 with
@@ -258,6 +265,13 @@ int tise_avgpool3_bias_relu_split_nhwc(const float* x_dev, int64_t x_ld, int x_o
 /* 3x3 / stride 2 max pool, split tensor -> split tensor (channel slice [out_off, out_off + C) of out; C % 8 == 0). */
 int tise_maxpool3s2_split_nhwc(const void* x_dev, int64_t x_ld, int x_off, int n, int h, int w,
                                int C, void* out_dev, int64_t out_ld, int out_off, void* stream);
+/* tise_avgpool3_bias_relu_split_nhwc with count_include_pad=False (divisor = taps inside the map). */
+int tise_avgpool3_excl_bias_relu_split_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C,
+                                            const float* bias_dev, void* out_dev, int64_t out_ld, int out_off,
+                                            void* stream);
+/* 3x3 / stride 1 / pad 1 max pool (padding = -inf), split tensor -> split tensor slice (n, h, w); C % 8 == 0. */
+int tise_maxpool3s1p1_split_nhwc(const void* x_dev, int64_t x_ld, int x_off, int n, int h, int w,
+                                 int C, void* out_dev, int64_t out_ld, int out_off, void* stream);
 
 /* Stem layer Conv2d_1a_3x3 (3 -> 32, 3x3, stride 2) from the fp32 NHWC input (n, h, w, 3), folded bias +
  * ReLU + fp16 split fused: out = split tensor (n, oh, ow, 32).  w_dev: [kh][kw][cin][cout] fp32 (27 x 32). */

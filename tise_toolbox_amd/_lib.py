@@ -90,6 +90,14 @@ SIGNATURES = {
                                                     c_void_p, c_int64, c_int, c_void_p]),
     "tise_maxpool3s2_split_nhwc": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                             c_int64, c_int, c_void_p]),
+    "tise_avgpool3_excl_bias_relu_nhwc": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                   c_int64, c_int, c_void_p]),
+    "tise_maxpool3s1p1_nhwc": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int,
+                                        c_void_p]),
+    "tise_avgpool3_excl_bias_relu_split_nhwc": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                                         c_void_p, c_int64, c_int, c_void_p]),
+    "tise_maxpool3s1p1_split_nhwc": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                              c_int64, c_int, c_void_p]),
     "tise_stem_conv3x3s2_split": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "tise_stem_conv3x3s2_split_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                               c_void_p]),

@@ -32,6 +32,7 @@ import torch
 
 from . import device, dist as tdist, weights as tweights
 from .engine import require_gpu
+from .inception import NETWORK_CLASSES, NETWORKS
 
 N_BINS = 15
 
@@ -193,14 +194,14 @@ class _NoStats:
         pass
 
 
-def collect_logits(files, rule="coco", drop_first_class=False, fc_bias="auto", weights=None, num_classes=1000, seed=0,
-                   batch_size=50):
+def collect_logits(files, rule="coco", drop_first_class=False, fc_bias="auto", weights=None, num_classes=None, seed=0,
+                   batch_size=50, network="torchvision"):
     """Image files -> (N, num_classes) fp32 logits on the device (one preallocated buffer) and c0 (1 with
     ``drop_first_class``, else 0).  The images go through inception_score's engine and feed (PNG ring, the rule's
     classifier bias -- inception.fc_bias_for_rule), so the logits are bitwise those IS* divides by T."""
     from . import inception_score as isc
     isc.configure(weights=weights, num_classes=num_classes, seed=seed, rule=rule, drop_first_class=drop_first_class,
-                  fc_bias=fc_bias, batch_size=batch_size)
+                  fc_bias=fc_bias, batch_size=batch_size, network=network)
     eng = isc._engine()
     n = len(files)
     out = torch.empty((n, eng.model.fc.out_features), dtype=torch.float32, device=eng.device)
@@ -233,7 +234,11 @@ def _build_parser():
     parser.add_argument("--weights", type=str, default=None, help="torchvision-format InceptionV3 state_dict (.pth)")
     parser.add_argument("--synthetic-weights", action="store_true",
                         help="seeded stand-in parameters (plumbing only; results are tagged)")
-    parser.add_argument("--num-classes", type=int, default=1000)
+    parser.add_argument("--num-classes", type=int, default=None, help="classifier width (default: 1000, 1008 for --network inception-2015)")
+    parser.add_argument("--network", type=str, default="torchvision", choices=list(NETWORKS),
+                        help="torchvision: torchvision's InceptionV3; inception-2015: the TensorFlow Inception-2015 graph of the "
+                             "reference's IS* for COCO (pytorch-fid's pt_inception-2015-12-05-6726825d.pth: 1008 classes, "
+                             "exclude-padding average pools, max-pool branch in Mixed_7c, input (v - 128) / 128)")
     parser.add_argument("--seed", type=int, default=0, help="seed of the --synthetic-weights parameters")
     parser.add_argument("--batch-size", type=int, default=50)
     parser.add_argument("--init-temp", type=float, default=1.0)
@@ -248,6 +253,8 @@ def _build_parser():
 
 def main(argv=None):
     args = _build_parser().parse_args(argv)
+    if args.num_classes is None:
+        args.num_classes = NETWORK_CLASSES[args.network]
     if tdist.env_world()[1] > 1:
         raise SystemExit("tise_toolbox_amd.calibration runs in one process: start it without torchrun "
                          "(the logits of a validation set fit one GPU)")
@@ -260,7 +267,7 @@ def main(argv=None):
         c0 = 1 if args.drop_first_class else 0
     else:
         wpath, tag = tweights.resolve(args.weights, args.synthetic_weights,
-                                      "inception80" if args.rule == "ois" and args.num_classes == 80 else "inception")
+                                      tweights.inception_kind(args.network, args.rule == "ois" and args.num_classes == 80))
         n_cls = args.num_classes - (1 if args.drop_first_class else 0)
         if args.labels == "subdirs":
             files, labels, _ = labels_from_subdirs(args.image_dir)
@@ -272,7 +279,7 @@ def main(argv=None):
         from .engine import run_with_exact_fallback
         logits, c0 = run_with_exact_fallback(
             lambda: collect_logits(files, args.rule, args.drop_first_class, args.fc_bias, wpath, args.num_classes,
-                                   args.seed, args.batch_size), "the logit collection")
+                                   args.seed, args.batch_size, args.network), "the logit collection")
         if args.save_features:
             np.savez(args.save_features, features=logits.cpu().numpy(), labels=labels)
     res = set_temperature_from_logits(logits, labels, args.init_temp, args.lr, args.max_iter, args.n_bins, c0, verbose=False)

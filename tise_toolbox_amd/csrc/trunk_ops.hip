@@ -16,6 +16,8 @@
 //                         torchvision InceptionA/C/E branch_pool).
 //   maxpool3s2            3x3 / stride 2 max pool, optionally max(. + b, 0) first (ReLU and max commute),
 //                         writing into a concat slice (InceptionB/D pool branch) or a packed tensor (stem).
+//   avgpool3_excl_*       the same average with count_include_pad=False (Inception-2015 graph, TensorFlow SAME pools).
+//   maxpool3s1p1          3x3 / stride 1 / pad 1 max pool, padding = -inf (Inception-2015 Mixed_7c pool branch).
 //
 // All are float4-vectorised along the channel dimension (every channel count / offset in the
 // network is a multiple of 16).  Algorithmic bytes: one read + one write of the tensor (+8 neighbour
@@ -45,6 +47,11 @@ __global__ __launch_bounds__(256) void bias_relu_nhwc_kernel(const float* __rest
     }
 }
 
+// EXCL: the divisor is the number of taps inside the map (count_include_pad=False; TensorFlow's SAME average, the
+// Inception-2015 graph's pool branches): 4 at corners, 6 on edges, 9 inside.  The raw-conv-then-pool order of the trunk
+// stays valid for it: the tap weights 1/count depend on the position only (the pool is still linear and commutes with
+// the 1x1 conv) and sum to 1 at every position, so pool(conv(x) + b) = pool(conv(x)) + b and the bias may follow the pool.
+template <bool EXCL>
 __global__ __launch_bounds__(256) void avgpool3_bias_relu_nhwc_kernel(const float* __restrict__ x, int64_t x_ld,
                                                                       int x_off, int N, int H, int W, int C4,
                                                                       const float* __restrict__ bias,
@@ -69,7 +76,9 @@ __global__ __launch_bounds__(256) void avgpool3_bias_relu_nhwc_kernel(const floa
                 s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
             }
         }
-        s.x /= 9.f; s.y /= 9.f; s.z /= 9.f; s.w /= 9.f;      // count_include_pad=True: always / 9
+        // count_include_pad=True: always / 9; EXCL: / (taps inside the map)
+        const float d = EXCL ? (float)((1 + (h > 0) + (h + 1 < H)) * (1 + (w > 0) + (w + 1 < W))) : 9.f;
+        s.x /= d; s.y /= d; s.z /= d; s.w /= d;
         const float4 b = *reinterpret_cast<const float4*>(bias + 4 * c4);
         *reinterpret_cast<float4*>(out + p * out_ld + out_off + 4 * c4) = f4_bias_relu(s, b);
     }
@@ -110,9 +119,11 @@ __global__ __launch_bounds__(256) void maxpool3s2_nhwc_kernel(const float* __res
 typedef _Float16 half8v __attribute__((ext_vector_type(8)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 
-// fp32 raw 1x1-conv output (slice) -> 3x3/s1/p1 average (count_include_pad) + bias, ReLU -> split tensor slice.
+// fp32 raw 1x1-conv output (slice) -> 3x3/s1/p1 average (count_include_pad; EXCL: count_include_pad=False, as
+// avgpool3_bias_relu_nhwc_kernel) + bias, ReLU -> split tensor slice.
 // Thread = (pixel, 8 channels): two 16-byte loads per tap, one 16-byte store per half (the pool branch's channel
 // counts are 32, 64 and 192).  Summation order per channel: (dh, dw) row-major, as the 4-channel form had.
+template <bool EXCL>
 __global__ __launch_bounds__(256) void avgpool3_bias_relu_split_kernel(const float* __restrict__ x, int64_t x_ld,
                                                                        int x_off, int N, int H, int W, int C8,
                                                                        const float* __restrict__ bias,
@@ -139,8 +150,10 @@ __global__ __launch_bounds__(256) void avgpool3_bias_relu_split_kernel(const flo
                 s1.x += v1.x; s1.y += v1.y; s1.z += v1.z; s1.w += v1.w;
             }
         }
-        s0.x /= 9.f; s0.y /= 9.f; s0.z /= 9.f; s0.w /= 9.f;      // count_include_pad=True: always / 9
-        s1.x /= 9.f; s1.y /= 9.f; s1.z /= 9.f; s1.w /= 9.f;
+        // count_include_pad=True: always / 9; EXCL: / (taps inside the map)
+        const float div = EXCL ? (float)((1 + (h > 0) + (h + 1 < H)) * (1 + (w > 0) + (w + 1 < W))) : 9.f;
+        s0.x /= div; s0.y /= div; s0.z /= div; s0.w /= div;
+        s1.x /= div; s1.y /= div; s1.z /= div; s1.w /= div;
         const float4 r0 = f4_bias_relu(s0, *reinterpret_cast<const float4*>(bias + 8 * c8));
         const float4 r1 = f4_bias_relu(s1, *reinterpret_cast<const float4*>(bias + 8 * c8 + 4));
         const float v[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
@@ -165,6 +178,7 @@ __global__ __launch_bounds__(256) void avgpool3_bias_relu_split_kernel(const flo
 // loads) instead of 9 (18 loads), and the index arithmetic is 32-bit and done once per thread, not per output
 // (the per-output form reached 2.6-3.3 TB/s of algorithmic bytes: bound by its 18 loads and 64-bit divisions, not by
 // HBM).  Summation order per channel: ((left + centre) + right) per row, then (above + this) + below.
+template <bool EXCL>
 __global__ __launch_bounds__(256) void avgpool3_bias_relu_split_colwalk_kernel(const float* __restrict__ x, int x_ld, int x_off,
                                                                                int N, int H, int W, int C8,
                                                                                const float* __restrict__ bias,
@@ -176,6 +190,7 @@ __global__ __launch_bounds__(256) void avgpool3_bias_relu_split_colwalk_kernel(c
     const unsigned col = e / (unsigned)C8;
     const unsigned w = col % (unsigned)W, n = col / (unsigned)W;
     const bool hasl = w > 0, hasr = w + 1 < (unsigned)W;
+    const int ncols = 1 + (int)hasl + (int)hasr;              // EXCL: taps of a row inside the map
     const float* base = x + ((size_t)n * H * W + w) * (size_t)x_ld + x_off + 8 * c8;
     const size_t rstride = (size_t)W * x_ld;
     const float4 b0 = *reinterpret_cast<const float4*>(bias + 8 * c8), b1 = *reinterpret_cast<const float4*>(bias + 8 * c8 + 4);
@@ -219,10 +234,12 @@ __global__ __launch_bounds__(256) void avgpool3_bias_relu_split_colwalk_kernel(c
 #pragma unroll
             for (int i = 0; i < 8; ++i) hs[2][i] = 0.f;
         }
+        // count_include_pad=True: always / 9; EXCL: / (taps inside the map)
+        const float div = EXCL ? (float)((1 + (y > 0) + (y + 1 < H)) * ncols) : 9.f;
         half8v hi, lo;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const float v = fmaxf(((hs[0][i] + hs[1][i]) + hs[2][i]) / 9.f + bs[i], 0.f);      // count_include_pad=True: always / 9
+            const float v = fmaxf(((hs[0][i] + hs[1][i]) + hs[2][i]) / div + bs[i], 0.f);
             vmax = fmaxf(vmax, v);
             hi[i] = (_Float16)v;
             lo[i] = (_Float16)((v - (float)hi[i]) * 2048.f);
@@ -287,6 +304,78 @@ __global__ __launch_bounds__(256) void maxpool3s2_split_kernel(const _Float16* _
         *reinterpret_cast<half8v*>(d) = bh;                      // (non-temporal stores measured 1 % slower here)
         *reinterpret_cast<half8v*>(d + tise_ilv_second(ch, out_C)) = bl;
     }
+}
+
+// 3x3 / stride 1 / pad 1 max pool, the pool branch of the Inception-2015 graph's last block (Mixed_7c: max-pool, then its
+// 1x1 conv; max does not commute with the conv, so the pool runs first, on the block input).  Padding acts as -inf: taps
+// outside the map are skipped (the centre tap always lies inside).  fp32 form (exact path): thread = (pixel, 4 channels).
+__global__ __launch_bounds__(256) void maxpool3s1p1_nhwc_kernel(const float* __restrict__ x, int64_t x_ld, int x_off,
+                                                                int N, int H, int W, int C4, float* __restrict__ out,
+                                                                int64_t out_ld, int out_off) {
+    const int64_t total = (int64_t)N * H * W * C4;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = e / C4;
+        const int c4 = (int)(e - p * C4);
+        const int w = (int)(p % W);
+        const int h = (int)((p / W) % H);
+        float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+#pragma unroll
+        for (int dh = -1; dh <= 1; ++dh) {
+            const int hh = h + dh;
+            if (hh < 0 || hh >= H) continue;
+#pragma unroll
+            for (int dw = -1; dw <= 1; ++dw) {
+                const int ww = w + dw;
+                if (ww < 0 || ww >= W) continue;
+                const float4 v = *reinterpret_cast<const float4*>(x + (p + (int64_t)dh * W + dw) * x_ld + x_off + 4 * c4);
+                m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+            }
+        }
+        *reinterpret_cast<float4*>(out + p * out_ld + out_off + 4 * c4) = m;
+    }
+}
+
+// Split form of the kernel above (split tensor -> split tensor slice, 8 channels per thread, image = blockIdx.y), with the
+// value arithmetic of maxpool3s2_split_kernel: the maximum of the exact fp32 values hi + lo * 2^-11, split again -- the
+// pooled tensor carries the winning tap's value, so a 1x1 conv on it is the conv of max_pool2d's result.
+__global__ __launch_bounds__(256) void maxpool3s1p1_split_kernel(const _Float16* __restrict__ x, int x_C, int x_off,
+                                                                 int N, int H, int W, int C8,
+                                                                 _Float16* __restrict__ out, int out_C, int out_off) {
+    const unsigned per_img = (unsigned)H * (unsigned)W * (unsigned)C8;
+    const unsigned e = blockIdx.x * 256u + threadIdx.x;
+    if (e >= per_img) return;
+    const unsigned pix = e / (unsigned)C8;
+    const int c8 = (int)(e - pix * (unsigned)C8);
+    const int h = (int)(pix / (unsigned)W), w = (int)(pix - (unsigned)h * (unsigned)W);
+    const int64_t n = blockIdx.y;
+    const int64_t p = n * H * W + pix;
+    const int xo = tise_ilv_off(x_off + 8 * c8, x_C), xs = tise_ilv_second(x_off + 8 * c8, x_C);
+    float bv[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bv[i] = -INFINITY;
+#pragma unroll
+    for (int dh = -1; dh <= 1; ++dh) {
+        if (h + dh < 0 || h + dh >= H) continue;
+#pragma unroll
+        for (int dw = -1; dw <= 1; ++dw) {
+            if (w + dw < 0 || w + dw >= W) continue;
+            const _Float16* q = x + (p + (int64_t)dh * W + dw) * (2 * (int64_t)x_C) + xo;
+            const half8v vh = *reinterpret_cast<const half8v*>(q);
+            const half8v vl = *reinterpret_cast<const half8v*>(q + xs);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) bv[i] = fmaxf(bv[i], (float)vh[i] + (float)vl[i] * (1.f / 2048.f));
+        }
+    }
+    half8v bh, bl;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        bh[i] = (_Float16)bv[i];
+        bl[i] = (_Float16)((bv[i] - (float)bh[i]) * 2048.f);
+    }
+    const int ch = out_off + 8 * c8;
+    _Float16* d = out + p * (2 * (int64_t)out_C) + tise_ilv_off(ch, out_C);
+    *reinterpret_cast<half8v*>(d) = bh;
+    *reinterpret_cast<half8v*>(d + tise_ilv_second(ch, out_C)) = bl;
 }
 
 // Stem convolution Conv2d_1a_3x3 (3 -> 32 channels, 3x3, stride 2, no padding; torchvision Inception3 /
@@ -488,6 +577,41 @@ inline int grid_for(int64_t total) {
 
 inline bool aligned4(int64_t a, int b, int c) { return (a % 4 == 0) && (b % 4 == 0) && (c % 4 == 0); }
 
+template <bool EXCL>
+int avgpool_nhwc_launch(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, const float* bias_dev,
+                        float* out_dev, int64_t out_ld, int out_off, void* stream) {
+    if (!x_dev || !bias_dev || !out_dev || n < 0 || h <= 0 || w <= 0 || C <= 0 || !aligned4(x_ld, x_off, C) ||
+        !aligned4(out_ld, out_off, C) || x_off + C > x_ld || out_off + C > out_ld)
+        return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    hipLaunchKernelGGL(avgpool3_bias_relu_nhwc_kernel<EXCL>, dim3(grid_for((int64_t)n * h * w * (C / 4))), dim3(256), 0,
+                       (hipStream_t)stream, x_dev, x_ld, x_off, n, h, w, C / 4, bias_dev, out_dev, out_ld, out_off);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+template <bool EXCL>
+int avgpool_split_launch(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, const float* bias_dev,
+                         void* out_dev, int64_t out_ld, int out_off, void* stream) {
+    if (!x_dev || !bias_dev || !out_dev || n < 0 || h <= 0 || w <= 0 || C <= 0 || C % 8 || x_ld % 4 || x_off % 4 ||
+        out_off % 8 || out_ld % 16 || x_off + C > x_ld || out_off + C > out_ld || out_ld > 0x7fffffff ||
+        (reinterpret_cast<uintptr_t>(bias_dev) & 15) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    const int64_t cols = (int64_t)n * w * (C / 8);
+    static const bool per_output = getenv("TISE_AVGPOOL_PER_OUTPUT") != nullptr;      // A/B switch: round 2's kernel
+    if (!per_output && cols < 0x7fffff00LL && x_ld < 0x7fffffffLL && (reinterpret_cast<uintptr_t>(x_dev) & 15) == 0)
+        hipLaunchKernelGGL(avgpool3_bias_relu_split_colwalk_kernel<EXCL>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, x_dev, (int)x_ld, x_off, n, h, w, C / 8, bias_dev,
+                           reinterpret_cast<_Float16*>(out_dev), (int)out_ld, out_off);
+    else
+        hipLaunchKernelGGL(avgpool3_bias_relu_split_kernel<EXCL>, dim3(grid_for((int64_t)n * h * w * (C / 8))), dim3(256), 0,
+                           (hipStream_t)stream, x_dev, x_ld, x_off, n, h, w, C / 8, bias_dev,
+                           reinterpret_cast<_Float16*>(out_dev), (int)out_ld, out_off);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -506,14 +630,12 @@ int tise_bias_relu_nhwc(const float* x_dev, int64_t x_ld, int x_off, int64_t pix
 
 int tise_avgpool3_bias_relu_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C,
                                  const float* bias_dev, float* out_dev, int64_t out_ld, int out_off, void* stream) {
-    if (!x_dev || !bias_dev || !out_dev || n < 0 || h <= 0 || w <= 0 || C <= 0 || !aligned4(x_ld, x_off, C) ||
-        !aligned4(out_ld, out_off, C) || x_off + C > x_ld || out_off + C > out_ld)
-        return TISE_ERR_INVALID_ARG;
-    if (n == 0) return TISE_OK;
-    hipLaunchKernelGGL(avgpool3_bias_relu_nhwc_kernel, dim3(grid_for((int64_t)n * h * w * (C / 4))), dim3(256), 0,
-                       (hipStream_t)stream, x_dev, x_ld, x_off, n, h, w, C / 4, bias_dev, out_dev, out_ld, out_off);
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    return avgpool_nhwc_launch<false>(x_dev, x_ld, x_off, n, h, w, C, bias_dev, out_dev, out_ld, out_off, stream);
+}
+
+int tise_avgpool3_excl_bias_relu_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C,
+                                      const float* bias_dev, float* out_dev, int64_t out_ld, int out_off, void* stream) {
+    return avgpool_nhwc_launch<true>(x_dev, x_ld, x_off, n, h, w, C, bias_dev, out_dev, out_ld, out_off, stream);
 }
 
 int tise_maxpool3s2_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, const float* bias_dev,
@@ -537,21 +659,37 @@ int tise_maxpool3s2_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int
 int tise_avgpool3_bias_relu_split_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C,
                                        const float* bias_dev, void* out_dev, int64_t out_ld, int out_off,
                                        void* stream) {
-    if (!x_dev || !bias_dev || !out_dev || n < 0 || h <= 0 || w <= 0 || C <= 0 || C % 8 || x_ld % 4 || x_off % 4 ||
-        out_off % 8 || out_ld % 16 || x_off + C > x_ld || out_off + C > out_ld || out_ld > 0x7fffffff ||
-        (reinterpret_cast<uintptr_t>(bias_dev) & 15) != 0)
+    return avgpool_split_launch<false>(x_dev, x_ld, x_off, n, h, w, C, bias_dev, out_dev, out_ld, out_off, stream);
+}
+
+int tise_avgpool3_excl_bias_relu_split_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C,
+                                            const float* bias_dev, void* out_dev, int64_t out_ld, int out_off,
+                                            void* stream) {
+    return avgpool_split_launch<true>(x_dev, x_ld, x_off, n, h, w, C, bias_dev, out_dev, out_ld, out_off, stream);
+}
+
+int tise_maxpool3s1p1_nhwc(const float* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, float* out_dev,
+                           int64_t out_ld, int out_off, void* stream) {
+    if (!x_dev || !out_dev || n < 0 || h <= 0 || w <= 0 || C <= 0 || !aligned4(x_ld, x_off, C) ||
+        !aligned4(out_ld, out_off, C) || x_off + C > x_ld || out_off + C > out_ld)
         return TISE_ERR_INVALID_ARG;
     if (n == 0) return TISE_OK;
-    const int64_t cols = (int64_t)n * w * (C / 8);
-    static const bool per_output = getenv("TISE_AVGPOOL_PER_OUTPUT") != nullptr;      // A/B switch: round 2's kernel
-    if (!per_output && cols < 0x7fffff00LL && x_ld < 0x7fffffffLL && (reinterpret_cast<uintptr_t>(x_dev) & 15) == 0)
-        hipLaunchKernelGGL(avgpool3_bias_relu_split_colwalk_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0,
-                           (hipStream_t)stream, x_dev, (int)x_ld, x_off, n, h, w, C / 8, bias_dev,
-                           reinterpret_cast<_Float16*>(out_dev), (int)out_ld, out_off);
-    else
-        hipLaunchKernelGGL(avgpool3_bias_relu_split_kernel, dim3(grid_for((int64_t)n * h * w * (C / 8))), dim3(256), 0,
-                           (hipStream_t)stream, x_dev, x_ld, x_off, n, h, w, C / 8, bias_dev,
-                           reinterpret_cast<_Float16*>(out_dev), (int)out_ld, out_off);
+    hipLaunchKernelGGL(maxpool3s1p1_nhwc_kernel, dim3(grid_for((int64_t)n * h * w * (C / 4))), dim3(256), 0,
+                       (hipStream_t)stream, x_dev, x_ld, x_off, n, h, w, C / 4, out_dev, out_ld, out_off);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+int tise_maxpool3s1p1_split_nhwc(const void* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C,
+                                 void* out_dev, int64_t out_ld, int out_off, void* stream) {
+    if (!x_dev || !out_dev || n < 0 || h <= 0 || w <= 0 || C <= 0 || C % 8 || x_ld % 16 || x_off % 8 || out_ld % 16 ||
+        out_off % 8 || x_off + C > x_ld || out_off + C > out_ld || x_ld > 0x7fffffff || out_ld > 0x7fffffff)
+        return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    if (n > 65535 || (int64_t)h * w * (C / 8) >= 0x7fffff00LL) return TISE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(maxpool3s1p1_split_kernel, dim3((unsigned)(((int64_t)h * w * (C / 8) + 255) / 256), (unsigned)n), dim3(256), 0,
+                       (hipStream_t)stream, reinterpret_cast<const _Float16*>(x_dev), (int)x_ld, x_off, n, h, w, C / 8,
+                       reinterpret_cast<_Float16*>(out_dev), (int)out_ld, out_off);
     TISE_LAUNCH_CHECK();
     return TISE_OK;
 }

@@ -103,14 +103,23 @@ def _require_cuda(*tensors):
             raise _lib.TiseLibraryError("tise_toolbox_amd runs on MI355X only: tensor is not on a HIP device")
 
 
-def make_lut(normalize_input=True, scale_pm1=False):
+def make_lut(normalize_input=True, scale_pm1=False, network="torchvision"):
     """3x256 fp32 table: byte -> network input value, with the reference's own op order.
 
     ToTensor (fid_score.py:211): fp32(v) / 255 (true division, fp32).  Then either the
     inception.py:120-124 affine ``x * (s/0.5) + (m-0.5)/0.5`` (fp32 multiply, fp32 add, Python
     scalars rounded to fp32 first, as torch does for tensor-scalar ops) or, for O-IS,
     Normalize((.5,.5,.5),(.5,.5,.5)) = (x - 0.5) / 0.5 (object_centric_inception_score.py:91).
+    ``network="inception-2015"`` (with ``normalize_input``): the 2015 graph's input map (v - 128) / 128 on the byte value v,
+    every channel (fp32; constants in inception.INCEPTION_2015_INPUT_SUB / _DIV).
     """
+    if network == "inception-2015" and normalize_input and not scale_pm1:
+        from .inception import INCEPTION_2015_INPUT_DIV, INCEPTION_2015_INPUT_SUB
+        b = np.arange(256, dtype=np.float32)
+        row = (b - np.float32(INCEPTION_2015_INPUT_SUB)) / np.float32(INCEPTION_2015_INPUT_DIV)
+        return np.ascontiguousarray(np.tile(row, (3, 1)).astype(np.float32))
+    if network not in ("torchvision", "inception-2015"):
+        raise ValueError(f"unknown network {network!r}")
     v = np.arange(256, dtype=np.float32) / np.float32(255.0)
     lut = np.empty((3, 256), dtype=np.float32)
     for c in range(3):

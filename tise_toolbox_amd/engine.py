@@ -63,9 +63,11 @@ def run_with_exact_fallback(fn, what="the evaluation"):
 
 
 class RealismEngine:
-    def __init__(self, dims=2048, device_index=None, weights=None, num_classes=1000, seed=0,
+    def __init__(self, dims=2048, device_index=None, weights=None, num_classes=None, seed=0,
                  channels_last=None, fold_bn=True, with_logits=False, model=None, normalize_input=True,
-                 lut=None, fused=None, fc_bias="auto"):
+                 lut=None, fused=None, fc_bias="auto", network="torchvision"):
+        """``network``: inception.NETWORKS -- "inception-2015" builds the TensorFlow Inception-2015 graph's variant of the
+        model (its pools, 1008-class head unless ``num_classes`` says otherwise) and its input table (device.make_lut)."""
         require_gpu()
         if device_index is None:
             device_index = torch.cuda.current_device()
@@ -86,7 +88,7 @@ class RealismEngine:
         if model is None:
             block = InceptionV3.BLOCK_INDEX_BY_DIM[dims]
             model = InceptionV3([block], weights=weights, num_classes=num_classes, seed=seed,
-                                normalize_input=normalize_input)
+                                normalize_input=normalize_input, network=network)
         from .inception import to_device_flat
         self.model = to_device_flat(model, self.device).eval()              # model.to(device), one copy per dtype
         # every rank must run the SAME parameters: the stand-in weights are calibrated with CPU convolutions
@@ -97,7 +99,8 @@ class RealismEngine:
         if fold_bn and hasattr(self.model, "fold_bn"):
             self.model.fold_bn(torch.channels_last if channels_last else torch.contiguous_format)
         if lut is None:
-            lut = device.make_lut(normalize_input=getattr(self.model, "normalize_input", True))
+            lut = device.make_lut(normalize_input=getattr(self.model, "normalize_input", True),
+                                  network=getattr(self.model, "network", "torchvision"))
         self.lut = lut
         # MIOpen convs + hand-written HIP epilogues (trunk.py); TISE_FUSED_TRUNK=0 runs the plain module graph
         self.fused = None

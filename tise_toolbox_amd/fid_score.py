@@ -40,7 +40,7 @@ import torch.utils.data
 from . import _lib, device, dist as tdist, img_data, weights as tweights
 from .engine import (RealismEngine, coalesce_batches, coalesce_u8, device_batch_images, frechet_solver, require_gpu,
                      run_with_exact_fallback)
-from .inception import InceptionV3
+from .inception import NETWORK_CLASSES, NETWORKS, InceptionV3
 
 warnings.filterwarnings("ignore")          # fid_score.py:49
 _T_IMPORT1 = time.time()
@@ -74,7 +74,11 @@ def _build_parser():
     parser.add_argument("--path2", type=str, required=True)
     parser.add_argument("--saved_file", type=str, default="")
     parser.add_argument("--weights", type=str, default=None, help="torchvision-format InceptionV3 state_dict (.pth)")
-    parser.add_argument("--num-classes", type=int, default=1000)
+    parser.add_argument("--num-classes", type=int, default=None, help="classifier width (default: 1000, 1008 for --network inception-2015)")
+    parser.add_argument("--network", type=str, default="torchvision", choices=list(NETWORKS),
+                        help="torchvision: torchvision's InceptionV3 (the reference's FID wrapper); inception-2015: the "
+                             "TensorFlow Inception-2015 graph pytorch-fid and TTUR take FID on (pt_inception-2015-12-05-6726825d.pth); "
+                             "--save-stats then tags the .npz with network=inception-2015")
     parser.add_argument("--synthetic-weights", action="store_true",
                         help="seeded stand-in parameters (plumbing / throughput only; results are tagged)")
     parser.add_argument("--seed", type=int, default=0, help="seed of the --synthetic-weights parameters")
@@ -313,7 +317,9 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
     if path.endswith(".npz"):
         f = np.load(path, allow_pickle=True)              # :201-203
         m, s = f["mu"][:], f["sigma"][:]
+        tag = str(f["network"]) if "network" in f.files else None
         f.close()
+        check_stats_network(path, tag, getattr(model, "network", "torchvision"))
         return m, s
     files = img_data.get_filenames(path)                  # os.walk order (img_data.py:27-35)
     rank, world, _ = tdist.env_world()
@@ -417,16 +423,33 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
     return out
 
 
-def _build_model(dims, weights, num_classes, seed):
+def stats_network_tag(network):
+    """Extra arrays of a statistics .npz: ``network`` for the Inception-2015 graph only, so that the default network's files
+    stay exactly the {mu, sigma} files of the reference (and of pytorch-fid)."""
+    return {} if network == "torchvision" else {"network": np.asarray(network)}
+
+
+def check_stats_network(path, tag, network):
+    """A tagged .npz was made on ``tag``'s network: statistics of one network do not compare with features of another.
+    Untagged files (the reference's, pytorch-fid's, the default network's) load as they always did."""
+    if tag is not None and tag != network:
+        raise RuntimeError(f"{path}: statistics of network {tag!r}, this run uses --network {network}")
+
+
+def save_stats_npz(path, mu, sigma, network="torchvision"):
+    np.savez(path, mu=np.asarray(mu), sigma=np.asarray(sigma), **stats_network_tag(network))
+
+
+def _build_model(dims, weights, num_classes, seed, network="torchvision"):
     block_idx = InceptionV3.BLOCK_INDEX_BY_DIM[dims]
-    model = InceptionV3([block_idx], weights=weights, num_classes=num_classes, seed=seed)
+    model = InceptionV3([block_idx], weights=weights, num_classes=num_classes, seed=seed, network=network)
     from .inception import to_device_flat
     to_device_flat(model, torch.device("cuda", torch.cuda.current_device()))     # model.cuda() (fid_score.py:232-233) in one copy
     return model
 
 
 @contextlib.contextmanager
-def _own_model(dims, weights, num_classes, seed):
+def _own_model(dims, weights, num_classes, seed, network="torchvision"):
     """The model of ONE call of this module's path-level functions.
 
     _engine_for hangs the engine on the model and the engine holds the model: a reference cycle, so a finished call's ~1.4 GiB of
@@ -437,7 +460,7 @@ def _own_model(dims, weights, num_classes, seed):
     prompt release in place two of thirteen runs of tests/test_gpu_pipeline.py failed in tests that had never failed before
      and the cause was not found in what was left of round 6 -- the collector-driven release is the
     behaviour of rounds 1-5."""
-    model = _build_model(dims, weights, num_classes, seed)
+    model = _build_model(dims, weights, num_classes, seed, network)
     try:
         yield model
     finally:
@@ -448,8 +471,8 @@ def _own_model(dims, weights, num_classes, seed):
                 pass
 
 
-def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=1000, seed=0,
-                              save_stats="", num_workers=8, u8_cache=False):
+def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0,
+                              save_stats="", num_workers=8, u8_cache=False, network="torchvision"):
     """Calculates the FID of two paths (fid_score.py:223-238).  ``weights=None`` = seeded stand-in parameters (the
     CLI only allows that behind --synthetic-weights)."""
     for p in paths:
@@ -471,7 +494,7 @@ def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_c
         torch.cuda.synchronize()
         print(f"[tise timing] prealloc {os.environ['TISE_PREALLOC_GB']} GB: {time.perf_counter() - tp:.3f} s", file=sys.stderr, flush=True)
         del _x
-    with _own_model(dims, weights, num_classes, seed) as model:
+    with _own_model(dims, weights, num_classes, seed, network) as model:
         _engine_for(model, dims)                               # fold BatchNorm, pack the split weights, load the code objects
         t = _timing("model + engine ready", t)
         m1, s1 = _compute_statistics_of_path(paths[0], model, batch_size, dims, cuda, num_workers, u8_cache)
@@ -486,7 +509,7 @@ def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_c
         m2, s2 = _compute_statistics_of_path(paths[1], model, batch_size, dims, cuda, num_workers, u8_cache)
         t = _timing("second side done", t)
         if save_stats and tdist.is_main():
-            np.savez(save_stats, mu=np.asarray(m2), sigma=np.asarray(s2))
+            save_stats_npz(save_stats, m2, s2, network)
         if not use_pf or np.shape(m1) != np.shape(m2) or np.shape(s1) != np.shape(s2):
             return calculate_frechet_distance(m1, s1, m2, s2)     # generic path (shape asserts :149-150 included)
         try:
@@ -501,8 +524,8 @@ def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_c
         return np.float64(res["fid"])
 
 
-def save_statistics_of_path(path, out_npz, batch_size, cuda, dims, weights=None, num_classes=1000, seed=0,
-                            num_workers=8, u8_cache=False):
+def save_statistics_of_path(path, out_npz, batch_size, cuda, dims, weights=None, num_classes=None, seed=0,
+                            num_workers=8, u8_cache=False, network="torchvision"):
     """STATS-ONLY mode: the step BEFORE the reference path -- write the ``.npz {mu, sigma}`` that
     ``_compute_statistics_of_path`` (fid_score.py:200-203) reads (the reference ships such files,
     download_evaluation_data.py:11-12, but no script that makes them).  No Frechet distance is solved."""
@@ -511,10 +534,10 @@ def save_statistics_of_path(path, out_npz, batch_size, cuda, dims, weights=None,
     _check_cuda(cuda)
     if not u8_cache:
         prefetch_png_ring(path, batch_size, num_workers)   # decode overlaps building the model
-    with _own_model(dims, weights, num_classes, seed) as model:
+    with _own_model(dims, weights, num_classes, seed, network) as model:
         mu, sigma = _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers, u8_cache)
         if tdist.is_main():
-            np.savez(out_npz, mu=np.asarray(mu), sigma=np.asarray(sigma))
+            save_stats_npz(out_npz, mu, sigma, network)
         return mu, sigma
 
 
@@ -599,7 +622,7 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None):
 
 
 def calculate_per_class_fid(paths, batch_size, cuda, dims, weights=None, num_classes=80, seed=0, num_workers=8,
-                            min_count=2):
+                            min_count=2, network="torchvision"):
     """EXTENSION (BASELINE configs[4]; the reference computes ONE O-FID over all crops): a Frechet
     distance per object class.  Returns (OrderedDict class -> fid, skipped) where ``skipped`` lists classes with
     fewer than ``min_count`` crops on either side (covariance undefined)."""
@@ -608,7 +631,7 @@ def calculate_per_class_fid(paths, batch_size, cuda, dims, weights=None, num_cla
         if not os.path.isdir(p):
             raise RuntimeError("Invalid path: %s" % p)
     _check_cuda(cuda)
-    with _own_model(dims, weights, num_classes, seed) as model:
+    with _own_model(dims, weights, num_classes, seed, network) as model:
         # the class list comes from the file names alone: the sorted union over both directories, identical on every rank,
         # dealt round-robin to the ranks
         present = [set(class_of_crop(f) for f in img_data.get_filenames(p)) for p in paths]
@@ -704,6 +727,8 @@ def _solve_classes(pairs, dims, dev, eps=1e-6):
 def main(argv=None):
     parser = _build_parser()
     args = parser.parse_args(argv)
+    if args.num_classes is None:
+        args.num_classes = NETWORK_CLASSES[args.network]
     _timing(f"imports done (this module's imports {_T_IMPORT1 - _T_IMPORT0:.2f} s)")
     if args.gpu == "":
         _check_cuda(False)
@@ -715,14 +740,14 @@ def main(argv=None):
     _PNG_FEED["mode"] = args.png_feed
     if args.conv is not None:
         os.environ["TISE_CONV"] = "miopen" if args.conv == "exact" else "split"
-    kind = "inception80" if (args.label == "O-FID" and args.num_classes == 80) else "inception"
+    kind = tweights.inception_kind(args.network, args.label == "O-FID" and args.num_classes == 80)
     wpath, tag = tweights.resolve(args.weights, args.synthetic_weights, kind)
     if args.path1 is None:                                             # statistics-only
         if tdist.is_main():
             print([args.path2])
         mu, sigma = run_with_exact_fallback(lambda: save_statistics_of_path(
             args.path2, args.save_stats, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.num_workers,
-            args.u8_cache), "the statistics pass")
+            args.u8_cache, args.network), "the statistics pass")
         if tdist.is_main():
             print(f"statistics of {args.path2} -> {args.save_stats}{tag}")
         return None
@@ -731,7 +756,8 @@ def main(argv=None):
         print(paths)                                                   # :247
     if args.per_class:
         per, skipped = run_with_exact_fallback(lambda: calculate_per_class_fid(
-            paths, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.num_workers), "the per-class FID")
+            paths, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.num_workers,
+            network=args.network), "the per-class FID")
         mean = float(np.mean(list(per.values()))) if per else float("nan")
         if tdist.is_main():
             lines = [f"{args.label}[{c}]: {v}{tag}" for c, v in per.items()]
@@ -745,7 +771,7 @@ def main(argv=None):
         return per
     fid_value = run_with_exact_fallback(lambda: calculate_fid_given_paths(
         paths, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.save_stats, args.num_workers,
-        args.u8_cache), "the FID").item()
+        args.u8_cache, args.network), "the FID").item()
     if tdist.is_main():
         if args.saved_file:
             with open(args.saved_file, "w") as f:

@@ -19,6 +19,45 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+# ---- networks -------------------------------------------------------------------------------------------------------
+# "torchvision": torchvision's Inception3 (inception_v3_google-1a9a5a14.pth), the network of the reference's FID wrapper.
+# "inception-2015": the TensorFlow Inception-2015 graph (classify_image_graph_def.pb) that the reference's IS* for COCO runs
+# (image_realism/IS/coco/inception_score_star_coco.py:64-108) and pytorch-fid / TTUR take FID on; its weights are
+# pytorch-fid's conversion pt_inception-2015-12-05-6726825d.pth (torchvision key names, no AuxLogits, fc 1008 x 2048).
+# Same module tree; it differs in its pool branches (``POOL_BRANCHES``), its 1008-class head and its input table.
+NETWORKS = ("torchvision", "inception-2015")
+NETWORK_CLASSES = {"torchvision": 1000, "inception-2015": 1008}
+# Input of the Inception-2015 graph: the uint8 image v (299 x 299 from the PIL-exact resize; the graph's own
+# ResizeBilinear 299 -> 299 is the identity) becomes (v - SUB) / DIV on every channel.  These are the graph's Sub / Mul
+# nodes AS COMMONLY DOCUMENTED (pytorch-fid's FIDInceptionV3 uses the same map); nobody has checked them against a copy
+# of the .pb file.  Every user of the constants reads them here (device.make_lut, InceptionV3.preprocess).
+INCEPTION_2015_INPUT_SUB = 128.0
+INCEPTION_2015_INPUT_DIV = 128.0
+# branch_pool of each mixed block: "avg" = avg_pool2d(3, 1, 1) with count_include_pad (torchvision), "avg_excl" = the same
+# with count_include_pad=False (TensorFlow's SAME average: divisor 4 at corners, 6 on edges, 9 inside), "max" =
+# max_pool2d(3, 1, 1), padding acting as -inf (the 2015 graph's Mixed_7c).  The 1x1 conv of the branch follows the pool.
+_MIXED_POOLED = ("Mixed_5b", "Mixed_5c", "Mixed_5d", "Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e", "Mixed_7b", "Mixed_7c")
+POOL_BRANCHES = {
+    "torchvision": {name: "avg" for name in _MIXED_POOLED},
+    "inception-2015": dict({name: "avg_excl" for name in _MIXED_POOLED}, Mixed_7c="max"),
+}
+
+
+def check_network(network):
+    if network not in NETWORKS:
+        raise ValueError(f"network must be one of {NETWORKS}, not {network!r}")
+    return network
+
+
+def _pool_branch(x, pool):
+    if pool == "avg":
+        return F.avg_pool2d(x, kernel_size=3, stride=1, padding=1)
+    if pool == "avg_excl":
+        return F.avg_pool2d(x, kernel_size=3, stride=1, padding=1, count_include_pad=False)
+    if pool == "max":
+        return F.max_pool2d(x, kernel_size=3, stride=1, padding=1)
+    raise ValueError(pool)
+
 
 class BasicConv2d(nn.Module):
     """conv(bias=False) -> BatchNorm(eps=1e-3) -> ReLU; torchvision key names ``conv``/``bn``."""
@@ -58,12 +97,13 @@ class InceptionA(nn.Module):
         self.branch3x3dbl_2 = BasicConv2d(64, 96, kernel_size=3, padding=1)
         self.branch3x3dbl_3 = BasicConv2d(96, 96, kernel_size=3, padding=1)
         self.branch_pool = BasicConv2d(cin, pool_features, kernel_size=1)
+        self.pool = "avg"
 
     def forward(self, x):
         b1 = self.branch1x1(x)
         b5 = self.branch5x5_2(self.branch5x5_1(x))
         b3 = self.branch3x3dbl_3(self.branch3x3dbl_2(self.branch3x3dbl_1(x)))
-        bp = self.branch_pool(F.avg_pool2d(x, kernel_size=3, stride=1, padding=1))
+        bp = self.branch_pool(_pool_branch(x, self.pool))
         return torch.cat([b1, b5, b3, bp], 1)
 
 
@@ -95,13 +135,14 @@ class InceptionC(nn.Module):
         self.branch7x7dbl_4 = BasicConv2d(c7, c7, kernel_size=(7, 1), padding=(3, 0))
         self.branch7x7dbl_5 = BasicConv2d(c7, 192, kernel_size=(1, 7), padding=(0, 3))
         self.branch_pool = BasicConv2d(cin, 192, kernel_size=1)
+        self.pool = "avg"
 
     def forward(self, x):
         b1 = self.branch1x1(x)
         b7 = self.branch7x7_3(self.branch7x7_2(self.branch7x7_1(x)))
         bd = self.branch7x7dbl_1(x)
         bd = self.branch7x7dbl_5(self.branch7x7dbl_4(self.branch7x7dbl_3(self.branch7x7dbl_2(bd))))
-        bp = self.branch_pool(F.avg_pool2d(x, kernel_size=3, stride=1, padding=1))
+        bp = self.branch_pool(_pool_branch(x, self.pool))
         return torch.cat([b1, b7, bd, bp], 1)
 
 
@@ -134,6 +175,7 @@ class InceptionE(nn.Module):
         self.branch3x3dbl_3a = BasicConv2d(384, 384, kernel_size=(1, 3), padding=(0, 1))
         self.branch3x3dbl_3b = BasicConv2d(384, 384, kernel_size=(3, 1), padding=(1, 0))
         self.branch_pool = BasicConv2d(cin, 192, kernel_size=1)
+        self.pool = "avg"
 
     def forward(self, x):
         b1 = self.branch1x1(x)
@@ -141,7 +183,7 @@ class InceptionE(nn.Module):
         b3 = torch.cat([self.branch3x3_2a(b3), self.branch3x3_2b(b3)], 1)
         bd = self.branch3x3dbl_2(self.branch3x3dbl_1(x))
         bd = torch.cat([self.branch3x3dbl_3a(bd), self.branch3x3dbl_3b(bd)], 1)
-        bp = self.branch_pool(F.avg_pool2d(x, kernel_size=3, stride=1, padding=1))
+        bp = self.branch_pool(_pool_branch(x, self.pool))
         return torch.cat([b1, b3, bd, bp], 1)
 
 
@@ -156,10 +198,12 @@ class InceptionAux(nn.Module):
 
 
 class Inception3(nn.Module):
-    """The torchvision ``Inception3`` module tree (names, shapes) without its forward."""
+    """The torchvision ``Inception3`` module tree (names, shapes) without its forward.  ``network="inception-2015"``: the
+    same tree with the 2015 graph's pool branches (``POOL_BRANCHES``); pass ``aux_logits=False`` for its weight files."""
 
-    def __init__(self, num_classes=1000, aux_logits=True):
+    def __init__(self, num_classes=1000, aux_logits=True, network="torchvision"):
         super().__init__()
+        self.network = check_network(network)
         self.Conv2d_1a_3x3 = BasicConv2d(3, 32, kernel_size=3, stride=2)
         self.Conv2d_2a_3x3 = BasicConv2d(32, 32, kernel_size=3)
         self.Conv2d_2b_3x3 = BasicConv2d(32, 64, kernel_size=3, padding=1)
@@ -179,10 +223,13 @@ class Inception3(nn.Module):
         self.Mixed_7b = InceptionE(1280)
         self.Mixed_7c = InceptionE(2048)
         self.fc = nn.Linear(2048, num_classes)
+        for name, pool in POOL_BRANCHES[network].items():
+            getattr(self, name).pool = pool
 
 
 def _trunk_forward(net, x):
-    """pool3 features of an ``Inception3`` module tree (used only to calibrate stand-in weights)."""
+    """pool3 features of an ``Inception3`` module tree (used only to calibrate stand-in weights).  The mixed blocks run
+    the pool branches of ``net.network`` (their ``pool`` attribute)."""
     x = net.Conv2d_2b_3x3(net.Conv2d_2a_3x3(net.Conv2d_1a_3x3(x)))
     x = F.max_pool2d(x, kernel_size=3, stride=2)
     x = net.Conv2d_4a_3x3(net.Conv2d_3b_1x1(x))
@@ -216,7 +263,9 @@ def seeded_init_(net, seed=0, calibration="fid"):
         # data-parallel run: rank 0 calibrates and the engine broadcasts its parameters to every rank
         # (engine.RealismEngine -> dist.broadcast_module_), so the other ranks skip the CPU convolutions
         return net
-    key = (seed, net.fc.out_features, calibration)
+    network = getattr(net, "network", "torchvision")
+    # the key of the default network is what it was before there were two networks (its cache files stay valid)
+    key = (seed, net.fc.out_features, calibration) + (() if network == "torchvision" else (network,))
     if key in _SEEDED_CACHE:
         # (the module tree may be a skeleton without storage -- build_inception3 -- so the tensors are ASSIGNED; clones, because
         # the in-memory copy serves every later model of the process)
@@ -252,6 +301,8 @@ def seeded_init_(net, seed=0, calibration="fid"):
     x = (1.0 - alpha) * x + alpha * torch.rand((n_cal, 3, 299, 299), generator=g)
     if calibration == "pm1":             # O-IS convention: Normalize((.5,.5,.5),(.5,.5,.5)) -> [-1, 1]
         x = (x - 0.5) / 0.5
+    elif network == "inception-2015":    # the 2015 graph's input map on 0..255 pixel values
+        x = (x * 255.0 - INCEPTION_2015_INPUT_SUB) / INCEPTION_2015_INPUT_DIV
     else:                                # FID wrapper convention: inception.py:120-124 on [0, 1] pixels
         x[:, 0] = x[:, 0] * (0.229 / 0.5) + (0.485 - 0.5) / 0.5
         x[:, 1] = x[:, 1] * (0.224 / 0.5) + (0.456 - 0.5) / 0.5
@@ -307,7 +358,8 @@ def _standin_cache_path(key):
         uid = os.getuid() if hasattr(os, "getuid") else 0
         root = os.path.join(tempfile.gettempdir(), f"tise_toolbox_amd_standin_{uid}")
     tag = hashlib.sha256(repr((_STANDIN_VERSION, key, CALIBRATION_NOISE_FRACTIONS, torch.__version__)).encode()).hexdigest()[:20]
-    return os.path.join(root, f"inception3_standin_{key[0]}_{key[1]}_{key[2]}_{tag}.pt")
+    net = "" if len(key) == 3 else f"{key[3]}_"
+    return os.path.join(root, f"inception3_standin_{net}{key[0]}_{key[1]}_{key[2]}_{tag}.pt")
 
 
 def _standin_cache_load(key):
@@ -366,17 +418,24 @@ def _materialize_(net):
     return net
 
 
-def build_inception3(weights=None, num_classes=1000, seed=0, calibration="fid"):
+def build_inception3(weights=None, num_classes=None, seed=0, calibration="fid", network="torchvision"):
     """Construct ``Inception3`` and load ``weights`` (a torchvision-format state_dict
     path) or, when ``weights`` is None, the seeded stand-in parameters.
+
+    ``network="inception-2015"``: the 2015 graph's tree without ``AuxLogits`` (pytorch-fid's weight file has none); the
+    file is loaded strictly, so a torchvision file fails here and a pytorch-fid file fails for the default network.
+    ``num_classes`` None: the network's own head (1000 / 1008).
 
     The module tree is built WITHOUT storage (``meta`` device) and the loaded tensors are assigned to it
     (``load_state_dict(assign=True)``): torch's default initialisation of 96 convolutions (kaiming_uniform_ over 24 M
     values) and the copy of every tensor into it were 0.11 s of a CLI process's start-up for values that are overwritten
     at once (tools/startup_probe.py, profiles/r06d_startup.txt).  Only when stand-in weights have to be computed from
     scratch (no cache file yet) does the skeleton get real storage first."""
+    check_network(network)
+    if num_classes is None:
+        num_classes = NETWORK_CLASSES[network]
     with torch.device("meta"), _no_default_init():
-        net = Inception3(num_classes=num_classes, aux_logits=True)
+        net = Inception3(num_classes=num_classes, aux_logits=network == "torchvision", network=network)
     if weights is not None:
         sd = torch.load(weights, map_location="cpu")
         if isinstance(sd, dict) and "state_dict" in sd:
@@ -397,22 +456,24 @@ class InceptionV3(nn.Module):
     Extra keyword arguments (all optional, defaults reproduce the reference call
     ``InceptionV3([block_idx])``): ``weights`` (state_dict path; the reference
     downloads the torchvision file, there is no network here), ``num_classes``
-    (80 for the O-FID/O-IS fine-tune, ``O-FID/inception.py:58-64``), ``seed``.
+    (80 for the O-FID/O-IS fine-tune, ``O-FID/inception.py:58-64``; None: the network's own head), ``seed``,
+    ``network`` (``NETWORKS``: "inception-2015" is the TensorFlow graph of the reference's IS* for COCO).
     """
 
     DEFAULT_BLOCK_INDEX = 3
     BLOCK_INDEX_BY_DIM = {64: 0, 192: 1, 768: 2, 2048: 3}   # inception.py:14-19
 
     def __init__(self, output_blocks=[DEFAULT_BLOCK_INDEX], resize_input=True, normalize_input=True,
-                 requires_grad=False, weights=None, num_classes=1000, seed=0, calibration="fid"):
+                 requires_grad=False, weights=None, num_classes=None, seed=0, calibration="fid", network="torchvision"):
         super().__init__()
+        self.network = check_network(network)
         self.resize_input = resize_input
         self.normalize_input = normalize_input
         self.output_blocks = sorted(output_blocks)
         self.last_needed_block = max(output_blocks)
         assert self.last_needed_block <= 3, "Last possible output block index is 3"   # inception.py:53
 
-        inception = build_inception3(weights, num_classes, seed, calibration)
+        inception = build_inception3(weights, num_classes, seed, calibration, network)
         self.blocks = nn.ModuleList()
         self.blocks.append(nn.Sequential(                                   # inception.py:59-66
             inception.Conv2d_1a_3x3, inception.Conv2d_2a_3x3, inception.Conv2d_2b_3x3,
@@ -465,6 +526,8 @@ class InceptionV3(nn.Module):
         if self.resize_input and tuple(x.shape[-2:]) != (299, 299):
             # :117-118; for 299x299 input align_corners bilinear is the identity map
             x = F.interpolate(x, size=(299, 299), mode="bilinear", align_corners=True)
+        if self.normalize_input and self.network == "inception-2015":     # the 2015 graph's Sub / Mul on 0..255 values
+            return (x * 255.0 - INCEPTION_2015_INPUT_SUB) / INCEPTION_2015_INPUT_DIV
         if self.normalize_input:                                            # :120-124
             x = x.clone()
             x[:, 0] = x[:, 0] * (0.229 / 0.5) + (0.485 - 0.5) / 0.5

@@ -9,7 +9,8 @@ Drop-in for the reference ``image_realism/IS/coco/inception_score_star_coco.py``
 
 Model note: the reference IS* runs the 2015 TensorFlow Inception graph (1008
 classes, T calibrated for it); north_star prescribes the PyTorch InceptionV3 instead, so scores are
-comparable between paths run with the SAME weights only.  What IS kept of the reference head: for
+comparable between paths run with the SAME weights only.  ``--network inception-2015`` runs that graph itself
+(pytorch-fid's weight file, 1008 classes) so the reference's T applies.  What IS kept of the reference head: for
 ``--rule coco`` the logits are ``pool3 @ W.T`` WITHOUT the classifier bias, as
 inception_score_star_coco.py:104-105 multiplies pool3 by the last layer's weight matrix only
 (``--fc-bias on`` adds it; the bird and ois rules use the model's biased logits like their scripts).  The reduction itself -- temperature,
@@ -27,12 +28,14 @@ import torch.utils.data
 
 from . import _lib, device, dist as tdist, img_data, weights as tweights
 from .engine import RealismEngine, T_BIRD, T_COCO, T_OIS, require_gpu
+from .inception import NETWORK_CLASSES, NETWORKS
 
 warnings.filterwarnings("ignore")
 
 _ENGINE = None
-_CONFIG = {"weights": None, "num_classes": 1000, "seed": 0, "temperature": T_COCO, "batch_size": 50,
-           "rule": "coco", "drop_first_class": False, "num_workers": 0, "fc_bias": "auto", "png_feed": "ring"}
+_CONFIG = {"weights": None, "num_classes": None, "seed": 0, "temperature": T_COCO, "batch_size": 50,
+           "rule": "coco", "drop_first_class": False, "num_workers": 0, "fc_bias": "auto", "png_feed": "ring",
+           "network": "torchvision"}
 
 
 def configure(**kw):
@@ -48,7 +51,7 @@ def _engine():
         _ENGINE = None                                   # the convolution path changed (engine.run_with_exact_fallback): build anew
     if _ENGINE is None:
         _ENGINE = RealismEngine(dims=2048, weights=_CONFIG["weights"], num_classes=_CONFIG["num_classes"],
-                                seed=_CONFIG["seed"], with_logits=True, fc_bias=_CONFIG["fc_bias"])
+                                seed=_CONFIG["seed"], with_logits=True, fc_bias=_CONFIG["fc_bias"], network=_CONFIG["network"])
     _ENGINE._conv_mode = os.environ.get("TISE_CONV", "split")
     return _ENGINE
 
@@ -178,7 +181,11 @@ def _build_parser():
     parser.add_argument("--weights", type=str, default=None, help="torchvision-format InceptionV3 state_dict (.pth)")
     parser.add_argument("--synthetic-weights", action="store_true",
                         help="seeded stand-in parameters (plumbing / throughput only; results are tagged)")
-    parser.add_argument("--num-classes", type=int, default=1000)
+    parser.add_argument("--num-classes", type=int, default=None, help="classifier width (default: 1000, 1008 for --network inception-2015)")
+    parser.add_argument("--network", type=str, default="torchvision", choices=list(NETWORKS),
+                        help="torchvision: torchvision's InceptionV3; inception-2015: the TensorFlow Inception-2015 graph of the "
+                             "reference's IS* for COCO (pytorch-fid's pt_inception-2015-12-05-6726825d.pth: 1008 classes, "
+                             "exclude-padding average pools, max-pool branch in Mixed_7c, input (v - 128) / 128)")
     parser.add_argument("--seed", type=int, default=0, help="seed of the --synthetic-weights parameters")
     parser.add_argument("--label", type=str, default="IS", choices=["IS", "O-IS", "bird"])
     parser.add_argument("--fc-bias", type=str, default="auto", choices=["auto", "on", "off"],
@@ -190,13 +197,16 @@ def _build_parser():
 
 def main(argv=None):
     args = _build_parser().parse_args(argv)
+    if args.num_classes is None:
+        args.num_classes = NETWORK_CLASSES[args.network]
     rank, world, _ = tdist.init_from_env()
     if world == 1:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", str(args.gpu))   # :146
     wpath, tag = tweights.resolve(args.weights, args.synthetic_weights,
-                                  "inception80" if args.label == "O-IS" and args.num_classes == 80 else "inception")
+                                  tweights.inception_kind(args.network, args.label == "O-IS" and args.num_classes == 80))
     configure(weights=wpath, num_classes=args.num_classes, seed=args.seed, temperature=args.temperature,
-              batch_size=args.batch_size, rule=args.rule, drop_first_class=args.drop_first_class, fc_bias=args.fc_bias)
+              batch_size=args.batch_size, rule=args.rule, drop_first_class=args.drop_first_class, fc_bias=args.fc_bias,
+              network=args.network)
     images = load_data(args.image_folder)
     print(".......")
     from .engine import run_with_exact_fallback

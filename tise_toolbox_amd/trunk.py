@@ -16,6 +16,11 @@ after the first rocprof pass (``profiles/r01a_*``: 35 % of a step was not convol
   ``torch.cat``;
 * the two stem max-pools absorb the preceding conv's bias + ReLU (``tise_maxpool3s2_nhwc``).
 
+``network="inception-2015"`` (the model's ``network``): the average pools exclude the padding
+(``tise_avgpool3_excl_bias_relu_*``; the raw-conv-then-pool order stays valid, see csrc/trunk_ops.hip) and Mixed_7c's
+pool branch is a 3x3 / stride 1 max pool, which does not commute with the conv: it runs first, on the block input
+(``tise_maxpool3s1p1_*``), and the branch's 1x1 conv follows; the fused 1x1 of Mixed_7c keeps its other 1152 channels.
+
 Numerics: fp32 throughout; relative to the reference graph order only fp32 summation order changes
 (pool/conv commutation, fused-1x1 kernel choice).  ``tests/test_gpu_pipeline.py`` checks it against the
 unfused module and against the CPU oracle.
@@ -73,6 +78,9 @@ class FusedTrunk:
                 return _Conv(ms, self.device)
 
             b0, b1, b2, b3 = "blocks.0.", "blocks.1.", "blocks.2.", "blocks.3."
+            self.network = getattr(model, "network", "torchvision")
+            # every average pool of a network has the same rule: count_include_pad (torchvision) or not (inception-2015)
+            self.avg_excl = self.network == "inception-2015"
             self.last_block = model.last_needed_block
             self.c1a, self.c2a, self.c2b = conv(b0 + "0"), conv(b0 + "1"), conv(b0 + "2")
             if self.last_block >= 1:
@@ -80,13 +88,20 @@ class FusedTrunk:
             self.blocks = []
             if self.last_block >= 2:
                 for i, kind in enumerate("AAABCCCC"):
-                    self.blocks.append((kind, self._block_params(kind, b2 + str(i) + ".", conv)))
+                    self.blocks.append((kind, self._block_params(kind, b2 + str(i) + ".", conv, mods)))
             if self.last_block >= 3:
                 for i, kind in enumerate("DEE"):
-                    self.blocks.append((kind, self._block_params(kind, b3 + str(i) + ".", conv)))
+                    self.blocks.append((kind, self._block_params(kind, b3 + str(i) + ".", conv, mods)))
 
-    @staticmethod
-    def _block_params(kind, p, conv):
+    def _block_params(self, kind, p, conv, mods):
+        pool = getattr(mods[p[:-1]], "pool", None)
+        if kind in "ACE":
+            assert pool in ("max", "avg_excl" if self.avg_excl else "avg"), (p, pool)
+        if kind == "E" and pool == "max":
+            # max-pool branch (inception-2015 Mixed_7c): the fused 1x1 without the pool branch, whose conv ("p") reads the pooled input
+            return dict(f=conv(p + "branch1x1", p + "branch3x3_1", p + "branch3x3dbl_1"), p=conv(p + "branch_pool"),
+                        a2=conv(p + "branch3x3_2a"), b2=conv(p + "branch3x3_2b"), d2=conv(p + "branch3x3dbl_2"),
+                        a3=conv(p + "branch3x3dbl_3a"), b3=conv(p + "branch3x3dbl_3b"))
         if kind == "A":
             return dict(f=conv(p + "branch1x1", p + "branch5x5_1", p + "branch3x3dbl_1", p + "branch_pool"),
                         c5=conv(p + "branch5x5_2"), d2=conv(p + "branch3x3dbl_2"), d3=conv(p + "branch3x3dbl_3"))
@@ -126,10 +141,18 @@ class FusedTrunk:
         return out
 
     @staticmethod
-    def _avgpool_bias_relu(raw, bias, x_off, C, out, out_off):
+    def _avgpool_bias_relu(raw, bias, x_off, C, out, out_off, excl=False):
         n, h, w, ld = raw.shape
-        _lib.call("tise_avgpool3_bias_relu_nhwc", _p(raw), ld, x_off, n, h, w, C, _p(bias), _p(out), out.shape[3],
-                  out_off, _stream())
+        fn = "tise_avgpool3_excl_bias_relu_nhwc" if excl else "tise_avgpool3_bias_relu_nhwc"
+        _lib.call(fn, _p(raw), ld, x_off, n, h, w, C, _p(bias), _p(out), out.shape[3], out_off, _stream())
+
+    @staticmethod
+    def _maxpool_s1(x):
+        """max_pool2d(x, 3, stride 1, padding 1) of an fp32 NHWC tensor (padding = -inf)."""
+        n, h, w, C = x.shape
+        out = torch.empty_like(x)
+        _lib.call("tise_maxpool3s1p1_nhwc", _p(x), C, 0, n, h, w, C, _p(out), C, 0, _stream())
+        return out
 
     @staticmethod
     def _maxpool(x, bias=None, out=None, out_off=0):
@@ -151,7 +174,7 @@ class FusedTrunk:
         self._bias_relu(raw, f.b[0:64], 0, 64, out, 0)
         t5 = self._bias_relu(raw, f.b[64:112], 64, 48)
         t3 = self._bias_relu(raw, f.b[112:176], 112, 64)
-        self._avgpool_bias_relu(raw, f.b[176:], 176, pf, out, 224)
+        self._avgpool_bias_relu(raw, f.b[176:], 176, pf, out, 224, self.avg_excl)
         self._bias_relu(self._conv(t5, c5), c5.b, 0, 64, out, 64)
         t3 = self._bias_relu(self._conv(t3, d2), d2.b)
         self._bias_relu(self._conv(t3, d3), d3.b, 0, 96, out, 128)
@@ -177,7 +200,7 @@ class FusedTrunk:
         self._bias_relu(raw, f.b[0:192], 0, 192, out, 0)
         t7 = self._bias_relu(raw, f.b[192:192 + c7], 192, c7)
         td = self._bias_relu(raw, f.b[192 + c7:192 + 2 * c7], 192 + c7, c7)
-        self._avgpool_bias_relu(raw, f.b[192 + 2 * c7:], 192 + 2 * c7, 192, out, 576)
+        self._avgpool_bias_relu(raw, f.b[192 + 2 * c7:], 192 + 2 * c7, 192, out, 576, self.avg_excl)
         t7 = self._bias_relu(self._conv(t7, P["s2"]), P["s2"].b)
         self._bias_relu(self._conv(t7, P["s3"]), P["s3"].b, 0, 192, out, 192)
         for k in ("d2", "d3", "d4"):
@@ -208,7 +231,10 @@ class FusedTrunk:
         self._bias_relu(raw, f.b[0:320], 0, 320, out, 0)
         t3 = self._bias_relu(raw, f.b[320:704], 320, 384)
         td = self._bias_relu(raw, f.b[704:1152], 704, 448)
-        self._avgpool_bias_relu(raw, f.b[1152:1344], 1152, 192, out, 1856)
+        if "p" in P:                                                 # max-pool branch: pool the block input, then its 1x1
+            self._bias_relu(self._conv(self._maxpool_s1(x), P["p"]), P["p"].b, 0, 192, out, 1856)
+        else:
+            self._avgpool_bias_relu(raw, f.b[1152:1344], 1152, 192, out, 1856, self.avg_excl)
         self._bias_relu(self._conv(t3, P["a2"]), P["a2"].b, 0, 384, out, 320)
         self._bias_relu(self._conv(t3, P["b2"]), P["b2"].b, 0, 384, out, 704)
         td = self._bias_relu(self._conv(td, P["d2"]), P["d2"].b)
@@ -370,10 +396,18 @@ class SplitTrunk(FusedTrunk):
         return out
 
     @staticmethod
-    def _avgpool_split(raw, bias, out, out_off):
+    def _avgpool_split(raw, bias, out, out_off, excl=False):
         n, h, w, c = raw.shape
-        _lib.call("tise_avgpool3_bias_relu_split_nhwc", _p(raw), c, 0, n, h, w, c, _p(bias), _p(out), out.shape[3] // 2,
-                  out_off, _stream())
+        fn = "tise_avgpool3_excl_bias_relu_split_nhwc" if excl else "tise_avgpool3_bias_relu_split_nhwc"
+        _lib.call(fn, _p(raw), c, 0, n, h, w, c, _p(bias), _p(out), out.shape[3] // 2, out_off, _stream())
+
+    @staticmethod
+    def _maxpool_s1_split(x):
+        """max_pool2d(x, 3, stride 1, padding 1) of a split tensor (padding = -inf) -> packed split tensor."""
+        n, h, w, c2 = x.shape
+        out = torch.empty_like(x)
+        _lib.call("tise_maxpool3s1p1_split_nhwc", _p(x), c2 // 2, 0, n, h, w, c2 // 2, _p(out), c2 // 2, 0, _stream())
+        return out
 
     def _sblock_a(self, x, P, pooled_input=False):
         n, h, w, _ = x.shape
@@ -386,7 +420,7 @@ class SplitTrunk(FusedTrunk):
         t5, t3 = self._new(n, h, w, 48, dev), self._new(n, h, w, 64, dev)
         raw = torch.empty((n, h, w, pf), dtype=torch.float32, device=dev)
         f(x, [(0, 64, out, 0, 0), (64, 112, t5, 0, 0), (112, 176, t3, 0, 0), (176, 176 + pf, raw, 0, 1)], pooled_input=pooled_input)
-        self._avgpool_split(raw, f.bias[176:176 + pf], out, 224)
+        self._avgpool_split(raw, f.bias[176:176 + pf], out, 224, self.avg_excl)
         P["c5"](t5, [(0, 64, out, 64, 0)])
         t3 = self._sconv(P["d2"], t3)
         P["d3"](t3, [(0, 96, out, 128, 0)])
@@ -413,7 +447,7 @@ class SplitTrunk(FusedTrunk):
         raw = torch.empty((n, h, w, 192), dtype=torch.float32, device=dev)
         f(x, [(0, 192, out, 0, 0), (192, 192 + c7, t7, 0, 0), (192 + c7, 192 + 2 * c7, td, 0, 0),
               (192 + 2 * c7, 384 + 2 * c7, raw, 0, 1)])
-        self._avgpool_split(raw, f.bias[192 + 2 * c7:384 + 2 * c7], out, 576)
+        self._avgpool_split(raw, f.bias[192 + 2 * c7:384 + 2 * c7], out, 576, self.avg_excl)
         t7 = self._sconv(P["s2"], t7)
         P["s3"](t7, [(0, 192, out, 192, 0)])
         for k in ("d2", "d3", "d4"):
@@ -442,9 +476,13 @@ class SplitTrunk(FusedTrunk):
         dev = x.device
         out = self._new(n, h, w, 2048, dev)
         t3, td = self._new(n, h, w, 384, dev), self._new(n, h, w, 448, dev)
-        raw = torch.empty((n, h, w, 192), dtype=torch.float32, device=dev)
-        f(x, [(0, 320, out, 0, 0), (320, 704, t3, 0, 0), (704, 1152, td, 0, 0), (1152, 1344, raw, 0, 1)])
-        self._avgpool_split(raw, f.bias[1152:1344], out, 1856)
+        if "p" in P:                                                    # max-pool branch: pool the block input, then its 1x1
+            f(x, [(0, 320, out, 0, 0), (320, 704, t3, 0, 0), (704, 1152, td, 0, 0)])
+            P["p"](self._maxpool_s1_split(x), [(0, 192, out, 1856, 0)])
+        else:
+            raw = torch.empty((n, h, w, 192), dtype=torch.float32, device=dev)
+            f(x, [(0, 320, out, 0, 0), (320, 704, t3, 0, 0), (704, 1152, td, 0, 0), (1152, 1344, raw, 0, 1)])
+            self._avgpool_split(raw, f.bias[1152:1344], out, 1856, self.avg_excl)
         P["a2"](t3, [(0, 384, out, 320, 0)])
         P["b2"](t3, [(0, 384, out, 704, 0)])
         td = self._sconv(P["d2"], td)

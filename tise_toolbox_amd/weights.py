@@ -24,6 +24,10 @@ _KINDS = {
                            os.path.join(_torch_home(), "checkpoints", "inception_v3_google-1a9a5a14.pth")]),
     "inception80": ("80-class fine-tuned InceptionV3",
                     lambda: [os.path.join("weights", "inceptionv3_fine_to_with_80_coco_classes.pth")]),
+    # the Inception-2015 graph (--network inception-2015): pytorch-fid's conversion of classify_image_graph_def.pb, at the
+    # path pytorch-fid caches it under
+    "inception2015": ("Inception-2015 graph (pytorch-fid pt_inception-2015-12-05-6726825d.pth)",
+                      lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "pt_inception-2015-12-05-6726825d.pth")]),
     "clip": ("CLIP ViT-B/32", lambda: [os.path.expanduser(os.path.join("~", ".cache", "clip", "ViT-B-32.pt"))]),
 }
 
@@ -35,6 +39,13 @@ def _torch_home():
 def warn_synthetic(what):
     print(f"[tise] WARNING: {what} runs with SEEDED STAND-IN parameters (no pretrained file given): scores are "
           f"meaningless except for comparing code paths on identical inputs", file=sys.stderr, flush=True)
+
+
+def inception_kind(network, label_80=False):
+    """The ``_KINDS`` entry of an InceptionV3 run: ``label_80`` = the 80-class fine-tune (O-IS / O-FID with 80 classes)."""
+    if network == "inception-2015":
+        return "inception2015"
+    return "inception80" if label_80 else "inception"
 
 
 def resolve(weights, synthetic, kind):
