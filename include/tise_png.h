@@ -46,6 +46,11 @@ size_t tise_png_slot_bytes(int h, int w, int bpp);
 int tise_png_inflate_slot(const uint8_t* file, size_t len, uint8_t* slot, size_t slot_bytes, int h, int w,
                           uint8_t* scratch, size_t scratch_bytes, int* got_w, int* got_h, int* mode_out);
 
+/* ---- CRC-32C (Castagnoli, reflected polynomial 0x82F63B78; RFC 3720 B.4) --------------------------------------------------
+ * The checksum of TensorFlow's checkpoint files (tise_toolbox_amd/tf_checkpoint.py): table block trailers store it masked,
+ * V2 tensor entries plain.  tise_crc32c continues a running value: crc = tise_crc32c(0, p, n) for a whole buffer. */
+uint32_t tise_crc32c(uint32_t crc, const uint8_t* data, size_t len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1045,6 +1045,12 @@ extern "C" int tise_conv_split_f16(const ConvArgs* args, int tn, void* stream) {
             (g.mode == 0 && g.off + (g.c1 - g.c0) > g.ld) ||
             (reinterpret_cast<uintptr_t>(g.dst) & 15) != 0 || (i > 0 && g.c0 != args->seg[i - 1].c1) || (g.mode != 0 && g.mode != 1))
             return TISE_ERR_INVALID_ARG;
+        // an fp32 segment receives whole 8-cout chunks up to the chunk that holds its last cout (the last segment: up to the
+        // chunk of Cout - 1): with a Cout that is not a multiple of 8 (51 bird logits) that chunk must still lie inside the
+        // row, or its tail would land in the next pixel's row -- or past the end of the tensor for the last pixel
+        const bool last = i == (args->nseg & 0xff) - 1;
+        const int c_end = ((last ? args->Cout : g.c1) + 7) / 8 * 8;
+        if (g.mode == 1 && g.off + (c_end - g.c0) > g.ld) return TISE_ERR_INVALID_ARG;
     }
     if (args->seg[0].c0 != 0) return TISE_ERR_INVALID_ARG;
     if (tn & 512) return tise_conv_pipe_launch(args, (tn & 255) | (tn & 1024), stream);   // resident-weights sliding-window kernel (| 1024: pooled output)

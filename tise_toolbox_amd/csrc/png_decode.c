@@ -66,6 +66,38 @@ static int chunk_crc_ok(const uint8_t* type_and_body, size_t n, const uint8_t* s
     return got == be32(stored);
 }
 
+/* ---- CRC-32C (include/tise_png.h): slicing by 8 over tables built once ---------------------------------------------- */
+static uint32_t g_crc32c[8][256];
+static int g_crc32c_ready = 0;
+
+static void crc32c_init(void) {
+    for (uint32_t i = 0; i < 256; ++i) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
+        g_crc32c[0][i] = c;
+    }
+    for (uint32_t i = 0; i < 256; ++i)
+        for (int t = 1; t < 8; ++t) g_crc32c[t][i] = (g_crc32c[t - 1][i] >> 8) ^ g_crc32c[0][g_crc32c[t - 1][i] & 0xff];
+    g_crc32c_ready = 1;     /* idempotent: two threads that race here write the same values */
+}
+
+uint32_t tise_crc32c(uint32_t crc, const uint8_t* p, size_t n) {
+    if (!g_crc32c_ready) crc32c_init();
+    crc = ~crc;
+    while (n && ((uintptr_t)p & 7)) { crc = (crc >> 8) ^ g_crc32c[0][(crc ^ *p++) & 0xff]; --n; }
+    while (n >= 8) {
+        uint64_t v;
+        memcpy(&v, p, 8);                                      /* little-endian host (x86-64) */
+        v ^= crc;
+        crc = g_crc32c[7][v & 0xff] ^ g_crc32c[6][(v >> 8) & 0xff] ^ g_crc32c[5][(v >> 16) & 0xff] ^ g_crc32c[4][(v >> 24) & 0xff] ^
+              g_crc32c[3][(v >> 32) & 0xff] ^ g_crc32c[2][(v >> 40) & 0xff] ^ g_crc32c[1][(v >> 48) & 0xff] ^ g_crc32c[0][v >> 56];
+        p += 8;
+        n -= 8;
+    }
+    while (n--) crc = (crc >> 8) ^ g_crc32c[0][(crc ^ *p++) & 0xff];
+    return ~crc;
+}
+
 /* ---- unfilter: one row, BPP bytes per pixel, in place; `up` = the previous unfiltered row (NULL for the first) --------- */
 static inline int paeth(int a, int b, int c) {
     const int p = a + b - c;

@@ -112,13 +112,20 @@ def make_lut(normalize_input=True, scale_pm1=False, network="torchvision"):
     Normalize((.5,.5,.5),(.5,.5,.5)) = (x - 0.5) / 0.5 (object_centric_inception_score.py:91).
     ``network="inception-2015"`` (with ``normalize_input``): the 2015 graph's input map (v - 128) / 128 on the byte value v,
     every channel (fp32; constants in inception.INCEPTION_2015_INPUT_SUB / _DIV).
+    ``network="slim"`` (with ``normalize_input``): the bird script's ``img.astype(np.float32) / 127.5 - 1.0``
+    (inception_score_star_bird.py:69-70) on the byte value, every channel, fp32 in that order.
     """
+    if network == "slim" and normalize_input and not scale_pm1:
+        from .inception import SLIM_INPUT_DIV, SLIM_INPUT_SUB
+        b = np.arange(256, dtype=np.uint8).astype(np.float32)
+        row = b / np.float32(SLIM_INPUT_DIV) - np.float32(SLIM_INPUT_SUB)
+        return np.ascontiguousarray(np.tile(row, (3, 1)).astype(np.float32))
     if network == "inception-2015" and normalize_input and not scale_pm1:
         from .inception import INCEPTION_2015_INPUT_DIV, INCEPTION_2015_INPUT_SUB
         b = np.arange(256, dtype=np.float32)
         row = (b - np.float32(INCEPTION_2015_INPUT_SUB)) / np.float32(INCEPTION_2015_INPUT_DIV)
         return np.ascontiguousarray(np.tile(row, (3, 1)).astype(np.float32))
-    if network not in ("torchvision", "inception-2015"):
+    if network not in ("torchvision", "inception-2015", "slim"):
         raise ValueError(f"unknown network {network!r}")
     v = np.arange(256, dtype=np.float32) / np.float32(255.0)
     lut = np.empty((3, 256), dtype=np.float32)

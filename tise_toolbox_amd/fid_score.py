@@ -31,7 +31,7 @@ import sys
 import time
 _T_IMPORT0 = time.time()
 import warnings
-from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
+from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
 
 import numpy as np
 import torch
@@ -63,6 +63,19 @@ def _timing(label, t0=None):
     return time.time()
 
 
+# the networks FID is taken on: the reference never takes FID on the TF-slim bird network (it serves IS* for CUB only)
+FID_NETWORKS = tuple(n for n in NETWORKS if n != "slim")
+
+
+def _fid_network(value):
+    if value == "slim":
+        raise ArgumentTypeError("the slim network (TF-slim InceptionV3 of the reference's IS* for CUB birds) has no FID in the "
+                                f"reference; choose from {', '.join(FID_NETWORKS)}")
+    if value not in FID_NETWORKS:
+        raise ArgumentTypeError(f"invalid choice: {value!r} (choose from {', '.join(FID_NETWORKS)})")
+    return value
+
+
 def _build_parser():
     parser = ArgumentParser(formatter_class=ArgumentDefaultsHelpFormatter)
     parser.add_argument("--batch-size", type=int, default=64, help="Batch size to use")
@@ -75,7 +88,7 @@ def _build_parser():
     parser.add_argument("--saved_file", type=str, default="")
     parser.add_argument("--weights", type=str, default=None, help="torchvision-format InceptionV3 state_dict (.pth)")
     parser.add_argument("--num-classes", type=int, default=None, help="classifier width (default: 1000, 1008 for --network inception-2015)")
-    parser.add_argument("--network", type=str, default="torchvision", choices=list(NETWORKS),
+    parser.add_argument("--network", type=_fid_network, default="torchvision", metavar="{" + ",".join(FID_NETWORKS) + "}",
                         help="torchvision: torchvision's InceptionV3 (the reference's FID wrapper); inception-2015: the "
                              "TensorFlow Inception-2015 graph pytorch-fid and TTUR take FID on (pt_inception-2015-12-05-6726825d.pth); "
                              "--save-stats then tags the .npz with network=inception-2015")

@@ -15,6 +15,7 @@ layer, no separate normalisation pass), the whole trunk runs channels-last so th
 HIP resize kernel can emit the input layout directly, and the input affine of
 ``inception.py:120-124`` is fused into that resize kernel's lookup table.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -25,14 +26,32 @@ import torch.nn.functional as F
 # (image_realism/IS/coco/inception_score_star_coco.py:64-108) and pytorch-fid / TTUR take FID on; its weights are
 # pytorch-fid's conversion pt_inception-2015-12-05-6726825d.pth (torchvision key names, no AuxLogits, fc 1008 x 2048).
 # Same module tree; it differs in its pool branches (``POOL_BRANCHES``), its 1008-class head and its input table.
-NETWORKS = ("torchvision", "inception-2015")
+# "slim": the 2016 TF-slim InceptionV3 (image_realism/IS/bird/inception/slim/inception_model.py) that the reference's IS*
+# for CUB birds runs, fine-tuned to 50 bird classes + background class 0 (inception_score_star_bird.py:181: 51 logits) and
+# restored from a TensorFlow checkpoint (tf_checkpoint.py, slim_variable_map).  Same module tree; every pool branch is TF's
+# SAME average (excluding the padding, Mixed_7c too), its BatchNorms have no gamma (slim/ops.py batch_norm scale=False,
+# eps 0.001: loaded as weight = 1 exactly), its classifier is biased and there is no AuxLogits on the pool3 path.
+NETWORKS = ("torchvision", "inception-2015", "slim")
+# head width of the two networks that FID and IS* share; the bird head is SLIM_CLASSES.  network_classes() covers all three.
 NETWORK_CLASSES = {"torchvision": 1000, "inception-2015": 1008}
+SLIM_CLASSES = 51
+
+
+def network_classes(network):
+    """Classifier width of a network's own head: 1000 / 1008 / 51."""
+    return SLIM_CLASSES if network == "slim" else NETWORK_CLASSES[network]
 # Input of the Inception-2015 graph: the uint8 image v (299 x 299 from the PIL-exact resize; the graph's own
 # ResizeBilinear 299 -> 299 is the identity) becomes (v - SUB) / DIV on every channel.  These are the graph's Sub / Mul
 # nodes AS COMMONLY DOCUMENTED (pytorch-fid's FIDInceptionV3 uses the same map); nobody has checked them against a copy
 # of the .pb file.  Every user of the constants reads them here (device.make_lut, InceptionV3.preprocess).
 INCEPTION_2015_INPUT_SUB = 128.0
 INCEPTION_2015_INPUT_DIV = 128.0
+# Input of the slim network: inception_score_star_bird.py:64-71 -- ``scipy.misc.imresize(img, (299, 299, 3),
+# interp="bilinear")``, then ``img.astype(np.float32) / 127.5 - 1.0``, in that fp32 order.  SciPy <= 1.2's imresize is
+# ``Image.fromarray(img).resize((299, 299), Image.BILINEAR)`` on the uint8 image, which the device resize reproduces
+# (csrc/resize.hip, Pillow-exact); that SciPy cannot be run here, so the equality rests on its published source.
+SLIM_INPUT_DIV = 127.5
+SLIM_INPUT_SUB = 1.0
 # branch_pool of each mixed block: "avg" = avg_pool2d(3, 1, 1) with count_include_pad (torchvision), "avg_excl" = the same
 # with count_include_pad=False (TensorFlow's SAME average: divisor 4 at corners, 6 on edges, 9 inside), "max" =
 # max_pool2d(3, 1, 1), padding acting as -inf (the 2015 graph's Mixed_7c).  The 1x1 conv of the branch follows the pool.
@@ -40,6 +59,7 @@ _MIXED_POOLED = ("Mixed_5b", "Mixed_5c", "Mixed_5d", "Mixed_6b", "Mixed_6c", "Mi
 POOL_BRANCHES = {
     "torchvision": {name: "avg" for name in _MIXED_POOLED},
     "inception-2015": dict({name: "avg_excl" for name in _MIXED_POOLED}, Mixed_7c="max"),
+    "slim": {name: "avg_excl" for name in _MIXED_POOLED},
 }
 
 
@@ -284,6 +304,8 @@ def seeded_init_(net, seed=0, calibration="fid"):
             m.weight.copy_(torch.randn(m.weight.shape, generator=g) * (2.0 / fan_in) ** 0.5)
         elif isinstance(m, nn.BatchNorm2d):
             m.weight.copy_(1.0 + 0.1 * torch.randn(m.weight.shape, generator=g))
+            if network == "slim":        # no gamma in the slim graph: its checkpoint cannot hold any other value
+                m.weight.fill_(1.0)
             m.bias.copy_(0.1 * torch.randn(m.bias.shape, generator=g))
             m.running_mean.zero_()
             m.running_var.fill_(1.0)
@@ -303,6 +325,8 @@ def seeded_init_(net, seed=0, calibration="fid"):
         x = (x - 0.5) / 0.5
     elif network == "inception-2015":    # the 2015 graph's input map on 0..255 pixel values
         x = (x * 255.0 - INCEPTION_2015_INPUT_SUB) / INCEPTION_2015_INPUT_DIV
+    elif network == "slim":              # the bird script's input map on 0..255 pixel values
+        x = x * 255.0 / SLIM_INPUT_DIV - SLIM_INPUT_SUB
     else:                                # FID wrapper convention: inception.py:120-124 on [0, 1] pixels
         x[:, 0] = x[:, 0] * (0.229 / 0.5) + (0.485 - 0.5) / 0.5
         x[:, 1] = x[:, 1] * (0.224 / 0.5) + (0.456 - 0.5) / 0.5
@@ -323,7 +347,10 @@ def seeded_init_(net, seed=0, calibration="fid"):
     # with them the absolute |dFID| <= 1e-3 budget -- sit in the range the reference publishes (2..200)
     for name in ("branch1x1", "branch3x3_2a", "branch3x3_2b", "branch3x3dbl_3a", "branch3x3dbl_3b", "branch_pool"):
         bn = getattr(net.Mixed_7c, name).bn
-        bn.weight.mul_(0.7)
+        if network == "slim":            # the same scaling without a gamma: through the variance
+            bn.running_var.add_(bn.eps).div_(0.49).sub_(bn.eps)
+        else:
+            bn.weight.mul_(0.7)
         bn.bias.mul_(0.7)
     net.eval()
     feats = _trunk_forward(net, x)
@@ -424,7 +451,9 @@ def build_inception3(weights=None, num_classes=None, seed=0, calibration="fid", 
 
     ``network="inception-2015"``: the 2015 graph's tree without ``AuxLogits`` (pytorch-fid's weight file has none); the
     file is loaded strictly, so a torchvision file fails here and a pytorch-fid file fails for the default network.
-    ``num_classes`` None: the network's own head (1000 / 1008).
+    ``network="slim"``: the TF-slim tree without ``AuxLogits``; ``weights`` is a TensorFlow checkpoint path (V1 file or V2
+    prefix), read by tf_checkpoint.py through ``slim_variable_map`` (the exponential-moving-average shadows).
+    ``num_classes`` None: the network's own head (1000 / 1008 / 51).
 
     The module tree is built WITHOUT storage (``meta`` device) and the loaded tensors are assigned to it
     (``load_state_dict(assign=True)``): torch's default initialisation of 96 convolutions (kaiming_uniform_ over 24 M
@@ -433,10 +462,12 @@ def build_inception3(weights=None, num_classes=None, seed=0, calibration="fid", 
     scratch (no cache file yet) does the skeleton get real storage first."""
     check_network(network)
     if num_classes is None:
-        num_classes = NETWORK_CLASSES[network]
+        num_classes = network_classes(network)
     with torch.device("meta"), _no_default_init():
         net = Inception3(num_classes=num_classes, aux_logits=network == "torchvision", network=network)
-    if weights is not None:
+    if weights is not None and network == "slim":
+        net.load_state_dict(load_slim_checkpoint(weights, net), strict=True, assign=True)
+    elif weights is not None:
         sd = torch.load(weights, map_location="cpu")
         if isinstance(sd, dict) and "state_dict" in sd:
             sd = sd["state_dict"]
@@ -448,6 +479,91 @@ def build_inception3(weights=None, num_classes=None, seed=0, calibration="fid", 
             for prm in net.parameters():
                 prm.detach().zero_()
     return net.eval()
+
+
+# ---- the slim network's TensorFlow checkpoint -------------------------------------------------------------------------
+# TF variable scope of every BasicConv2d on the pool3 path (inception_model.py: the outer name_scope adds nothing to variable
+# names; ``ops.conv2d`` without a scope opens variable_scope(None, "Conv"), uniquified per enclosing scope as Conv, Conv_1, ...
+# in call order).  tests/golden/slim_inception_v3_variables.json, recorded from the reference's own code, pins these names.
+def _slim_conv_scopes():
+    out = {"Conv2d_1a_3x3": "conv0", "Conv2d_2a_3x3": "conv1", "Conv2d_2b_3x3": "conv2", "Conv2d_3b_1x1": "conv3",
+           "Conv2d_4a_3x3": "conv4"}
+
+    def convs(block, tf_block, branches):
+        for tf_branch, names in branches:
+            for i, name in enumerate(names):
+                out[f"{block}.{name}"] = f"{tf_block}/{tf_branch}/Conv" + (f"_{i}" if i else "")
+    a = [("branch1x1", ["branch1x1"]), ("branch5x5", ["branch5x5_1", "branch5x5_2"]),
+         ("branch3x3dbl", ["branch3x3dbl_1", "branch3x3dbl_2", "branch3x3dbl_3"]), ("branch_pool", ["branch_pool"])]
+    for block, tf_block in (("Mixed_5b", "mixed_35x35x256a"), ("Mixed_5c", "mixed_35x35x288a"), ("Mixed_5d", "mixed_35x35x288b")):
+        convs(block, tf_block, a)
+    convs("Mixed_6a", "mixed_17x17x768a", [("branch3x3", ["branch3x3"]),
+                                           ("branch3x3dbl", ["branch3x3dbl_1", "branch3x3dbl_2", "branch3x3dbl_3"])])
+    c = [("branch1x1", ["branch1x1"]), ("branch7x7", ["branch7x7_1", "branch7x7_2", "branch7x7_3"]),
+         ("branch7x7dbl", ["branch7x7dbl_1", "branch7x7dbl_2", "branch7x7dbl_3", "branch7x7dbl_4", "branch7x7dbl_5"]),
+         ("branch_pool", ["branch_pool"])]
+    for block, tf_block in (("Mixed_6b", "mixed_17x17x768b"), ("Mixed_6c", "mixed_17x17x768c"),
+                            ("Mixed_6d", "mixed_17x17x768d"), ("Mixed_6e", "mixed_17x17x768e")):
+        convs(block, tf_block, c)
+    convs("Mixed_7a", "mixed_17x17x1280a", [("branch3x3", ["branch3x3_1", "branch3x3_2"]),
+                                            ("branch7x7x3", ["branch7x7x3_1", "branch7x7x3_2", "branch7x7x3_3", "branch7x7x3_4"])])
+    e = [("branch1x1", ["branch1x1"]), ("branch3x3", ["branch3x3_1", "branch3x3_2a", "branch3x3_2b"]),
+         ("branch3x3dbl", ["branch3x3dbl_1", "branch3x3dbl_2", "branch3x3dbl_3a", "branch3x3dbl_3b"]),
+         ("branch_pool", ["branch_pool"])]
+    for block, tf_block in (("Mixed_7b", "mixed_8x8x2048a"), ("Mixed_7c", "mixed_8x8x2048b")):
+        convs(block, tf_block, e)
+    return out
+
+
+SLIM_EMA_SUFFIX = "/ExponentialMovingAverage"
+
+
+def slim_variable_map():
+    """{Inception3 state_dict key: (checkpoint tensor name, layout)} of the slim network's pool3 and logits ancestors.
+
+    The names are those ``tf.train.ExponentialMovingAverage(0.9999).variables_to_restore()`` gives the bird script's Saver
+    (inception_score_star_bird.py:196-201): every trainable or moving-average variable -- conv weights, BatchNorm beta,
+    moving mean and variance, the classifier's weights and biases -- is read from ``<variable>/ExponentialMovingAverage``.
+    layout "conv": TF [kh, kw, cin, cout] -> torch [cout, cin, kh, kw]; "fc": [2048, C] -> [C, 2048]; "vec": as stored.
+    The auxiliary head and optimizer slots are not read."""
+    out = {}
+    for mod, scope in _slim_conv_scopes().items():
+        out[f"{mod}.conv.weight"] = (f"{scope}/weights{SLIM_EMA_SUFFIX}", "conv")
+        for key, var in (("bias", "beta"), ("running_mean", "moving_mean"), ("running_var", "moving_variance")):
+            out[f"{mod}.bn.{key}"] = (f"{scope}/BatchNorm/{var}{SLIM_EMA_SUFFIX}", "vec")
+    out["fc.weight"] = (f"logits/logits/weights{SLIM_EMA_SUFFIX}", "fc")
+    out["fc.bias"] = (f"logits/logits/biases{SLIM_EMA_SUFFIX}", "vec")
+    return out
+
+
+def load_slim_checkpoint(path, net):
+    """state_dict of ``net`` (an Inception3 with network="slim") from the TensorFlow checkpoint ``path``: the tensors of
+    ``slim_variable_map`` re-laid out, BatchNorm weight = 1 exactly (slim has no gamma), bias = beta.  Shapes are checked
+    against the module tree, so a checkpoint of another class count is refused with the tensor's name."""
+    from . import tf_checkpoint
+    vmap = slim_variable_map()
+    tensors = tf_checkpoint.read_tensors(path, [name for name, _ in vmap.values()])
+    want = net.state_dict()
+    sd = {}
+    for key, ref in want.items():
+        if key in vmap:
+            name, layout = vmap[key]
+            a = tensors[name]
+            if layout == "conv" and a.ndim == 4:
+                a = a.transpose(3, 2, 0, 1)
+            elif layout == "fc" and a.ndim == 2:
+                a = a.T
+            if tuple(a.shape) != tuple(ref.shape):
+                raise tf_checkpoint.CheckpointError(f"{path}: tensor {name} has shape {list(tensors[name].shape)}, the slim "
+                                                    f"network needs {list(ref.shape)} for {key}")
+            sd[key] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        elif key.endswith(".bn.weight"):
+            sd[key] = torch.ones(ref.shape, dtype=torch.float32)
+        elif key.endswith(".num_batches_tracked"):
+            sd[key] = torch.zeros((), dtype=torch.long)
+        else:
+            raise KeyError(f"no checkpoint tensor for {key}")
+    return sd
 
 
 class InceptionV3(nn.Module):
@@ -528,6 +644,8 @@ class InceptionV3(nn.Module):
             x = F.interpolate(x, size=(299, 299), mode="bilinear", align_corners=True)
         if self.normalize_input and self.network == "inception-2015":     # the 2015 graph's Sub / Mul on 0..255 values
             return (x * 255.0 - INCEPTION_2015_INPUT_SUB) / INCEPTION_2015_INPUT_DIV
+        if self.normalize_input and self.network == "slim":               # inception_score_star_bird.py:70 on 0..255 values
+            return x * 255.0 / SLIM_INPUT_DIV - SLIM_INPUT_SUB
         if self.normalize_input:                                            # :120-124
             x = x.clone()
             x[:, 0] = x[:, 0] * (0.229 / 0.5) + (0.485 - 0.5) / 0.5

@@ -28,7 +28,7 @@ import torch.utils.data
 
 from . import _lib, device, dist as tdist, img_data, weights as tweights
 from .engine import RealismEngine, T_BIRD, T_COCO, T_OIS, require_gpu
-from .inception import NETWORK_CLASSES, NETWORKS
+from .inception import NETWORKS, network_classes
 
 warnings.filterwarnings("ignore")
 
@@ -178,14 +178,18 @@ def _build_parser():
     parser.add_argument("--rule", type=str, default="coco", choices=["coco", "bird", "ois"])
     parser.add_argument("--drop-first-class", action="store_true", help="bird: class 0 is background")
     parser.add_argument("--batch-size", type=int, default=50)
-    parser.add_argument("--weights", type=str, default=None, help="torchvision-format InceptionV3 state_dict (.pth)")
+    parser.add_argument("--weights", type=str, default=None,
+                        help="torchvision-format InceptionV3 state_dict (.pth); --network slim: a TensorFlow checkpoint")
     parser.add_argument("--synthetic-weights", action="store_true",
                         help="seeded stand-in parameters (plumbing / throughput only; results are tagged)")
-    parser.add_argument("--num-classes", type=int, default=None, help="classifier width (default: 1000, 1008 for --network inception-2015)")
+    parser.add_argument("--num-classes", type=int, default=None,
+                        help="classifier width (default: 1000, 1008 for --network inception-2015, 51 for --network slim)")
     parser.add_argument("--network", type=str, default="torchvision", choices=list(NETWORKS),
                         help="torchvision: torchvision's InceptionV3; inception-2015: the TensorFlow Inception-2015 graph of the "
                              "reference's IS* for COCO (pytorch-fid's pt_inception-2015-12-05-6726825d.pth: 1008 classes, "
-                             "exclude-padding average pools, max-pool branch in Mixed_7c, input (v - 128) / 128)")
+                             "exclude-padding average pools, max-pool branch in Mixed_7c, input (v - 128) / 128); slim: the "
+                             "TF-slim InceptionV3 of the reference's IS* for CUB birds (a TensorFlow checkpoint: 51 classes, "
+                             "exclude-padding average pools, no BatchNorm gamma, input v / 127.5 - 1)")
     parser.add_argument("--seed", type=int, default=0, help="seed of the --synthetic-weights parameters")
     parser.add_argument("--label", type=str, default="IS", choices=["IS", "O-IS", "bird"])
     parser.add_argument("--fc-bias", type=str, default="auto", choices=["auto", "on", "off"],
@@ -198,7 +202,9 @@ def _build_parser():
 def main(argv=None):
     args = _build_parser().parse_args(argv)
     if args.num_classes is None:
-        args.num_classes = NETWORK_CLASSES[args.network]
+        args.num_classes = network_classes(args.network)
+    if args.network == "slim" and args.rule == "bird":
+        args.drop_first_class = True          # the bird head's class 0 is background (inception_score_star_bird.py:180-189)
     rank, world, _ = tdist.init_from_env()
     if world == 1:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", str(args.gpu))   # :146

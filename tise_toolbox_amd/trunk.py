@@ -16,6 +16,9 @@ after the first rocprof pass (``profiles/r01a_*``: 35 % of a step was not convol
   ``torch.cat``;
 * the two stem max-pools absorb the preceding conv's bias + ReLU (``tise_maxpool3s2_nhwc``).
 
+``network="slim"``: every pool branch, Mixed_7c's included, is the exclude-padding average; Mixed_7c's fused 1x1 keeps its
+pool segment and ``tise_avgpool3_excl_bias_relu_*`` runs at 8 x 8 on it.
+
 ``network="inception-2015"`` (the model's ``network``): the average pools exclude the padding
 (``tise_avgpool3_excl_bias_relu_*``; the raw-conv-then-pool order stays valid, see csrc/trunk_ops.hip) and Mixed_7c's
 pool branch is a 3x3 / stride 1 max pool, which does not commute with the conv: it runs first, on the block input
@@ -79,8 +82,10 @@ class FusedTrunk:
 
             b0, b1, b2, b3 = "blocks.0.", "blocks.1.", "blocks.2.", "blocks.3."
             self.network = getattr(model, "network", "torchvision")
-            # every average pool of a network has the same rule: count_include_pad (torchvision) or not (inception-2015)
-            self.avg_excl = self.network == "inception-2015"
+            # every average pool of a network has the same rule: count_include_pad (torchvision) or not (inception-2015,
+            # slim); inception.POOL_BRANCHES alone decides it
+            from .inception import POOL_BRANCHES
+            self.avg_excl = "avg_excl" in POOL_BRANCHES[self.network].values()
             self.last_block = model.last_needed_block
             self.c1a, self.c2a, self.c2b = conv(b0 + "0"), conv(b0 + "1"), conv(b0 + "2")
             if self.last_block >= 1:
@@ -362,9 +367,12 @@ class SplitTrunk(FusedTrunk):
         """(n, classes) fp32 logits of the pool3 rows of the LAST forward pass (their split form was kept by _global_mean)."""
         fs = self._feat_split
         assert self.sfc is not None and fs is not None and fs.shape[0] == n, "fc_logits follows a forward pass of the same batch"
-        out = torch.empty((n, 1, 1, self.sfc.cout), dtype=torch.float32, device=fs.device)
+        # the epilogue stores whole 8-cout chunks: a row of the destination is padded to a multiple of 8 (51 bird logits ->
+        # 56), the kernel's zero-weight couts land in the padding and the logits are a row-strided view of it
+        ld = -(-self.sfc.cout // 8) * 8
+        out = torch.empty((n, 1, 1, ld), dtype=torch.float32, device=fs.device)
         self.sfc(fs, [(0, self.sfc.cout, out, 0, 1)])
-        out = out.view(n, self.sfc.cout)
+        out = out.view(n, ld) if ld == self.sfc.cout else out.view(n, ld)[:, :self.sfc.cout]
         if bias and self.fc_bias is not None:
             out = out + self.fc_bias
         return out

@@ -28,6 +28,10 @@ _KINDS = {
     # path pytorch-fid caches it under
     "inception2015": ("Inception-2015 graph (pytorch-fid pt_inception-2015-12-05-6726825d.pth)",
                       lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "pt_inception-2015-12-05-6726825d.pth")]),
+    # the TF-slim InceptionV3 of the reference's IS* for CUB birds: a TensorFlow checkpoint (V1 file or V2 prefix) at the
+    # path of inception_score_star_bird.py:35-39, relative to the working directory as there
+    "slim": ("TF-slim InceptionV3 fine-tuned on CUB birds (TensorFlow checkpoint birds_valid299/model.ckpt)",
+             lambda: [os.path.join("IS", "bird", "inception_finetuned_models", "birds_valid299", "model.ckpt")]),
     "clip": ("CLIP ViT-B/32", lambda: [os.path.expanduser(os.path.join("~", ".cache", "clip", "ViT-B-32.pt"))]),
 }
 
@@ -45,7 +49,14 @@ def inception_kind(network, label_80=False):
     """The ``_KINDS`` entry of an InceptionV3 run: ``label_80`` = the 80-class fine-tune (O-IS / O-FID with 80 classes)."""
     if network == "inception-2015":
         return "inception2015"
+    if network == "slim":
+        return "slim"
     return "inception80" if label_80 else "inception"
+
+
+def _exists(path, kind):
+    """A TensorFlow checkpoint path names a V1 file or the prefix of a V2 checkpoint (``path.index`` + data shards)."""
+    return os.path.exists(path) or (kind == "slim" and os.path.exists(path + ".index"))
 
 
 def resolve(weights, synthetic, kind):
@@ -59,11 +70,11 @@ def resolve(weights, synthetic, kind):
         warn_synthetic(what)
         return None, SYNTHETIC_TAG
     if weights:
-        if not os.path.exists(weights):
+        if not _exists(weights, kind):
             raise RuntimeError("Invalid path: %s" % weights)
         return weights, ""
     for p in defaults():
-        if os.path.exists(p):
+        if _exists(p, kind):
             print(f"[tise] {what}: parameters from {p}", file=sys.stderr, flush=True)
             return p, ""
     raise RuntimeError(
