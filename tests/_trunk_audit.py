@@ -1,0 +1,497 @@
+"""Launch recorder and fp64 references for tests/test_gpu_trunk_launches.py (helper, no tests).
+
+While a ``SplitTrunk`` forward runs, ``Recorder`` intercepts ``SplitConv.__call__`` with the integer ``code`` it hands to
+``tise_conv_split_f16`` and every other ``tise_*`` entry point the trunk reaches through ``_lib.call``, and keeps the
+operands AS THAT LAUNCH SAW THEM: a clone of the input, a clone of every destination before and after the call, the
+segment list and the integer arguments.  ``check_launch`` then computes the same operation in fp64 from the recorded
+input of that launch alone, so no error is carried from one layer into the next, and compares at the tolerance the
+project uses for that kernel on its own.
+
+The fp64 references need each convolution's ORIGINAL weights: ``keep_weights`` wraps ``SplitConv.__init__`` and keeps
+``(weight.double(), bias.double())`` beside each instance -- never unpacked from ``SplitConv.w`` / ``w_fast``, which
+would test the packing with itself.  The split layout (csrc/common.h) is restated here (``split_index``) instead of
+imported from conv_split.py for the same reason.
+
+Nothing here touches a device at import time.
+"""
+import contextlib
+
+import torch
+import torch.nn.functional as F
+
+CONV_TOL = 4e-6        # of the launch's output scale: test_gpu_kernels.py, every convolution test against fp64
+AVG_TOL = 2e-6         # of max(1, output scale): test_gpu_inception2015.py::test_exclude_padding_avgpool_split_vs_fp64
+FC_TOL = 2e-6          # of the logit scale
+U24 = 2.0 ** -24       # unit roundoff of fp32
+
+# name -> (input pointer positions, destination pointer positions) among the arguments of _lib.call(name, *args)
+KNOWN = {
+    "tise_stem_conv3x3s2_split": ((0,), (6,)),
+    "tise_stem_conv3x3s2_split_u8": ((0, 1), (7,)),
+    "tise_stem_conv3x3s2_split_u8_mfma": ((0, 1), (8,)),
+    "tise_maxpool3s2_split_nhwc": ((0,), (7,)),
+    "tise_maxpool3s1p1_split_nhwc": ((0,), (7,)),
+    "tise_avgpool3_bias_relu_split_nhwc": ((0, 7), (8,)),
+    "tise_avgpool3_excl_bias_relu_split_nhwc": ((0, 7), (8,)),
+    "tise_split_mean_nhwc": ((0,), (4,)),
+    "tise_split_mean_both_nhwc": ((0,), (4, 5)),
+}
+STEMS = ("tise_stem_conv3x3s2_split", "tise_stem_conv3x3s2_split_u8", "tise_stem_conv3x3s2_split_u8_mfma")
+
+
+# ---------------------------------------------------------------------------------------------------- split layout
+def split_index(C, device):
+    """Positions of the hi and the lo half of channel c inside a (..., 2C) split row: blocks of 32 channels as
+    [hi x32 | lo x32], then a last block [hi x16 | lo x16] when C % 32 == 16."""
+    assert C % 16 == 0
+    c = torch.arange(C, device=device)
+    full = C & ~31
+    hi = torch.where(c < full, (c // 32) * 64 + c % 32, 2 * full + (c - full))
+    lo = torch.where(c < full, hi + 32, hi + 16)
+    return hi, lo
+
+
+def merge64(t):
+    """split tensor (..., 2C) fp16 -> fp64 (..., C), hi + lo * 2**-11 (exact)."""
+    hi, lo = split_index(t.shape[-1] // 2, t.device)
+    return t[..., hi].double() + t[..., lo].double() * (2.0 ** -11)
+
+
+def raw_mask(C, c0, c1, split, device):
+    """Boolean mask over the raw last dimension of a destination row: the elements that hold channels [c0, c1)."""
+    if not split:
+        m = torch.zeros(C, dtype=torch.bool, device=device)
+        m[c0:c1] = True
+        return m
+    hi, lo = split_index(C, device)
+    m = torch.zeros(2 * C, dtype=torch.bool, device=device)
+    m[hi[c0:c1]] = True
+    m[lo[c0:c1]] = True
+    return m
+
+
+def bits(t):
+    """The tensor's bit patterns (uninitialised memory may hold NaNs, which never compare equal as numbers)."""
+    return t.contiguous().view({2: torch.int16, 4: torch.int32, 1: torch.uint8}[t.element_size()])
+
+
+# ------------------------------------------------------------------------------------------------------- recording
+class Launch:
+    """One kernel launch: ``name``, the cloned ``inputs``, ``dsts`` = [(before, after)] per distinct destination tensor,
+    and for a convolution ``conv`` (the SplitConv), ``segs`` = [(c0, c1, destination index, off, mode)], ``kw``, ``code``
+    and ``args`` (the ConvArgs fields as passed); for the others ``ints`` = the call's integer arguments by position."""
+
+    def __init__(self, name):
+        self.name = name
+        self.inputs, self.dsts = [], []
+        self.conv = self.segs = self.kw = self.code = self.args = None
+        self.ints = {}
+        self.in_ptr = None
+        self.dst_ptrs = []
+
+    def __repr__(self):
+        if self.conv is not None:
+            c = self.conv
+            return (f"{self.args['H']}x{self.args['W']}x{c.cin}->{c.cout} k{c.kh}x{c.kw} s{c.stride[0]} p{c.padding} "
+                    f"code {self.code:#x} {self.kw or ''}")
+        return f"{self.name} {[v for _, v in sorted(self.ints.items())]}"
+
+
+@contextlib.contextmanager
+def keep_weights():
+    """While active every new SplitConv keeps ``_audit_wb`` = (weight.double(), bias.double()) on its own device."""
+    from tise_toolbox_amd.conv_split import SplitConv
+    orig = SplitConv.__init__
+
+    def init(self, weight, bias, *a, **k):
+        orig(self, weight, bias, *a, **k)
+        self._audit_wb = (weight.detach().double().to(self.scale.device), bias.detach().double().to(self.scale.device))
+    SplitConv.__init__ = init
+    try:
+        yield
+    finally:
+        SplitConv.__init__ = orig
+
+
+class Recorder:
+    """``with Recorder() as rec: trunk.forward_u8(...)`` -> ``rec.launches``.  A ``tise_*`` name the recorder does not know
+    is an error: a future kernel cannot slip past the audit."""
+
+    def __init__(self, sync=None):
+        self.launches = []
+        self._stack, self._tensors = [], {}
+        self._sync = sync or torch.cuda.synchronize
+
+    def _clone(self, t):
+        self._sync()
+        return t.detach().clone()
+
+    def __enter__(self):
+        from tise_toolbox_amd import _lib, trunk
+        from tise_toolbox_amd.conv_split import SplitConv
+        rec = self
+        self._orig = (SplitConv.__call__, _lib.call, trunk._p)
+        orig_call, orig_lib, orig_p = self._orig
+        self._kw = keep_weights()
+        self._kw.__enter__()
+
+        def p(t):                                                # trunk._p: remember which tensor a raw pointer is
+            rec._tensors[t.data_ptr()] = t
+            return orig_p(t)
+
+        def conv_call(self, xs, segs, pooled_input=False, **kw):   # signature handling as tools/split_layer_probe.py
+            fr = dict(conv=self, segs=list(segs), kw=dict(kw, pooled_input=pooled_input), launch=None)
+            uniq = []
+            for sg in segs:
+                if all(sg[2] is not u for u in uniq):
+                    uniq.append(sg[2])
+            fr["uniq"] = uniq
+            x0 = rec._clone(xs)
+            before = [rec._clone(u) for u in uniq]
+            rec._stack.append(fr)
+            try:
+                r = orig_call(self, xs, segs, pooled_input=pooled_input, **kw)
+            finally:
+                rec._stack.pop()
+            L = fr["launch"]
+            if L is not None:                                     # this frame launched (not the one that handed on to a _fallback)
+                L.inputs = [x0]
+                L.dsts = [(b, rec._clone(u)) for b, u in zip(before, uniq)]
+                L.in_ptr, L.dst_ptrs = xs.data_ptr(), [u.data_ptr() for u in uniq]
+            return r
+
+        def lib_call(name, *args):
+            if name == "tise_conv_split_f16":
+                assert rec._stack, "tise_conv_split_f16 outside SplitConv.__call__"
+                fr = rec._stack[-1]
+                assert fr["launch"] is None, "two launches from one SplitConv.__call__"
+                a = args[0]._obj
+                L = Launch(name)
+                L.conv, L.kw, L.code = fr["conv"], {k: v for k, v in fr["kw"].items() if v}, int(args[1])
+                L.segs = [(c0, c1, next(i for i, u in enumerate(fr["uniq"]) if u is d), off, mode) for c0, c1, d, off, mode in fr["segs"]]
+                L.args = {f: getattr(a, f) for f in ("N", "H", "W", "Cin", "KH", "KW", "SH", "SW", "PH", "PW", "OH", "OW", "Cout", "K",
+                                                     "Kpad", "M", "nseg", "out_hp", "out_wp", "out_y0", "out_x0")}
+                fr["launch"] = L
+                rec.launches.append(L)
+                return orig_lib(name, *args)
+            if name not in KNOWN:
+                raise AssertionError(f"the trunk reached {name}, which the launch recorder does not know")
+            ins, outs = KNOWN[name]
+            L = Launch(name)
+
+            def tensor(i):
+                t = rec._tensors.get(args[i].value)
+                assert t is not None, (name, i)
+                return t
+            L.inputs = [rec._clone(tensor(i)) for i in ins]
+            dst = [tensor(i) for i in outs]
+            before = [rec._clone(t) for t in dst]
+            L.ints = {i: v for i, v in enumerate(args) if isinstance(v, int)}
+            L.in_ptr, L.dst_ptrs = args[ins[0]].value, [t.data_ptr() for t in dst]
+            r = orig_lib(name, *args)
+            L.dsts = [(b, rec._clone(t)) for b, t in zip(before, dst)]
+            rec.launches.append(L)
+            return r
+
+        SplitConv.__call__, _lib.call, trunk._p = conv_call, lib_call, p
+        return self
+
+    def __exit__(self, *exc):
+        from tise_toolbox_amd import _lib, trunk
+        from tise_toolbox_amd.conv_split import SplitConv
+        SplitConv.__call__, _lib.call, trunk._p = self._orig
+        self._kw.__exit__(*exc)
+        self._tensors.clear()
+
+
+# ------------------------------------------------------------------------------------------------------ references
+def _nchw(x):
+    return x.permute(0, 3, 1, 2)
+
+
+def _nhwc(x):
+    return x.permute(0, 2, 3, 1)
+
+
+def _untouched(L, di, own):
+    """Everything of destination ``di`` outside ``own`` (a bool tensor broadcastable to it: True = the launch's own
+    elements) must hold the bits it held before the call."""
+    before, after = L.dsts[di]
+    same = bits(before) == bits(after)
+    assert bool((same | own).all()), f"{L!r}: destination {di} changed outside the launch's own slice"
+
+
+def conv_reference(L):
+    """fp64 NHWC (linear, relu(linear + bias), output scale) of a recorded convolution launch from the launch's own input;
+    the activated result is on the grid of the destinations (pooled for pool_output / pool_h)."""
+    c, kw = L.conv, L.kw
+    w, b = c._audit_wb
+    x = _nchw(merge64(L.inputs[0]))
+    pin = kw.get("pooled_input")
+    if pin == "v":
+        x = F.max_pool2d(x, (3, 1), (2, 1))                       # three vertical taps at stride 2
+    elif pin:
+        x = F.max_pool2d(x, 3, 2)
+    lin = F.conv2d(x, w, None, c.stride, c.padding)
+    act = torch.relu(lin + b.view(1, -1, 1, 1))
+    scale = act.abs().max().item()
+    assert (L.args["OH"], L.args["OW"]) == tuple(lin.shape[2:]), (L, lin.shape)
+    if kw.get("pool_output"):
+        act = F.max_pool2d(act, 3, 2)
+    elif kw.get("pool_h"):
+        act = F.max_pool2d(act, (1, 3), (1, 2))                   # horizontal 3-tap max at stride 2
+    return _nhwc(lin), _nhwc(act), scale
+
+
+def check_conv(L, fc=False):
+    """Returns the launch's largest error as a fraction of its output scale (asserted <= the tolerance)."""
+    kw = L.kw
+    lin, act, scale = conv_reference(L)
+    tol = CONV_TOL
+    if fc:                                                        # raw logits: of the logit scale
+        tol, scale = FC_TOL, lin.abs().max().item()
+    pooled = bool(kw.get("pool_output") or kw.get("pool_h"))
+    out_pad = kw.get("out_pad")
+    n, gh, gw = act.shape[:3]
+    worst = 0.0
+    masks = [None] * len(L.dsts)
+    for c0, c1, di, off, mode in L.segs:
+        before, after = L.dsts[di]
+        split = mode == 0
+        assert not (pooled and not split)
+        C = after.shape[3] // 2 if split else after.shape[3]
+        got = merge64(after) if split else after.double()
+        want = (act if split else lin)[..., c0:c1]
+        if out_pad is not None:
+            hp, wp, y0, x0 = out_pad
+            assert tuple(after.shape[:3]) == (n, hp, wp)
+            inner = torch.zeros((hp, wp), dtype=torch.bool, device=after.device)
+            inner[y0:y0 + gh, x0:x0 + gw] = True
+            assert not bool(got[:, ~inner][..., off:off + c1 - c0].any()), f"{L!r}: the border of the destination is not zero"
+            got = got[:, y0:y0 + gh, x0:x0 + gw]
+            rows = inner.view(1, hp, wp, 1)
+        else:
+            assert tuple(after.shape[:3]) == (n, gh, gw), (L, after.shape, act.shape)
+            rows = torch.ones((1, 1, 1, 1), dtype=torch.bool, device=after.device)
+        err = (got[..., off:off + c1 - c0] - want).abs().max().item()
+        worst = max(worst, err / scale)
+        assert err <= tol * scale, f"{L!r}: segment [{c0}, {c1}) at offset {off}: error {err:.3e} > {tol:g} x scale {scale:.3e}"
+        # an fp32 segment receives whole 8-cout chunks (51 bird logits -> 56: the destination row is padded for them)
+        width = c1 - c0 if split else -(-(c1 - c0) // 8) * 8
+        m = raw_mask(C, off, off + width, split, after.device).view(1, 1, 1, -1) & rows
+        masks[di] = m if masks[di] is None else (masks[di] | m)
+    for di, m in enumerate(masks):
+        _untouched(L, di, m)
+    return worst
+
+
+def check_stem(L, trunk):
+    i = L.ints
+    w, b = trunk.c1a.w.double(), trunk.c1a.b.double()             # the folded fp32 parameters, not the kernels' packed forms
+    if L.name == "tise_stem_conv3x3s2_split":
+        x = L.inputs[0]
+        n, h, wd = i[1], i[2], i[3]
+        assert x.numel() == n * h * wd * 3 and x.dtype == torch.float32
+        x = x.reshape(n, h, wd, 3).double()
+    else:
+        u8, lut = L.inputs
+        n, h, wd = i[2], i[3], i[4]
+        assert u8.dtype == torch.uint8 and tuple(u8.shape) == (n, h, wd, 3) and lut.numel() == 768
+        x = torch.stack([lut.view(3, 256)[ch][u8[..., ch].long()] for ch in range(3)], -1).double()
+    want = _nhwc(torch.relu(F.conv2d(_nchw(x), w, b, 2)))
+    before, after = L.dsts[0]
+    assert tuple(after.shape) == (*want.shape[:3], 64)
+    scale = want.abs().max().item()
+    err = (merge64(after) - want).abs().max().item()
+    assert err <= CONV_TOL * scale, f"{L!r}: error {err:.3e} > {CONV_TOL:g} x scale {scale:.3e}"
+    return err / scale
+
+
+def check_pool(L):
+    """The two split max pools (bit-equal after merge) and the two split average pools (AVG_TOL); returns the error."""
+    i = L.ints
+    ld, x_off, n, h, w, C = i[1], i[2], i[3], i[4], i[5], i[6]
+    avg = "avgpool" in L.name
+    out_ld, out_off = (i[9], i[10]) if avg else (i[8], i[9])
+    x = L.inputs[0]
+    before, after = L.dsts[0]
+    assert tuple(x.shape) == (n, h, w, ld if avg else 2 * ld) and after.shape[3] == 2 * out_ld and after.shape[0] == n
+    if avg:
+        assert x.dtype == torch.float32 and L.inputs[1].numel() == C
+        raw = _nchw(x.double()[..., x_off:x_off + C])
+        want = torch.relu(F.avg_pool2d(raw, 3, 1, 1, count_include_pad="excl" not in L.name) + L.inputs[1].double().view(1, -1, 1, 1))
+    else:
+        xin = _nchw(merge64(x)[..., x_off:x_off + C])
+        want = F.max_pool2d(xin, 3, 2) if "3s2" in L.name else F.max_pool2d(xin, 3, 1, 1)      # max_pool2d pads with -inf
+    want = _nhwc(want)
+    assert tuple(after.shape[:3]) == tuple(want.shape[:3])
+    got = merge64(after)[..., out_off:out_off + C]
+    err = (got - want).abs().max().item()
+    if avg:
+        bound = AVG_TOL * max(1.0, want.abs().max().item())
+        assert err <= bound, f"{L!r}: error {err:.3e} > {bound:.3e}"
+    else:
+        assert torch.equal(got, want), f"{L!r}: not bit-equal to max_pool2d of the merged input (max difference {err:.3e})"
+    _untouched(L, 0, raw_mask(out_ld, out_off, out_off + C, True, after.device).view(1, 1, 1, -1))
+    return err
+
+
+def mean_emulation(v):
+    """fp32 (N, HW, C) -> (N, C): the HW values of a channel added in position order into one fp32 accumulator, then one
+    fp32 division by (float)HW -- a plain loop of HW tensor additions, vectorised over images and channels."""
+    acc = torch.zeros((v.shape[0], v.shape[2]), dtype=torch.float32, device=v.device)
+    for s in range(v.shape[1]):
+        acc = acc + v[:, s, :]
+    return acc / torch.tensor(float(v.shape[1]), dtype=torch.float32, device=v.device)
+
+
+def check_mean_values(x_split, hw, got):
+    """split_mean's fp32 output ``got`` (N, C) of the split tensor (N, HW, 2C) against the fp32 sequential emulation
+    (<= 1 ulp: the division) and the fp64 mean (recursive summation of non-negative terms: HW * 2**-24 * mean per channel).
+    Returns (largest ulp distance to the emulation, largest fp64 error, largest fp64 error / bound)."""
+    n = x_split.shape[0]
+    v64 = merge64(x_split.reshape(n, hw, -1))
+    v32 = v64.float()
+    assert torch.equal(v32.double(), v64)                         # hi + lo * 2**-11 is exact in fp32
+    assert bool((v64 >= 0).all()), "the bound is for non-negative terms (post-ReLU activations)"
+    emu = mean_emulation(v32)
+    ulps = (bits(got).long() - bits(emu).long()).abs().max().item()
+    assert ulps <= 1, f"split_mean at HW {hw}: {ulps} ulp from the fp32 sequential emulation"
+    mean = v64.mean(1)
+    bound = hw * U24 * mean
+    err = (got.double() - mean).abs()
+    assert bool((err <= bound).all()), f"split_mean at HW {hw}: fp64 error {err.max().item():.3e} beyond HW * 2^-24 * mean"
+    assert bool(((emu.double() - mean).abs() <= bound).all())     # ... which guards the emulation itself
+    ratio = (err / bound.clamp_min(1e-300)).max().item()
+    return ulps, err.max().item(), ratio
+
+
+def check_mean(L):
+    i = L.ints
+    n, hw, C = i[1], i[2], i[3]
+    x = L.inputs[0]
+    assert x.shape[0] == n and x.shape[1] * x.shape[2] == hw and x.shape[3] == 2 * C
+    feat = L.dsts[0][1]
+    assert tuple(feat.shape) == (n, C) and feat.dtype == torch.float32
+    res = check_mean_values(x, hw, feat)
+    if L.name == "tise_split_mean_both_nhwc":                     # the split row is the exact split of the fp32 row
+        row = L.dsts[1][1].reshape(n, 2 * C)
+        hi = feat.half()
+        lo = ((feat - hi.float()) * 2048.0).half()
+        ih, il = split_index(C, feat.device)
+        assert torch.equal(row[:, ih], hi) and torch.equal(row[:, il], lo)
+    return res
+
+
+def check_launch(L, trunk):
+    """Dispatch on the launch's kind; returns (kind, figure) for the printed table."""
+    if L.conv is not None:
+        fc = L.conv is getattr(trunk, "sfc", None)
+        return ("fc" if fc else "conv"), check_conv(L, fc)
+    if L.name in STEMS:
+        return "stem", check_stem(L, trunk)
+    if "pool" in L.name:
+        return "pool", check_pool(L)
+    return "mean", check_mean(L)
+
+
+# ------------------------------------------------------------------------------------- how the launches fit together
+def own_rows(L):
+    """[(destination index, 1-D bool mask over the destination's raw row)]: the elements of a pixel's row the launch writes."""
+    dev = L.dsts[0][1].device
+    if L.conv is not None:
+        out = {}
+        for c0, c1, di, off, mode in L.segs:
+            after = L.dsts[di][1]
+            split = mode == 0
+            C = after.shape[3] // 2 if split else after.shape[3]
+            m = raw_mask(C, off, off + (c1 - c0 if split else -(-(c1 - c0) // 8) * 8), split, dev)
+            out[di] = m if di not in out else (out[di] | m)
+        return sorted(out.items())
+    if "pool" in L.name:
+        i = L.ints
+        out_ld, out_off = (i[9], i[10]) if "avgpool" in L.name else (i[8], i[9])
+        return [(0, raw_mask(out_ld, out_off, out_off + i[6], True, dev))]
+    return [(di, torch.ones(d[1].shape[-1], dtype=torch.bool, device=dev)) for di, d in enumerate(L.dsts)]
+
+
+def check_assembly(launches):
+    """The segment lists of trunk.py as a whole: every element of every tensor a launch reads was written by exactly one
+    earlier launch -- a segment that lands 8 channels off inside a concat buffer overlaps its neighbour's slice (reported at
+    that launch) and leaves a gap (reported at the first launch that reads the buffer).  Returns the list of failures.
+    (Two whole branches of equal width written to each other's slices would pass here: every later layer then sees its
+    input channels permuted, which the end-to-end tests catch at any tolerance.)"""
+    state, fails = {}, []                                         # data pointer -> [written mask, sealed by a reader]
+    for k, L in enumerate(launches):
+        st = state.get(L.in_ptr)
+        if st is not None:
+            if not bool(st[0].all()) and not st[1]:
+                fails.append(f"launch {k}: {L!r} reads a tensor with {int((~st[0]).sum())} raw row elements no launch has written")
+            st[1] = True
+        for di, own in own_rows(L):
+            ptr = L.dst_ptrs[di]
+            st = state.get(ptr)
+            if st is None or st[1] or st[0].numel() != own.numel():
+                st = state[ptr] = [torch.zeros_like(own), False]   # a new tensor (the allocator hands addresses out again)
+            if bool((st[0] & own).any()):
+                fails.append(f"launch {k}: {L!r} writes {int((st[0] & own).sum())} raw row elements of destination {di} that an earlier launch wrote")
+            st[0] |= own
+    for ptr, st in state.items():
+        if not st[1] and not bool(st[0].all()):
+            fails.append(f"a tensor no launch read (an output of the forward) has {int((~st[0]).sum())} raw row elements unwritten")
+    return fails
+
+
+# ------------------------------------------------------------------------------------------------- what was launched
+def rowwin_np(ow, kw):
+    """Window pieces per wave of the row-window kernel (csrc/conv_split.hip rowwin_np)."""
+    j = (ow + 126) // ow + 1
+    return -(-(128 + j * (kw - 1) + 1) // 32)
+
+
+def instance_of(L):
+    """The kernel template instance a recorded convolution launch selects, as the dispatchers in csrc/conv_split.hip
+    (tise_conv_split_f16, launch_rowwin_any, launch_poolin) and csrc/conv_pipe.hip (launch_regw32, launch_regw32_pool) do."""
+    code, a = L.code, L.args
+    if code & 512:
+        assert code & 255 == 34
+        return ("pipe34", a["Cout"], "padded" if (a["PH"] | a["PW"]) else "unpadded",
+                "pooled" if code & 1024 else ("border" if a["out_hp"] else "plain"))
+    if code & 256:
+        return ("poolin", 2 if a["Cout"] <= 128 else 4, "VT" if code & 2048 else "9tap")
+    if code & 64:
+        return ("rowwin", code & 15, a["Cin"] % 32, rowwin_np(a["OW"], a["KW"]), "POOLH" if code & 2048 else "")
+    if code & 128:
+        return ("fast", code & 15, a["Cin"] % 32, "block" if code & 4096 else "tap")
+    return ("glds", code & 15, a["Cin"] % 32)
+
+
+def conv_members(launches):
+    """(Cin, Cout, kh, kw, sh, sw, ph, pw, OH, OW) of every convolution the launches compute: a fused 1x1 launch counts once
+    per segment; a launch that reads a zero-bordered buffer another launch filled (out_pad) carries that border as its padding."""
+    borders, out = {}, []
+    for L in launches:
+        if L.conv is None:
+            continue
+        c, a = L.conv, L.args
+        ph, pw = c.padding
+        if L.in_ptr in borders:
+            y0, x0 = borders[L.in_ptr]
+            ph, pw = ph + y0, pw + x0
+        if L.kw.get("out_pad"):
+            for p in L.dst_ptrs:
+                borders[p] = tuple(L.kw["out_pad"][2:])
+        for c0, c1, _, _, _ in L.segs:
+            out.append((c.cin, c1 - c0, c.kh, c.kw, *c.stride, ph, pw, a["OH"], a["OW"]))
+    return out
+
+
+def tensor_sizes(launches):
+    """{description: (elements per image, bytes per image)} of every activation tensor the launches read or wrote."""
+    out = {}
+    for L in launches:
+        for t in list(L.inputs[:1]) + [d[1] for d in L.dsts]:
+            n = t.shape[0]
+            key = f"{'x'.join(str(s) for s in t.shape[1:])} {str(t.dtype).replace('torch.', '')}"
+            out[key] = (t.numel() // n, t.numel() // n * t.element_size())
+    return out

@@ -485,7 +485,9 @@ def test_fused_trunk_matches_module_graph(dev, dims):
 def test_conv_split_matches_fp64_conv(dev, shape, variant):
     """3-term split fp16 MFMA conv vs an fp64 convolution: fp32-class accuracy (|err| <= 4e-6 of the
     output scale), including M/N/K tails, padding, stride, channel counts with Cin % 32 == 16 (input AND
-    destination tensors with a 16-channel tail block), for the default and the generic kernel."""
+    destination tensors with a 16-channel tail block), for the default and the generic kernel.
+    The per-kernel bounds are listed in one place in tests/test_gpu_trunk_launches.py, which applies this one to every
+    launch the trunk itself makes."""
     from tise_toolbox_amd.conv_split import SplitConv, merge, split
     H, W, Cin, Cout, kh, kw, st, pad = shape
     g = torch.Generator(device="cpu").manual_seed(Cin + Cout)
@@ -613,7 +615,9 @@ def test_conv_rowwin_kernel_matches_fp64_conv(dev, case):
     against an fp64 convolution at the default kernel's tolerance -- image-row and image boundaries inside tiles (the
     zero rows of the window), top / bottom padding (zero-page lines per kh), valid and asymmetric padding, Cin = 32 n + 16
     (tail groups pairing two taps per step, odd and even KW), M and Cout tails, three destination segments incl. raw
-    fp32, rows shorter than 8 pixels -- and bit-identical over repeated runs."""
+    fp32, rows shorter than 8 pixels -- and bit-identical over repeated runs.
+    The per-kernel bounds are listed in one place in tests/test_gpu_trunk_launches.py, which applies this one to every
+    launch the trunk itself makes."""
     from tise_toolbox_amd.conv_split import SplitConv, merge, split
     H, W, Cin, Cout, kh, kw, pad, tn, n = case
     g = torch.Generator(device="cpu").manual_seed(H + Cin + Cout + kw)
