@@ -69,6 +69,33 @@ int tise_png_unfilter_rgb8(const uint8_t* slots_dev, int64_t n, int64_t slot_str
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (a2) JPEG reconstruction on the device.  Replaces the second half of ``Image.open(f).convert("RGB")`` of
+ * Dataset.__getitem__ (image_realism/FID/img_data.py:19-25; third-party Pillow -> libjpeg-turbo: dequantisation, the accurate
+ * integer IDCT, "fancy" chroma upsampling, YCbCr -> RGB) for JPEG files.  The feed's decode threads only parse markers and
+ * Huffman-decode a file into a slot (libtise_jpeg.so, csrc/jpeg_decode.c: tise_jpeg_entropy_decode; slot layout in
+ * include/tise_jpeg.h); the slots are copied to HBM as they are and this call reconstructs the pixels of n images of
+ * DIFFERENT sizes in one launch pair (csrc/jpeg_idct.hip).  A slot of mode 0 holds pixels decoded on the host: copied.
+ *   slots_dev         n slots, slot_stride bytes apart (multiple of 16, 16-byte aligned base)
+ *   headers_host      the same n slot headers in HOST memory, header_stride bytes apart (the feed's pinned arena: stride =
+ *                     slot_stride).  Every size the kernels index with is taken from here and checked here -- against
+ *                     each other, slot_stride, dst_bytes and ws_bytes -- and reaches the kernels in a device table this
+ *                     call writes to the head of ws_dev (a stream-ordered copy the call waits for).
+ *   out_offsets_host  n byte offsets into dst_dev: image i is written as (h_i, w_i, 3) uint8 at dst_dev + offset, the layout
+ *                     tise_resize_u8 reads (offsets i * h * w * 3 give a dense (n, h, w, 3) tensor)
+ *   ws_dev            ws_bytes >= tise_jpeg_workspace_bytes(n, slot_stride) of device scratch, 16-byte aligned
+ *   table_host_pinned NULL, or 64 * n bytes of PAGE-LOCKED host scratch (8-byte aligned) the call builds the device table in and
+ *                     copies from asynchronously: the caller leaves it alone until the stream has passed this call.  NULL: the
+ *                     table is copied from a buffer of the call, which then waits for the stream to reach that copy.
+ * Bit-exact against Pillow (tests/test_gpu_jpeg.py).  Rejected before any HIP call (TISE_ERR_INVALID_ARG): a NULL pointer,
+ * n < 0, a misaligned base or stride, a header whose sampling, block counts or payload length disagree with its size, a slot
+ * beyond slot_stride, an output beyond dst_bytes, a workspace too small.  n > 65535: TISE_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+int tise_jpeg_workspace_bytes(int64_t n, int64_t slot_stride, size_t* bytes);
+int tise_jpeg_reconstruct_rgb8(const uint8_t* slots_dev, int64_t n, int64_t slot_stride, const uint8_t* headers_host,
+                               int64_t header_stride, const int64_t* out_offsets_host, uint8_t* dst_dev, int64_t dst_bytes,
+                               uint8_t* ws_dev, int64_t ws_bytes, uint8_t* table_host_pinned, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a3) PIL-exact uint8 bilinear resize + ToTensor + input affine, fused.
  * Replaces transforms.Resize((299,299)) + ToTensor()   image_realism/FID/fid_score.py:208-213
  * (Pillow ImagingResample, 8bpc: 22-bit fixed-point coefficients, horizontal pass -> u8 ->

@@ -1,0 +1,278 @@
+"""CPU: the host half of the JPEG feed (csrc/jpeg_decode.c -> libtise_jpeg.so) against the installed Pillow, byte for byte.
+
+The ground truth everywhere is ``np.asarray(Image.open(f).convert("RGB"))``; there is no tolerance.  Every file of the
+matrices must be decoded NATIVELY (return code TISE_JPEG_OK is asserted), so no comparison passes by leaving a case to Pillow."""
+import ctypes
+import io
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+from PIL import Image
+
+from . import _cases, _jpeg_cases as jc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def jf():
+    from tise_toolbox_amd import build, jpeg_feed
+    build.build_jpeg(force=False, verbose=False)
+    jpeg_feed.load_decoder()
+    return jpeg_feed
+
+
+def _assert_native_equal(jf, cases):
+    bad = []
+    for name, blob in cases:
+        rc, got = jf.decode_rgb8(blob)
+        if rc != jf.TISE_JPEG_OK:
+            bad.append((name, "rc", rc))
+        elif not np.array_equal(got, jc.pillow_rgb(blob)):
+            bad.append((name, "pixels", int(np.abs(got.astype(int) - jc.pillow_rgb(blob)).max())))
+    assert not bad, (len(bad), len(cases), bad[:10])
+
+
+def test_decode_equals_pillow_on_the_pillow_matrix(jf, tmp_path):
+    cases = jc.pillow_matrix(tmp_path)
+    assert len(cases) == 1024
+    _assert_native_equal(jf, cases)
+
+
+def test_decode_equals_pillow_on_hand_placed_extremes(jf):
+    cases = jc.writer_extremes()
+    assert len(cases) >= 20
+    _assert_native_equal(jf, cases)
+
+
+def test_tiny_chroma_planes_are_replicated_not_filtered(jf, tmp_path):
+    """libjpeg's triangle filter needs a chroma plane more than 2 samples wide; narrower ones are replicated."""
+    _assert_native_equal(jf, jc.tiny_chroma(tmp_path))
+
+
+def test_files_outside_the_subset_are_unsupported(jf, tmp_path):
+    img = _cases.smooth_images(1, 40, 56, seed=1)[0]
+    p = str(tmp_path / "u.jpg")
+    refused = [("progressive", jc.save_jpeg(img, p, quality=80, progressive=True)),
+               ("cmyk", jc.save_jpeg(img, p, quality=80, mode="CMYK"))]
+    b = io.BytesIO()
+    Image.fromarray(img).save(b, "PNG")
+    refused.append(("png", b.getvalue()))
+    refused.append(("beyond-guard", jc.beyond_guard()))
+    refused += jc.unsupported_layouts()
+    for name, blob in refused:
+        assert jf.probe(blob)[0] in (jf.TISE_JPEG_UNSUPPORTED, jf.TISE_JPEG_OK), name
+        assert jf.decode_rgb8(blob)[0] == jf.TISE_JPEG_UNSUPPORTED, name
+    for name in ("progressive", "cmyk", "png", "440", "411", "two-scans", "ids-RGB", "adobe-transform-0"):
+        assert jf.probe(dict(refused)[name])[0] == jf.TISE_JPEG_UNSUPPORTED, name
+    # the writer's files are real JPEGs: Pillow (which decodes whatever is refused here) reads the layouts it supports
+    for name in ("440", "411", "two-scans"):
+        assert jc.pillow_rgb(dict(refused)[name]).shape == (24, 40, 3)
+
+
+def _scan_start(blob):
+    return blob.index(b"\xff\xda") + 2 + int.from_bytes(blob[blob.index(b"\xff\xda") + 2:blob.index(b"\xff\xda") + 4], "big")
+
+
+def test_damaged_files_are_corrupt_or_equal_pillow_never_a_crash(jf, tmp_path):
+    img = np.random.default_rng(3).integers(0, 256, (72, 88, 3), dtype=np.uint8)
+    good = jc.save_jpeg(img, str(tmp_path / "g.jpg"), quality=85, subsampling=2, restart_marker_blocks=2)
+    assert jf.decode_rgb8(good)[0] == jf.TISE_JPEG_OK
+    damaged = [("cut-half", good[:len(good) // 2]), ("cut-2", good[:-2])]
+    rst = [m.start() for m in re.finditer(rb"\xff[\xd0-\xd7]", good)]
+    assert len(rst) > 4
+    damaged.append(("rst-removed", good[:rst[2]] + good[rst[2] + 2:]))
+    damaged.append(("rst-out-of-order", good[:rst[1] + 1] + bytes([good[rst[2] + 1]]) + good[rst[1] + 2:]))
+    s0 = _scan_start(good)
+    rng = np.random.default_rng(11)
+    for k in range(200):                                                     # flipped bits anywhere in the scan
+        pos = int(rng.integers(s0, len(good) - 2))
+        b = bytearray(good)
+        b[pos] ^= 1 << int(rng.integers(0, 8))
+        damaged.append((f"flip-{pos}", bytes(b)))
+    from tests import _jpeg_writer as jw
+    blocks = [np.zeros(s + (64,), dtype=np.int32) for s in jw.blocks_shape(32, 16, [(1, 1)])]
+    blocks[0][..., 0] = 5
+    damaged.append(("writer-rst-dropped", jw.write_jpeg(32, 16, blocks, [np.ones(64, dtype=np.int32)], restart=2, drop_rst=1)))
+    n_corrupt = 0
+    for name, blob in damaged:
+        rc, got = jf.decode_rgb8(blob)
+        assert rc in (jf.TISE_JPEG_OK, jf.TISE_JPEG_CORRUPT, jf.TISE_JPEG_UNSUPPORTED), (name, rc)
+        if rc == jf.TISE_JPEG_OK:                                            # the damage still decodes cleanly: then exactly as Pillow does
+            assert np.array_equal(got, jc.pillow_rgb(blob)), name
+        else:
+            n_corrupt += 1
+    for name in ("cut-half", "cut-2", "rst-removed", "rst-out-of-order", "writer-rst-dropped"):
+        assert jf.decode_rgb8(dict(damaged)[name])[0] == jf.TISE_JPEG_CORRUPT, name
+    assert n_corrupt > 20                                                     # bit flips that yield an invalid code or a lost marker
+
+
+def test_slot_round_trip_equals_the_one_call_decode(jf, tmp_path):
+    """tise_jpeg_entropy_decode + the host restatement of the kernel on the slot == tise_jpeg_decode_rgb8: pins the slot layout
+    (header fields, quantisation tables, plane order) the kernel consumes."""
+    lib = jf.load_decoder()
+    for name, blob in jc.writer_extremes()[:8] + jc.pillow_matrix(tmp_path)[::37]:
+        rc, w, h, lay = jf.probe(blob)
+        assert rc == 0, name
+        sb = int(lib.tise_jpeg_slot_bytes(w, h, lay))
+        slot = np.zeros(sb, dtype=np.uint8)
+        assert lib.tise_jpeg_entropy_decode(blob, len(blob), slot.ctypes.data, sb, None, None) == 0, name
+        hdr = slot[:64].view(np.int32)
+        hs, vs = (1, 1) if lay < 2 else ((2, 1) if lay == 2 else (2, 2))
+        mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+        nc = 1 if lay == 0 else 3
+        assert list(hdr[:6]) == [1, w, h, nc, hs, vs], name
+        assert list(hdr[6:12]) == ([mx * hs, mx, mx, my * vs, my, my] if nc == 3 else [mx, 0, 0, my, 0, 0]), name
+        assert hdr[12] == sb - 256 == 128 * (mx * hs * my * vs + (2 * mx * my if nc == 3 else 0)), name
+        out = np.empty((h, w, 3), dtype=np.uint8)
+        assert lib.tise_jpeg_reconstruct_slot_rgb8(slot.ctypes.data, sb, out.ctypes.data, out.nbytes) == 0, name
+        assert np.array_equal(out, jf.decode_rgb8(blob)[1]), name
+        # a slot one byte too small is refused with the size reported, nothing is written past it
+        gw, gh = ctypes.c_int(), ctypes.c_int()
+        assert lib.tise_jpeg_entropy_decode(blob, len(blob), slot.ctypes.data, sb - 1, ctypes.byref(gw), ctypes.byref(gh)) == jf.TISE_JPEG_SIZE
+        assert (gw.value, gh.value) == (w, h)
+        # a header that disagrees with itself is refused by the restatement
+        bad = slot.copy()
+        bad[:64].view(np.int32)[6] += 1
+        assert lib.tise_jpeg_reconstruct_slot_rgb8(bad.ctypes.data, sb, out.ctypes.data, out.nbytes) == jf.TISE_JPEG_CORRUPT
+
+
+def test_jpeg_library_exports_its_header(jf):
+    from tise_toolbox_amd import build
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tise_jpeg.h")).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(tise_jpeg_[a-z0-9_]+)\s*\(", text)))
+    assert declared == sorted(jf.DECODER_SIGNATURES) and len(declared) == 5
+    raw = ctypes.CDLL(build.JPEG_LIB)
+    for name in declared:
+        getattr(raw, name)
+    exported = subprocess.run(["nm", "-D", "--defined-only", build.JPEG_LIB], capture_output=True, text=True, check=True).stdout
+    assert sorted(set(re.findall(r"\b(tise_[a-z0-9_]+)\b", exported))) == declared
+    png = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "tise_png.h")).read(), flags=re.S)
+    assert "tise_jpeg" not in png
+
+
+def test_host_iteration_over_a_ragged_directory(jf, tmp_path):
+    """40 files of different sizes, three of them outside the native subset at known positions: order, pixels, drop-last
+    bookkeeping and the counters of JpegFeedLoader on a host device."""
+    rng = np.random.default_rng(9)
+    files, want = [], []
+    for i in range(40):
+        w, h = int(rng.integers(9, 70)), int(rng.integers(9, 70))
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8) if i % 2 else _cases.smooth_images(1, h, w, seed=i)[0]
+        path = str(tmp_path / f"img_{i:03d}.jpg")
+        kw = dict(quality=int(rng.choice([50, 75, 92])), subsampling=int(rng.choice([0, 1, 2])))
+        if i in (5, 17):
+            kw["progressive"] = True
+        if i == 30:
+            Image.fromarray(img).save(path, "PNG")                          # a PNG under a .jpg name
+        else:
+            jc.save_jpeg(img, path, **kw)
+        files.append(path)
+        want.append(np.asarray(Image.open(path).convert("RGB")))
+    loader = jf.JpegFeedLoader(files, 8, "cpu", workers=3)
+    assert len(loader) == 5
+    got = []
+    for item in loader:
+        assert isinstance(item, list) and len(item) == 8                    # ragged: what collate_u8 makes of such a batch
+        got += [t.numpy() for t in item]
+    assert len(got) == 40 and all(np.array_equal(g, w) for g, w in zip(got, want))
+    assert (loader.native, loader.pillow) == (37, 3)
+    # three threads: which refused file comes first is not fixed, but it is one of the three and says why
+    assert loader.first_pillow_reason in ("img_005.jpg: outside the native subset", "img_017.jpg: outside the native subset",
+                                          "img_030.jpg: outside the native subset")
+    one = jf.JpegFeedLoader(files[16:24], 8, "cpu", workers=1)               # one refused file in the batch: the reason is that file's
+    assert len(list(one)) == 1 and (one.native, one.pillow, one.first_pillow_reason) == (7, 1, "img_017.jpg: outside the native subset")
+    cut = str(tmp_path / "cut.jpg")
+    with open(files[0], "rb") as f, open(cut, "wb") as g:
+        g.write(f.read()[:-2])                                               # EOI missing: doubtful -> Pillow decides (and decodes it)
+    from PIL import ImageFile
+    old, ImageFile.LOAD_TRUNCATED_IMAGES = ImageFile.LOAD_TRUNCATED_IMAGES, True
+    try:
+        bad = jf.JpegFeedLoader([cut], 1, "cpu", workers=1)
+        assert len(list(bad)) == 1 and bad.first_pillow_reason == "cut.jpg: malformed or doubtful"
+    finally:
+        ImageFile.LOAD_TRUNCATED_IMAGES = old
+    short = jf.JpegFeedLoader(files[:39], 8, "cpu", workers=2)               # drop-last: 39 files -> 4 batches, 32 images
+    assert len(short) == 4 and sum(len(b) for b in short) == 32 and short.native + short.pillow == 32
+    same = jf.JpegFeedLoader([files[0]] * 6, 3, "cpu", workers=2)            # one size: a dense (B, H, W, 3) tensor
+    items = list(same)
+    assert len(items) == 2 and tuple(items[0].shape) == (3,) + want[0].shape and np.array_equal(items[1][2].numpy(), want[0])
+    assert len(jf.JpegFeedLoader(files[:2], 8, "cpu")) == 0 and list(jf.JpegFeedLoader(files[:2], 8, "cpu")) == []
+
+
+def test_u8_cache_of_a_jpeg_directory_holds_pillows_bytes(jf, tmp_path):
+    """img_data.build_u8_cache on a JPEG directory goes through tise_jpeg_decode_rgb8 (Pillow for the odd file): the cache holds
+    exactly Pillow's pixels in walk order; a directory of two sizes is refused as before."""
+    from tise_toolbox_amd import img_data
+    root = tmp_path / "set"
+    root.mkdir()
+    rng = np.random.default_rng(4)
+    for i in range(23):
+        img = rng.integers(0, 256, (40, 56, 3), dtype=np.uint8) if i % 3 else _cases.smooth_images(1, 40, 56, seed=i)[0]
+        jc.save_jpeg(img, str(root / f"c_{i:02d}.jpg"), quality=80, subsampling=int(rng.choice([0, 1, 2])), progressive=(i == 7))
+    files = img_data.get_filenames(str(root))
+    assert len(files) == 23 and jf.probe_file(files[0]) or files[0].endswith("c_07.jpg")
+    if not jf.probe_file(files[0]):                                          # the walk happened to start with the progressive file
+        files = files[1:] + files[:1]
+    cache = str(tmp_path / "cache.npy")
+    img_data.build_u8_cache(files, cache, num_workers=3, batch_size=5)
+    arr = np.load(cache, mmap_mode="r")
+    assert arr.shape == (23, 40, 56, 3)
+    for i, f in enumerate(files):
+        assert np.array_equal(arr[i], np.asarray(Image.open(f).convert("RGB"))), f
+    assert img_data.u8_cache_is_current(cache, files)
+    jc.save_jpeg(rng.integers(0, 256, (41, 56, 3), dtype=np.uint8), str(root / "z_odd.jpg"), quality=80)
+    with pytest.raises(ValueError, match="one size"):
+        img_data.build_u8_cache(files + [str(root / "z_odd.jpg")], str(tmp_path / "cache2.npy"), num_workers=2, batch_size=5)
+    assert not os.path.exists(str(tmp_path / "cache2.npy"))
+
+
+def test_host_decoder_under_sanitizers(jf, tmp_path):
+    """The decoder built with -fsanitize=address,undefined (host code, CPU build) over the extremes, the refusals and damaged
+    files: no report, same return codes."""
+    src = os.path.join(ROOT, "tise_toolbox_amd", "csrc", "jpeg_decode.c")
+    harness = tmp_path / "h.c"
+    harness.write_text(
+        '#include "tise_jpeg.h"\n#include <stdio.h>\n#include <stdlib.h>\n'
+        "int main(int argc, char** argv) { for (int i = 1; i < argc; ++i) { FILE* f = fopen(argv[i], \"rb\"); if (!f) return 3;\n"
+        "  fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET); unsigned char* b = malloc(n ? n : 1);\n"
+        "  if (fread(b, 1, n, f) != (size_t)n) return 3; fclose(f); int w = 0, h = 0, lay = 0;\n"
+        "  int rc = tise_jpeg_probe(b, n, &w, &h, &lay); int rd = -1;\n"
+        "  if (rc == 0) { unsigned char* d = malloc((size_t)w * h * 3); rd = tise_jpeg_decode_rgb8(b, n, d, (size_t)w * h * 3, 0, 0); free(d); }\n"
+        "  printf(\"%d %d\\n\", rc, rd); free(b); } return 0; }\n")
+    exe = str(tmp_path / "h")
+    cc = os.environ.get("CC", "gcc")
+    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fwrapv"]
+    empty = tmp_path / "empty.c"
+    empty.write_text("int main(void) { return 0; }\n")
+    # is there a sanitizer runtime at all?  Asked with a program that has nothing to do with the product, so that a compile
+    # error in jpeg_decode.c can never be read as a skip
+    if subprocess.run([cc] + san + ["-o", str(tmp_path / "empty"), str(empty)], capture_output=True).returncode != 0:
+        pytest.skip("this compiler has no sanitizer runtime")
+    r = subprocess.run([cc] + san + ["-I", os.path.join(ROOT, "include"), "-o", exe, str(harness), src], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    img = np.random.default_rng(3).integers(0, 256, (40, 56, 3), dtype=np.uint8)
+    good = jc.save_jpeg(img, str(tmp_path / "g.jpg"), quality=85, subsampling=2, restart_marker_blocks=2)
+    blobs = [b for _, b in jc.writer_extremes()[:10] + jc.unsupported_layouts()] + [jc.beyond_guard(), good, good[:len(good) // 2], good[:-2], b"", b"\xff\xd8"]
+    rng = np.random.default_rng(1)
+    for _ in range(150):
+        b = bytearray(good)
+        for _ in range(int(rng.integers(1, 4))):
+            b[int(rng.integers(2, len(b)))] = int(rng.integers(0, 256))
+        blobs.append(bytes(b))
+    paths = []
+    for i, b in enumerate(blobs):
+        p = tmp_path / f"s{i}.bin"
+        p.write_bytes(b)
+        paths.append(str(p))
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe] + paths, capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.split()
+    assert len(lines) == 2 * len(blobs)
+    for b, rd in zip(blobs, lines[1::2]):
+        rc = jf.decode_rgb8(b)[0] if jf.probe(b)[0] == 0 else -1
+        assert int(rd) == rc

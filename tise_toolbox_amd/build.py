@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtise_hip.so")
-SOURCES = ["capi.hip", "stats.hip", "resize.hip", "is_score.hip", "frechet.hip", "trunk_ops.hip", "conv_split.hip", "conv_pipe.hip", "retrieval.hip", "clip_ops.hip", "png_unfilter.hip", "calibrate.hip"]
+SOURCES = ["capi.hip", "stats.hip", "resize.hip", "is_score.hip", "frechet.hip", "trunk_ops.hip", "conv_split.hip", "conv_pipe.hip", "retrieval.hip", "clip_ops.hip", "png_unfilter.hip", "calibrate.hip", "jpeg_idct.hip"]
 HEADERS = ["common.h", "gemm_tile.h", "conv_epilogue.h", os.path.join("..", "..", "include", "tise_hip.h")]
 
 
@@ -56,7 +56,25 @@ def build_png(force=False, verbose=True):
     return PNG_LIB
 
 
-OBJ_DIR = os.path.join(CSRC, "_obj")       # per-source objects (git-ignored: *.o): a change to one kernel file recompiles that file only
+JPEG_LIB = os.path.join(HERE, "libtise_jpeg.so")
+JPEG_SRC = os.path.join(CSRC, "jpeg_decode.c")
+JPEG_HDR = os.path.join(HERE, "..", "include", "tise_jpeg.h")
+
+
+def build_jpeg(force=False, verbose=True):
+    """gcc over csrc/jpeg_decode.c -> tise_toolbox_amd/libtise_jpeg.so: the host half of the JPEG feed (marker parsing,
+    Huffman decoding, and the scalar restatement of csrc/jpeg_idct.hip; plain C, no HIP, no libjpeg)."""
+    cc = os.environ.get("CC", "gcc")
+    newest = max(os.path.getmtime(JPEG_SRC), os.path.getmtime(JPEG_HDR))
+    if force or not os.path.exists(JPEG_LIB) or os.path.getmtime(JPEG_LIB) < newest:
+        cmd = [cc, "-O3", "-fwrapv", "-fPIC", "-shared", "-o", JPEG_LIB, JPEG_SRC]
+        if verbose:
+            print("[tise build]", " ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True, cwd=CSRC)
+    return JPEG_LIB
+
+
+OBJ_DIR = os.path.join(CSRC, "_obj")      # per-source objects (git-ignored: *.o): a change to one kernel file recompiles that file only
 
 
 def _deps(src):
@@ -75,6 +93,7 @@ def build(force=False, verbose=True, jobs=None):
     newer), then one link."""
     from concurrent.futures import ThreadPoolExecutor
     build_png(force, verbose)
+    build_jpeg(force, verbose)
     if not force and not needs_build():
         return LIB
     os.makedirs(OBJ_DIR, exist_ok=True)

@@ -112,6 +112,11 @@ def _build_parser():
                         help="ring: decode workers write into one shared page-locked ring the parent copies from (png_ring.py); "
                              "dataloader: torch DataLoader workers + collate + pin_memory (round 1-4 path, also the fallback "
                              "for directories whose images differ in size)")
+    parser.add_argument("--jpeg-feed", type=str, default=None, choices=["native", "pillow"],
+                        help="native: a directory (shard) whose first file is a JPEG of the native subset is Huffman-decoded by threads "
+                             "of this process and reconstructed on the GPU (jpeg_feed.py; images may differ in size); pillow: such "
+                             "directories take the path of every other file (Pillow in the --png-feed workers).  Default: native for "
+                             "directories whose images differ in size, pillow for directories of one size (the faster one of each, DESIGN.md)")
     return parser
 
 
@@ -287,8 +292,18 @@ U8_CACHE_NAME = ".tise_u8_cache.npy"
 
 
 _PNG_FEED = {"mode": "ring"}        # --png-feed
+_JPEG_FEED = {"mode": None}         # --jpeg-feed (None: native for ragged JPEG directories, pillow for directories of one size)
 _RING_PREFETCH = {}                  # directory -> PngRingLoader whose workers are already decoding (started before the model was built)
 _RING_LOCK = __import__("threading").Lock()   # the second directory's prefetch is started from the first loader's feeder thread
+
+
+def _native_jpeg_shard(shard):
+    """--jpeg-feed native applies: the shard's first file probes as a JPEG of the native subset (and --png-feed was not
+    turned to the DataLoader)."""
+    if _PNG_FEED["mode"] != "ring" or not shard:
+        return False
+    from . import jpeg_feed
+    return jpeg_feed.use_native(shard, _JPEG_FEED["mode"])
 
 
 def _num_workers(num_workers, world=1):
@@ -313,7 +328,7 @@ def prefetch_png_ring(path, batch_size, num_workers=0):
         if path in _RING_PREFETCH:
             return _RING_PREFETCH[path]
         shard, world = _shard_of_path(path, batch_size)
-        if not shard:
+        if not shard or _native_jpeg_shard(shard):
             return None
         group = device_batch_images(batch_size) // batch_size
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_initialized() else torch.device("cuda", tdist.env_world()[2])
@@ -376,6 +391,21 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         return out
     shard, _ = tdist.shard_files(files, batch_size, rank, world)       # drop_last=True (:215-217), whole batches
     num_workers = _num_workers(num_workers, world)
+    if _native_jpeg_shard(shard):
+        # decode threads -> page-locked coefficient arenas -> side-stream H2D -> IDCT / upsampling / colour on the GPU
+        # (jpeg_feed.py).  Items are loader batches as the DataLoader's collate_u8 makes them (dense or ragged), so the
+        # statistics below are the DataLoader path's to the last bit; images may differ in size, under torchrun as well
+        from . import jpeg_feed
+        loader = jpeg_feed.JpegFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers)
+        t0 = time.perf_counter()
+        try:
+            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda)
+        finally:
+            loader.close()
+        if tdist.is_main():
+            print(loader.feed_line(time.perf_counter() - t0), file=sys.stderr)
+        _compute_statistics_of_path.last_jpeg_loader = loader
+        return out
     if _PNG_FEED["mode"] == "ring":
         # decode workers -> shared page-locked ring -> side-stream H2D (png_ring.py).  A directory with images of different
         # sizes: one process falls back to the DataLoader path below; under torchrun the rank that meets the odd file raises
@@ -751,6 +781,7 @@ def main(argv=None):
     if world == 1:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)        # reference: CUDA_VISIBLE_DEVICES = args.gpu (:243)
     _PNG_FEED["mode"] = args.png_feed
+    _JPEG_FEED["mode"] = args.jpeg_feed
     if args.conv is not None:
         os.environ["TISE_CONV"] = "miopen" if args.conv == "exact" else "split"
     kind = tweights.inception_kind(args.network, args.label == "O-FID" and args.num_classes == 80)

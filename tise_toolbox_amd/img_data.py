@@ -95,12 +95,23 @@ def build_u8_cache(files, out_path, num_workers=8, batch_size=256, root=None):
     arr = np.lib.format.open_memmap(out_path, mode="w+", dtype=np.uint8, shape=(len(files), h, w, 3))
     # decode processes write into a shared ring, this process only copies finished chunks into the file (png_ring.py:
     # no pickling queues; round 4 built the cache through a DataLoader at ~4 k images/s)
-    from . import png_ring
-    ring = png_ring.PngRingLoader(files, 1, "cpu", workers=max(1, num_workers), start=True)
+    from . import jpeg_feed, png_ring
+    if os.path.exists(jpeg_feed.JPEG_LIB_PATH) and jpeg_feed.probe_file(files[0]):
+        # a JPEG directory: the native host decode (tise_jpeg_decode_rgb8) in threads of this process, Pillow for the odd file
+        def chunks():
+            pos = 0
+            for item in jpeg_feed.JpegFeedLoader(files, min(batch_size, len(files)), "cpu", workers=max(1, num_workers), drop_last=False).iter_host():
+                if isinstance(item, list) or tuple(item.shape[1:]) != (h, w, 3):
+                    raise png_ring.RaggedImages(f"images of different sizes near file {pos}")
+                yield pos, item.numpy()
+                pos += item.shape[0]
+        source = chunks()
+    else:
+        source = png_ring.PngRingLoader(files, 1, "cpu", workers=max(1, num_workers), start=True).iter_host()
     i = 0
     try:
         try:
-            for lo, view in ring.iter_host():
+            for lo, view in source:
                 arr[lo:lo + view.shape[0]] = view
                 i = lo + view.shape[0]
         except png_ring.RaggedImages as e:

@@ -19,6 +19,7 @@ softmax, split rule, KL, exp, mean/std -- is the reference's, evaluated on devic
 """
 import os
 import sys
+import time
 import warnings
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
 
@@ -35,7 +36,7 @@ warnings.filterwarnings("ignore")
 _ENGINE = None
 _CONFIG = {"weights": None, "num_classes": None, "seed": 0, "temperature": T_COCO, "batch_size": 50,
            "rule": "coco", "drop_first_class": False, "num_workers": 0, "fc_bias": "auto", "png_feed": "ring",
-           "network": "torchvision"}
+           "jpeg_feed": None, "network": "torchvision"}
 
 
 def configure(**kw):
@@ -127,6 +128,30 @@ def feed_images(eng, images, lo, hi, begin):
         return coalesce_batches(loader, eng.device, device_batch_images(bs))
 
     if _CONFIG.get("png_feed", "ring") == "ring" and hi > lo:
+        from . import jpeg_feed
+        if jpeg_feed.use_native(images[lo:hi], _CONFIG.get("jpeg_feed")):
+            # JPEG files (the CUB photographs, COCO val2014): Huffman decoding in threads of this process, the rest on the GPU
+            # (jpeg_feed.py); every image is used (no drop-last), images may differ in size
+            # items = the device batches the PNG ring would deliver for files of the first one's size (engine.item_schedule over
+            # loader batches of 1, clamped to STAGING_BYTES_CAP of pixels): the same reduction order, the same IS* to the last bit
+            from .engine import STAGING_BYTES_CAP, item_schedule
+            with open(images[lo], "rb") as fh_:
+                _, w0, h0, _ = jpeg_feed.probe(fh_.read())
+            sb = jpeg_feed.pick_slot_bytes(images[lo:hi])                     # the largest of the first files, not the first one
+            rows = item_schedule(hi - lo, 1, min(device_batch_images(1), max(1, STAGING_BYTES_CAP // max(1, h0 * w0 * 3)),
+                                                   max(1, (1 << 29) // sb)))                             # ... and an arena of at most 512 MiB
+            loader = jpeg_feed.JpegFeedLoader(images[lo:hi], 1, eng.device, workers=workers, drop_last=False, item_rows=rows,
+                                              slot_bytes=sb)
+            t0 = time.perf_counter()
+            try:
+                run(loader)
+            finally:
+                loader.close()
+            if tdist.is_main():
+                print(loader.feed_line(time.perf_counter() - t0), file=sys.stderr)
+            feed_images.last_jpeg_loader = loader
+            return
+    if _CONFIG.get("png_feed", "ring") == "ring" and hi > lo:
         # decode processes -> shared page-locked ring -> side-stream H2D (png_ring.py); every image is used (no drop-last:
         # inception_score_star_coco.py:44-51 feeds the images one by one), so the ring's loader batch is 1
         ring = png_ring.PngRingLoader(images[lo:hi], 1, eng.device, group=device_batch_images(1), workers=workers)
@@ -191,6 +216,10 @@ def _build_parser():
                              "TF-slim InceptionV3 of the reference's IS* for CUB birds (a TensorFlow checkpoint: 51 classes, "
                              "exclude-padding average pools, no BatchNorm gamma, input v / 127.5 - 1)")
     parser.add_argument("--seed", type=int, default=0, help="seed of the --synthetic-weights parameters")
+    parser.add_argument("--jpeg-feed", type=str, default=None, choices=["native", "pillow"],
+                        help="native: JPEG files of the native subset are Huffman-decoded by threads of this process and reconstructed "
+                             "on the GPU (jpeg_feed.py); pillow: every file through Pillow, as PNG directories' odd files are.  Default: "
+                             "native for image sets whose files differ in size, pillow for sets of one size")
     parser.add_argument("--label", type=str, default="IS", choices=["IS", "O-IS", "bird"])
     parser.add_argument("--fc-bias", type=str, default="auto", choices=["auto", "on", "off"],
                         help="classifier bias in the logits. auto follows the reference script of --rule: coco forms its logits "
@@ -212,7 +241,7 @@ def main(argv=None):
                                   tweights.inception_kind(args.network, args.label == "O-IS" and args.num_classes == 80))
     configure(weights=wpath, num_classes=args.num_classes, seed=args.seed, temperature=args.temperature,
               batch_size=args.batch_size, rule=args.rule, drop_first_class=args.drop_first_class, fc_bias=args.fc_bias,
-              network=args.network)
+              network=args.network, jpeg_feed=args.jpeg_feed)
     images = load_data(args.image_folder)
     print(".......")
     from .engine import run_with_exact_fallback

@@ -100,6 +100,10 @@ def _build_parser():
     parser.add_argument("--num-workers", type=int, default=0, help="decode processes (0: automatic)")
     parser.add_argument("--png-feed", type=str, default="ring", choices=["ring", "loader"],
                         help="ring: native decode processes + shared pinned ring; loader: the DataLoader path")
+    parser.add_argument("--jpeg-feed", type=str, default=None, choices=["native", "pillow"],
+                        help="native: JPEG files of the native subset (the CUB photographs) are Huffman-decoded by threads of this "
+                             "process and reconstructed on the GPU (jpeg_feed.py); pillow: every file through Pillow.  Default: native "
+                             "for image sets whose files differ in size, pillow for sets of one size")
     return parser
 
 
@@ -114,7 +118,7 @@ def main(argv=None):
                                   args.synthetic_weights, "slim")
     isc.configure(weights=wpath, num_classes=args.num_classes + 1, seed=args.seed, temperature=args.temperature,
                   rule="bird", drop_first_class=True, fc_bias="auto", network="slim", num_workers=args.num_workers,
-                  png_feed=args.png_feed)
+                  png_feed=args.png_feed, jpeg_feed=args.jpeg_feed)
     print(args.image_folder)
     files = isc.img_data.get_filenames(args.image_folder)
     if not files:
