@@ -97,14 +97,34 @@ def resize_u8(img, out_h, out_w, filter="bilinear"):
 
     Pillow runs the horizontal pass first (skipped when the width is unchanged),
     stores uint8, then the vertical pass (skipped when the height is unchanged).
+
+    One exception, in ``Image.resize`` itself (PIL/Image.py, read from Pillow 12.2.0):
+
+        if self.size[1] > self.size[0] * 100 and size[1] < self.size[1]:
+            im = self.im.resize((self.size[0], size[1]), resample, (0, box[1], self.size[0], box[3]))
+            im = im.resize(size, resample, (box[0], 0, box[2], size[1]))
+
+    A source more than 100 times taller than wide whose height shrinks is resized to (w, out_h) first and to
+    (out_w, out_h) second: the VERTICAL pass runs first.  ``pillow_vertical_first`` states the rule; the tests hold this
+    function to the installed Pillow on both sides of it.  The reference's Pillow 8.3.2 was not available to compare,
+    so whether that version has the rule is not known here; the contract is "equal to the installed Pillow", which is
+    also what the product's host roads (DataLoader, clip_model.preprocess) call.
     """
     img = np.ascontiguousarray(img)
     h, w = img.shape[:2]
+    if pillow_vertical_first(h, w, out_h):
+        img = _resample_axis0(img, out_h, filter)
+        h = out_h
     if w != out_w:
         img = np.swapaxes(_resample_axis0(np.swapaxes(img, 0, 1), out_w, filter), 0, 1)
     if h != out_h:
         img = _resample_axis0(img, out_h, filter)
     return np.ascontiguousarray(img)
+
+
+def pillow_vertical_first(h, w, out_h):
+    """Image.resize's rule for running the vertical pass before the horizontal one (see resize_u8)."""
+    return h > 100 * w and out_h < h
 
 
 def resize_bilinear_u8(img, out_h, out_w):

@@ -51,53 +51,7 @@ def test_gemm_asymmetric_identity(dev):
     np.testing.assert_array_equal(c, b)
 
 
-# ------------------------------------------------------------------------------------------- resize
-def test_resize_golden_bit_exact(dev, golden_dir):
-    from tise_toolbox_amd import device
-    g = np.load(os.path.join(golden_dir, "pil_resize_299.npz"))
-    names = [k[3:] for k in g.files if k.startswith("in_")]
-    lut = device.make_lut(True)
-    for k in names:
-        src = torch.as_tensor(g["in_" + k], device=dev).unsqueeze(0)
-        for cl in (True, False):
-            out, u8 = device.resize_bilinear_u8(src, (299, 299), lut, channels_last=cl, return_u8=True)
-            np.testing.assert_array_equal(u8[0].cpu().numpy(), g["out_" + k], err_msg=f"{k} cl={cl}")
-            # fused ToTensor + inception.py:120-124 affine: bit-exact against the numpy restatement
-            want = resize_oracle.normalize_input(resize_oracle.to_tensor(g["out_" + k]))
-            got = out[0].cpu().numpy()
-            assert got.shape == (3, 299, 299)
-            np.testing.assert_array_equal(got, want, err_msg=f"{k} cl={cl} float")
-            assert out.is_contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format)
-
-
-@pytest.mark.parametrize("h,w", [(256, 256), (64, 48), (299, 299), (300, 299), (299, 301), (517, 31), (1024, 768), (7, 5)])
-def test_resize_random_sizes_vs_oracle(dev, h, w):
-    from tise_toolbox_amd import device
-    rng = np.random.default_rng(h * 7 + w)
-    n = 3
-    imgs = rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)
-    out, u8 = device.resize_bilinear_u8(torch.as_tensor(imgs, device=dev), (299, 299), device.make_lut(False),
-                                        channels_last=True, return_u8=True)
-    only = device.resize_u8_only(torch.as_tensor(imgs, device=dev), (299, 299))     # the product path: uint8 out only (4 bytes per lane)
-    for i in range(n):
-        want = resize_oracle.resize_bilinear_u8(imgs[i], 299, 299)
-        np.testing.assert_array_equal(u8[i].cpu().numpy(), want)
-        np.testing.assert_array_equal(only[i].cpu().numpy(), want)
-        np.testing.assert_array_equal(out[i].cpu().numpy(), resize_oracle.to_tensor(want))
-    # a destination that is not a multiple of four bytes wide and not 299: the dword stores' row tails
-    for (oh, ow) in ((61, 37), (300, 298)):
-        got = device.resize_u8_only(torch.as_tensor(imgs[:1], device=dev), (oh, ow))
-        np.testing.assert_array_equal(got[0].cpu().numpy(), resize_oracle.resize_bilinear_u8(imgs[0], oh, ow))
-
-
-def test_resize_batch_and_empty(dev):
-    from tise_toolbox_amd import device
-    imgs = _cases.smooth_images(5, 256, 256, seed=1)
-    out, u8 = device.resize_bilinear_u8(torch.as_tensor(imgs, device=dev), return_u8=True)
-    for i in range(5):
-        np.testing.assert_array_equal(u8[i].cpu().numpy(), resize_oracle.resize_bilinear_u8(imgs[i], 299, 299))
-    empty = device.resize_bilinear_u8(torch.empty((0, 256, 256, 3), dtype=torch.uint8, device=dev))
-    assert tuple(empty.shape) == (0, 3, 299, 299)
+# (the resize kernel has a file of its own: tests/test_gpu_resize.py)
 
 
 # ------------------------------------------------------------------------------------------- statistics

@@ -377,6 +377,29 @@ def test_two_ranks_with_an_empty_shard(setup, tmp_path):
     assert all(rc != 0 and "ZeroDivisionError" in o for rc, o in res), res
 
 
+def test_thin_tall_crops_enter_the_trunk_as_pillow_resizes_them(setup, monkeypatch):
+    """A 480 x 4 and a 1024 x 8 object crop are inside Image.resize's vertical-pass-first rule (h > 100 w, the height
+    shrinks): the uint8 network input that engine.features_from_u8_list hands to the trunk equals Pillow's resize of the
+    same pixels byte for byte, as the DataLoader road's does by construction (a 480 x 5 crop, outside the rule, rides along)."""
+    from PIL import Image
+    eng = setup["eng"]
+    rng = np.random.default_rng(480)
+    crops = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for (h, w) in ((480, 4), (1024, 8), (480, 5))]
+    seen = []
+    trunk_u8, trunk = eng._trunk_u8, eng._trunk
+    if eng._u8_stem:
+        monkeypatch.setattr(eng, "_trunk_u8", lambda u8: (seen.append(u8.cpu().numpy()), trunk_u8(u8))[1])
+    else:
+        lut = eng.lut_dev.view(3, 256).cpu().numpy()
+        monkeypatch.setattr(eng, "_trunk", lambda x, prenormalized: (seen.append(x.permute(0, 2, 3, 1).cpu().numpy()), trunk(x, prenormalized))[1])
+    feats, _ = eng.features_from_u8_list([torch.from_numpy(c) for c in crops])
+    assert len(seen) == 1 and tuple(feats.shape) == (3, 2048) and bool(torch.isfinite(feats).all())
+    want = np.stack([np.asarray(Image.fromarray(c).resize((299, 299), Image.BILINEAR)) for c in crops])
+    if not eng._u8_stem:
+        want = np.stack([lut[c][want[..., c]] for c in range(3)], axis=-1)
+    np.testing.assert_array_equal(seen[0], want)
+
+
 def test_ragged_crops_one_trunk_pass_and_per_class_fid(setup, tmp_path):
     """ADVICE r1 + section 8 f2: crops of different sizes are resized into ONE batch (a single trunk pass), results
     equal the per-image path bit for bit; --per-class groups crops by the {class} token (crop_object.py:45) and

@@ -140,6 +140,28 @@ def make_lut(normalize_input=True, scale_pm1=False, network="torchvision"):
 
 
 _IDENTITY_LUT = np.ascontiguousarray(np.tile(np.arange(256, dtype=np.float32) / np.float32(255.0), (3, 1)))
+_FILTERS = {"bilinear": 0, "bicubic": 1}
+
+
+def pillow_vertical_first(h, w, oh):
+    """Pillow's ``Image.resize`` (PIL/Image.py, read from 12.2.0) resizes a source more than 100 times taller than wide whose
+    height shrinks to (w, oh) first and to (ow, oh) second: ``if self.size[1] > self.size[0] * 100 and size[1] < self.size[1]``.
+    Everywhere else the horizontal pass runs first, which is the order the kernel states.  The uint8 intermediate makes the
+    order visible (about one byte in five differs by 1 for 480 x 4 -> 299 x 299), and the host roads (DataLoader,
+    clip_model.preprocess) call Pillow for the same pixels, so the device road follows the rule: _vertical_pass_first."""
+    return h > 100 * w and oh < h
+
+
+def _vertical_pass_first(src_u8, oh, filter):
+    """Inside Pillow's rule: (N,h,w,3) -> (N,oh,w,3) uint8, a launch of its own whose horizontal pass is the identity; the
+    caller's launch then sees h == oh and runs the horizontal pass only.  Outside the rule: ``src_u8`` itself."""
+    n, h, w, _ = src_u8.shape
+    if not pillow_vertical_first(h, w, oh):
+        return src_u8
+    mid = torch.empty((n, oh, w, 3), dtype=torch.uint8, device=src_u8.device)
+    _lib.call("tise_resize_u8", _ptr(src_u8), n, h, w, None, oh, w, 1,
+              _IDENTITY_LUT.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _ptr(mid), _FILTERS[filter], _stream())
+    return mid
 
 
 def resize_bilinear_u8(src_u8, out_hw=(299, 299), lut=None, channels_last=True, return_u8=False):
@@ -152,9 +174,9 @@ def resize_bilinear_u8(src_u8, out_hw=(299, 299), lut=None, channels_last=True, 
     _require_cuda(src_u8)
     if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3:
         raise ValueError("src_u8 must be (N,H,W,3) uint8")
-    src_u8 = src_u8.contiguous()
-    n, h, w, _ = src_u8.shape
     oh, ow = out_hw
+    src_u8 = _vertical_pass_first(src_u8.contiguous(), oh, "bilinear")
+    n, h, w, _ = src_u8.shape
     if lut is None:
         lut = make_lut(True)
     lut = np.ascontiguousarray(lut, dtype=np.float32)
@@ -177,9 +199,9 @@ def resize_u8_lut(src_u8, out_hw, lut, filter="bicubic", channels_last=False, re
     _require_cuda(src_u8)
     if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3:
         raise ValueError("src_u8 must be (N,H,W,3) uint8")
-    src_u8 = src_u8.contiguous()
-    n, h, w, _ = src_u8.shape
     oh, ow = out_hw
+    src_u8 = _vertical_pass_first(src_u8.contiguous(), oh, filter)
+    n, h, w, _ = src_u8.shape
     lut = np.ascontiguousarray(lut, dtype=np.float32)
     if channels_last:
         store = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=src_u8.device)
@@ -190,7 +212,7 @@ def resize_u8_lut(src_u8, out_hw, lut, filter="bicubic", channels_last=False, re
     u8 = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=src_u8.device) if return_u8 else None
     _lib.call("tise_resize_u8", _ptr(src_u8), n, h, w, _ptr(store), oh, ow, 1 if channels_last else 0,
               lut.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), _ptr(u8) if u8 is not None else None,
-              {"bilinear": 0, "bicubic": 1}[filter], _stream())
+              _FILTERS[filter], _stream())
     return (out, u8) if return_u8 else out
 
 
@@ -201,9 +223,9 @@ def resize_u8_only(src_u8, out_hw=(299, 299), out=None):
     _require_cuda(src_u8)
     if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3:
         raise ValueError("src_u8 must be (N,H,W,3) uint8")
-    src_u8 = src_u8.contiguous()
-    n, h, w, _ = src_u8.shape
     oh, ow = out_hw
+    src_u8 = _vertical_pass_first(src_u8.contiguous(), oh, "bilinear")
+    n, h, w, _ = src_u8.shape
     if out is None:
         u8 = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=src_u8.device)
     else:
