@@ -9,7 +9,8 @@
  *
  * Subset: 8-bit Huffman SOF0 / SOF1, ONE scan holding all components; 1 component (1x1) or 3 components YCbCr (JFIF
  * marker, or Adobe marker with transform 1, or neither marker and component ids 1, 2, 3) with luma sampling 1x1, 2x1
- * or 2x2 and chroma 1x1; 8-bit quantisation tables; every |coefficient * quantiser| <= 16383.
+ * or 2x2 and chroma 1x1; 8-bit quantisation tables; every |coefficient * quantiser| <= 16383; width and height at most
+ * 65500 (TISE_JPEG_MAX_DIMENSION: libjpeg refuses a larger file, Pillow raises OSError for it, and so must the feed).
  */
 #ifndef TISE_JPEG_H
 #define TISE_JPEG_H
@@ -45,6 +46,9 @@ extern "C" {
  * one after the other, block rows padded to whole MCUs (component c: blocks-per-column x blocks-per-row blocks, row-major). */
 #define TISE_JPEG_SLOT_HDR 256
 #define TISE_JPEG_MAX_PRODUCT 16383
+/* libjpeg's JPEG_MAX_DIMENSION: probe / entropy_decode / decode_rgb8 answer TISE_JPEG_UNSUPPORTED above it.  (Mode-0 slots carry
+ * Pillow's pixels of any file Pillow opened; tise_jpeg_reconstruct_rgb8 keeps its own bound of 65535, which is about indexing.) */
+#define TISE_JPEG_MAX_DIMENSION 65500
 
 /* slot bytes (header + coefficients, a multiple of 16) of a w x h image of `layout` */
 size_t tise_jpeg_slot_bytes(int w, int h, int layout);

@@ -73,6 +73,93 @@ def test_files_outside_the_subset_are_unsupported(jf, tmp_path):
         assert jc.pillow_rgb(dict(refused)[name]).shape == (24, 40, 3)
 
 
+def test_decode_equals_pillow_with_a_table_of_its_own_for_every_component(jf):
+    """Pillow's files share one quantisation table between Cb and Cr, the other writer cases one between all three: here every
+    component has its own.  The case is sensitive: Pillow's pixels change when Cr is given Cb's table."""
+    cases = jc.distinct_tables()
+    assert len(cases) == 6
+    for (name, blob), (_, swapped) in zip(cases, jc.distinct_tables_cr_takes_cb()):
+        assert blob != swapped and not np.array_equal(jc.pillow_rgb(blob), jc.pillow_rgb(swapped)), name
+    _assert_native_equal(jf, cases)
+
+
+def test_decode_equals_pillow_on_dense_blocks_near_the_guard(jf):
+    """Many products near TISE_JPEG_MAX_PRODUCT in one block: the 16-bit wrap / saturation of the column pass and a row pass
+    that leaves 32 bits, in combination (the extremes place one such term per block)."""
+    cases = jc.dense_out_of_range()
+    assert len(cases) == 4 * (len(jc.DENSE_BOUNDS) * 5 + 2)
+    _assert_native_equal(jf, cases)
+
+
+def test_decode_equals_pillow_at_libjpegs_largest_dimension(jf):
+    cases = jc.long_edges()
+    assert [jf.probe(b)[1:3] for _, b in cases] == [(w, h) for w, h, _ in jc.LONG_EDGES]
+    _assert_native_equal(jf, cases)
+
+
+def test_dimensions_beyond_libjpegs_limit_are_unsupported(jf):
+    """65500 is libjpeg's JPEG_MAX_DIMENSION: Pillow raises for a larger file, so the reference job fails on it.  The native
+    decoder must hand such a file to Pillow (which raises), not produce pixels."""
+    lib = jf.load_decoder()
+    cases = jc.beyond_libjpeg_dimension()
+    assert len(cases) == 3
+    for name, blob in cases:
+        with pytest.raises(OSError):
+            jc.pillow_rgb(blob)
+        assert jf.probe(blob)[0] == jf.TISE_JPEG_UNSUPPORTED, name
+        slot = np.zeros(1 << 21, dtype=np.uint8)
+        assert lib.tise_jpeg_entropy_decode(blob, len(blob), slot.ctypes.data, slot.nbytes, None, None) == jf.TISE_JPEG_UNSUPPORTED, name
+        out = np.zeros(65535 * 3, dtype=np.uint8)
+        assert lib.tise_jpeg_decode_rgb8(blob, len(blob), out.ctypes.data, out.nbytes, None, None) == jf.TISE_JPEG_UNSUPPORTED, name
+        assert not slot.any() and not out.any(), name
+
+
+def test_loader_raises_what_pillow_raises_for_a_file_beyond_libjpegs_limit(jf, tmp_path):
+    """The reference's Dataset.__getitem__ raises on such a file; so does the loader (the decode thread's exception, as it is)."""
+    img = _cases.smooth_images(1, 24, 32, seed=2)[0]
+    files = []
+    for i in range(4):
+        path = str(tmp_path / f"f_{i}.jpg")
+        jc.save_jpeg(img, path, quality=80)
+        files.append(path)
+    with open(files[2], "wb") as f:
+        f.write(jc.beyond_libjpeg_dimension()[0][1])
+    with pytest.raises(OSError) as pillow:
+        Image.open(files[2]).convert("RGB")
+    with pytest.raises(OSError) as ours:
+        list(jf.JpegFeedLoader(files, 2, "cpu", workers=2))
+    assert type(ours.value) is type(pillow.value) and str(ours.value) == str(pillow.value)
+    with pytest.raises(OSError):
+        jf.decode_file_host(files[2])
+
+
+def test_every_branch_of_the_two_kernels_is_reached_by_the_gpu_launches(jf, tmp_path):
+    """The branch census (tests/_jpeg_cases.py: branch_census) of the launches of tests/test_gpu_jpeg.py: no row may be empty
+    for the matrix launch, so a change to the case lists cannot silently lose a branch of csrc/jpeg_idct.hip."""
+    cases = jc.matrix_cases(tmp_path)
+    items = []
+    for name, blob in cases:
+        rc, w, h, lay = jf.probe(blob)
+        assert rc == 0, name
+        items.append((w, h, jc.LAYOUT_NAMES[lay]))
+    items.append(jc.PIXEL_SLOT + ("pix",))
+    for align, residue in ((16, 0), (1, 0), (1, 3)):                           # the aligned launch and the two dense ones
+        offs, _ = jc.plan_offsets([(h, w) for w, h, _ in items], align=align)
+        census = jc.branch_census([it + (residue + int(o),) for it, o in zip(items, offs)])
+        print(align, residue, census)
+        assert list(census) == list(jc.CENSUS_ROWS) and len(census) == 22
+        assert all(v > 0 for v in census.values()), [k for k, v in census.items() if v == 0]
+    # the census itself, on launches small enough to count by hand
+    one = jc.branch_census([(6, 2, "420", 0)])                                 # chroma 3 x 1: left 2, right 2, interior 8; y = 0 top, y = 1 bottom
+    assert (one["2x2-left"], one["2x2-right"], one["2x2-interior"], one["2x2-oy-top"], one["2x2-oy-bottom"], one["2x2-oy-free"]) == (2, 2, 8, 6, 6, 0)
+    assert (one["store-npx2"], one["store-npx4-dword"], one["store-npx4-bytes"]) == (2, 1, 1)      # row 1 starts at byte 18
+    assert (one["idct-groups-live"], one["idct-groups-shadow"], one["idct-workgroups-idle"]) == (6, 26, 0)
+    two = jc.branch_census([(4, 9, "422", 1), (300, 8, "gray", 112), (5, 3, "pix", 7312)])
+    assert (two["2x1-narrow"], two["gray"], two["mode0-copy"], two["store-npx4-dword"], two["store-npx1"]) == (36, 2400, 15, 75 * 8 + 1, 3)
+    assert two["store-npx4-bytes"] == 9 + 2                                    # 4 x 9 at offset 1: never aligned; 5 x 3 at 7312: row 0 only is
+    assert (two["idct-groups-live"], two["idct-groups-shadow"], two["idct-workgroups-idle"]) == (8 + 38, 24 + 26, 1 + 0 + 2)
+
+
 def _scan_start(blob):
     return blob.index(b"\xff\xda") + 2 + int.from_bytes(blob[blob.index(b"\xff\xda") + 2:blob.index(b"\xff\xda") + 4], "big")
 
@@ -257,6 +344,7 @@ def test_host_decoder_under_sanitizers(jf, tmp_path):
     img = np.random.default_rng(3).integers(0, 256, (40, 56, 3), dtype=np.uint8)
     good = jc.save_jpeg(img, str(tmp_path / "g.jpg"), quality=85, subsampling=2, restart_marker_blocks=2)
     blobs = [b for _, b in jc.writer_extremes()[:10] + jc.unsupported_layouts()] + [jc.beyond_guard(), good, good[:len(good) // 2], good[:-2], b"", b"\xff\xd8"]
+    blobs += [b for _, b in jc.distinct_tables()[::2] + jc.dense_out_of_range()[::9] + jc.long_edges()[1:4] + jc.beyond_libjpeg_dimension()]
     rng = np.random.default_rng(1)
     for _ in range(150):
         b = bytearray(good)

@@ -104,6 +104,9 @@ static int parse_headers(const uint8_t* f, size_t len, jpg_t* j) {
             if (j->h == 0) return TISE_JPEG_UNSUPPORTED;                                 // height from a DNL marker
             if (j->w == 0 || j->ncomp == 0) return TISE_JPEG_CORRUPT;
             if (n != 6 + 3 * j->ncomp) return TISE_JPEG_CORRUPT;
+            // A SOF marker can state up to 65535, but libjpeg refuses anything above its JPEG_MAX_DIMENSION (65500) and Pillow
+            // then raises OSError: the reference job fails on such a file, so it is not turned into pixels here either.
+            if (j->w > TISE_JPEG_MAX_DIMENSION || j->h > TISE_JPEG_MAX_DIMENSION) return TISE_JPEG_UNSUPPORTED;
             if (j->ncomp != 1 && j->ncomp != 3) return TISE_JPEG_UNSUPPORTED;            // CMYK / YCCK / two components
             for (int c = 0; c < j->ncomp; ++c) {
                 cid[c] = d[6 + 3 * c];
