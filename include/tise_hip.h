@@ -68,6 +68,28 @@ int tise_memcpy_h2d_async(void* dst_dev, const void* src_host, size_t bytes, voi
 int tise_png_unfilter_rgb8(const uint8_t* slots_dev, int64_t n, int64_t slot_stride, int h, int w, uint8_t* dst_dev,
                            void* stream);
 
+/* The same reconstruction for n images of DIFFERENT sizes in one launch (object crops, O-FID / O-IS:
+ * tise_toolbox_amd/crop_feed.py).  The slots -- RGB, RGBA and mode-0 ones mixed freely -- sit at per-image offsets in one device
+ * arena, the pixels go to per-image offsets in one device buffer as (h_i, w_i, 3) uint8.  One wave per image; LDS is sized
+ * for the largest image of the launch.
+ *   arena_dev         the arena (4-byte aligned), arena_bytes long
+ *   slot_offsets_host n byte offsets of the slots in the arena, multiples of 4
+ *   hwm_host          n x 3 int32: height, width and mode (0, 3 or 4) of every slot, as the HOST knows them (what
+ *                     tise_png_inflate_slot reported); the slot's own header is not read
+ *   out_offsets_host  n byte offsets into dst_dev (dst_bytes long)
+ *   table_dev         table_bytes >= 48 * n of device scratch, 8-byte aligned: the call writes the kernel's table there
+ *   table_host_pinned NULL, or 48 * n bytes of PAGE-LOCKED host scratch (8-byte aligned) the table is built in and copied from
+ *                     asynchronously (the caller leaves it alone until the stream has passed this call); NULL: the call waits
+ *                     for its own copy
+ * Every value the kernel indexes with comes from these host arrays and is checked here, before any HIP call
+ * (TISE_ERR_INVALID_ARG): a NULL pointer, n < 0, a misaligned base or offset, h or w outside 1..65535, a mode other than
+ * 0 / 3 / 4, a filtered row above 8192 bytes (such a file must arrive as mode 0), a slot -- payload plus the 8 bytes the dword
+ * staging may read past it -- beyond arena_bytes, pixels beyond dst_bytes, a table too small.  The LDS row pitch and the rows
+ * per block of every image are computed here, rows >= 1. */
+int tise_png_unfilter_ragged_rgb8(const uint8_t* arena_dev, int64_t arena_bytes, int64_t n, const int64_t* slot_offsets_host,
+                                  const int32_t* hwm_host, const int64_t* out_offsets_host, uint8_t* dst_dev, int64_t dst_bytes,
+                                  uint8_t* table_dev, int64_t table_bytes, uint8_t* table_host_pinned, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * (a2) JPEG reconstruction on the device.  Replaces the second half of ``Image.open(f).convert("RGB")`` of
  * Dataset.__getitem__ (image_realism/FID/img_data.py:19-25; third-party Pillow -> libjpeg-turbo: dequantisation, the accurate
@@ -118,6 +140,21 @@ int tise_resize_bilinear_u8(const uint8_t* src_dev, int n, int h, int w,
  * dst_dev planar (n, 3, oh, ow) with nhwc == 0.  Square inputs need no CenterCrop. */
 int tise_resize_u8(const uint8_t* src_dev, int n, int h, int w, float* dst_dev, int oh, int ow, int nhwc,
                    const float* lut, uint8_t* u8_out_dev, int filter, void* stream);
+
+/* The uint8 result of the same resample for n images of DIFFERENT sizes, written into one (n, oh, ow, 3) uint8 batch by one
+ * launch per 4096 images (RealismEngine.features_from_u8_list: object crops).  Byte for byte what tise_resize_u8 writes to
+ * u8_out_dev image by image; plans come from the same per-size cache (a launch's plans cannot evict each other).
+ *   src_ptrs_host     n DEVICE pointers in a host array: image i is (h_host[i], w_host[i], 3) uint8, contiguous, any alignment
+ *   ws_dev            ws_bytes >= 64 * n + 4 * n * oh + 16 * ceil(n / 4096) of device scratch, 16-byte aligned (descriptors and
+ *                     the workgroup -> image map)
+ *   table_host_pinned NULL, or as many bytes of PAGE-LOCKED host scratch (16-byte aligned) the table is built in and copied from
+ *                     asynchronously; NULL: the call waits for its own copies
+ *   bad_index         optional: receives the index of the image a refusal is about, else -1
+ * Checked before anything is enqueued: a NULL pointer or a size <= 0 (TISE_ERR_INVALID_ARG), a size the plan builder
+ * refuses -- no row tile of it fits LDS -- or ow * 3 > 2048 (TISE_ERR_UNSUPPORTED). */
+int tise_resize_ragged_u8(const uint8_t* const* src_ptrs_host, const int32_t* h_host, const int32_t* w_host, int64_t n,
+                          uint8_t* dst_dev, int oh, int ow, int filter, uint8_t* ws_dev, int64_t ws_bytes,
+                          uint8_t* table_host_pinned, int64_t* bad_index, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a7) Streaming activation statistics: n, s = sum_i x_i, S = sum_i x_i x_i^T in fp64 from

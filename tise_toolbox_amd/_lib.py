@@ -41,6 +41,8 @@ SIGNATURES = {
     "tise_host_unregister": (c_int, [c_void_p]),
     "tise_memcpy_h2d_async": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "tise_png_unfilter_rgb8": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "tise_png_unfilter_ragged_rgb8": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                               c_int64, c_void_p, c_void_p]),
     "tise_jpeg_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
     "tise_jpeg_reconstruct_rgb8": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                             c_int64, c_void_p, c_void_p]),
@@ -48,6 +50,8 @@ SIGNATURES = {
                                          POINTER(c_float), c_void_p, c_void_p]),
     "tise_resize_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
                                 POINTER(c_float), c_void_p, c_int, c_void_p]),
+    "tise_resize_ragged_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int64,
+                                       c_void_p, POINTER(c_int64), c_void_p]),
     "tise_cosine_top1": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                   c_void_p, c_void_p]),
     "tise_gemm_f16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,

@@ -39,17 +39,17 @@ PNG_WORKER_SRC = os.path.join(CSRC, "png_worker.c")
 
 def build_png(force=False, verbose=True):
     """gcc over csrc/png_decode.c -> tise_toolbox_amd/libtise_png.so: the host-side PNG decoder of the image feed (plain C,
-    links zlib, dlopens libdeflate when present; no HIP, so a worker never loads the GPU runtime); and over
+    links zlib, dlopens libdeflate when present -- one decompressor per thread; no HIP, so a worker never loads the GPU runtime); and over
     csrc/png_worker.c + png_decode.c -> tise_toolbox_amd/tise_png_worker: the native decode process of the feed."""
     cc = os.environ.get("CC", "gcc")
     newest = max(os.path.getmtime(PNG_SRC), os.path.getmtime(PNG_WORKER_SRC))
     if force or not os.path.exists(PNG_LIB) or os.path.getmtime(PNG_LIB) < os.path.getmtime(PNG_SRC):
-        cmd = [cc, "-O3", "-mssse3", "-msse4.1", "-fPIC", "-shared", "-o", PNG_LIB, PNG_SRC, "-lz", "-ldl"]
+        cmd = [cc, "-O3", "-mssse3", "-msse4.1", "-fPIC", "-shared", "-o", PNG_LIB, PNG_SRC, "-lz", "-ldl", "-pthread"]
         if verbose:
             print("[tise build]", " ".join(cmd), flush=True)
         subprocess.run(cmd, check=True, cwd=CSRC)
     if force or not os.path.exists(PNG_WORKER) or os.path.getmtime(PNG_WORKER) < newest:
-        cmd = [cc, "-O3", "-mssse3", "-msse4.1", "-o", PNG_WORKER, PNG_WORKER_SRC, PNG_SRC, "-lz", "-ldl"]
+        cmd = [cc, "-O3", "-mssse3", "-msse4.1", "-o", PNG_WORKER, PNG_WORKER_SRC, PNG_SRC, "-lz", "-ldl", "-pthread"]
         if verbose:
             print("[tise build]", " ".join(cmd), flush=True)
         subprocess.run(cmd, check=True, cwd=CSRC)

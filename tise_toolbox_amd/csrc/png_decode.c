@@ -19,6 +19,7 @@
  * from the inflated rows into the caller's ring slot.
  */
 #include <dlfcn.h>
+#include <pthread.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -33,28 +34,56 @@
 
 static inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
-/* ---- libdeflate through dlopen ------------------------------------------------------------------------------------ */
+/* ---- libdeflate through dlopen ------------------------------------------------------------------------------------
+ * The library is looked up once per process (pthread_once: the crop feed decodes on THREADS, crop_feed.py).  A libdeflate
+ * decompressor holds the decode tables of the stream it is working on, so two threads must never share one: every thread
+ * gets its own on first use, freed when the thread ends.  The ring's decode processes have one thread and so one each. */
 typedef void* (*ld_alloc_fn)(void);
+typedef void (*ld_free_fn)(void*);
 typedef int (*ld_zlib_fn)(void*, const void*, size_t, void*, size_t, size_t*);
 typedef uint32_t (*ld_crc_fn)(uint32_t, const void*, size_t);
+static ld_alloc_fn g_ld_alloc = 0;
+static ld_free_fn g_ld_free = 0;
 static ld_zlib_fn g_ld_zlib = 0;
 static ld_crc_fn g_ld_crc = 0;
-static void* g_ld_dec = 0;
-static int g_ld_state = 0;       /* 0 untried, 1 usable, -1 absent */
+static int g_ld_state = 0;       /* 0 untried, 1 usable, -1 absent; written inside ld_init_once only */
+static pthread_once_t g_ld_once = PTHREAD_ONCE_INIT;
+static pthread_key_t g_ld_key;   /* this thread's decompressor */
 
-static void ld_init(void) {
-    if (g_ld_state) return;
+static void ld_free_dec(void* d) { if (d && g_ld_free) g_ld_free(d); }
+
+static void ld_init_once(void) {
     g_ld_state = -1;
     if (getenv("TISE_PNG_ZLIB")) return;                      /* A/B switch: force zlib's inflate */
     void* h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
     if (!h) h = dlopen("libdeflate.so", RTLD_NOW | RTLD_LOCAL);
     if (!h) return;
     ld_alloc_fn alloc = (ld_alloc_fn)dlsym(h, "libdeflate_alloc_decompressor");
-    g_ld_zlib = (ld_zlib_fn)dlsym(h, "libdeflate_zlib_decompress");
-    if (!alloc || !g_ld_zlib) return;
-    g_ld_crc = (ld_crc_fn)dlsym(h, "libdeflate_crc32");       /* carry-less-multiply CRC-32, ~10 x zlib's; optional */
-    g_ld_dec = alloc();
-    if (g_ld_dec) g_ld_state = 1;
+    ld_zlib_fn zfn = (ld_zlib_fn)dlsym(h, "libdeflate_zlib_decompress");
+    g_ld_free = (ld_free_fn)dlsym(h, "libdeflate_free_decompressor");
+    if (!alloc || !zfn) return;
+    if (pthread_key_create(&g_ld_key, ld_free_dec) != 0) return;
+    void* d = alloc();                                        /* the calling thread's; also shows that allocation works */
+    if (!d) return;
+    pthread_setspecific(g_ld_key, d);
+    g_ld_crc = (ld_crc_fn)dlsym(h, "libdeflate_crc32");       /* carry-less-multiply CRC-32, ~10 x zlib's; optional, stateless */
+    g_ld_alloc = alloc;
+    g_ld_zlib = zfn;
+    g_ld_state = 1;
+}
+
+static void ld_init(void) { pthread_once(&g_ld_once, ld_init_once); }
+
+/* This thread's decompressor, or NULL (no libdeflate, or out of memory): the caller then takes zlib's uncompress. */
+static void* ld_dec(void) {
+    ld_init();
+    if (g_ld_state != 1) return 0;
+    void* d = pthread_getspecific(g_ld_key);
+    if (!d) {
+        d = g_ld_alloc();
+        if (d && pthread_setspecific(g_ld_key, d) != 0) { ld_free_dec(d); d = 0; }
+    }
+    return d;
 }
 
 int tise_png_inflate_backend(void) { ld_init(); return g_ld_state == 1 ? 1 : 0; }   /* 1 libdeflate, 0 zlib */
@@ -273,10 +302,10 @@ int tise_png_decode_rgb8(const uint8_t* file, size_t len, uint8_t* dst, int h, i
     const size_t stride = (size_t)w * bpp, raw_len = (size_t)h * (stride + 1);
     if (used + raw_len > scratch_bytes) return TISE_PNG_SCRATCH;
     uint8_t* raw = scratch + used;
-    ld_init();
-    if (g_ld_state == 1) {
+    void* const dec = ld_dec();
+    if (dec) {
         size_t got = 0;
-        if (g_ld_zlib(g_ld_dec, idat, idat_len, raw, raw_len, &got) != 0 || got != raw_len) return TISE_PNG_CORRUPT;
+        if (g_ld_zlib(dec, idat, idat_len, raw, raw_len, &got) != 0 || got != raw_len) return TISE_PNG_CORRUPT;
     } else {
         uLongf got = (uLongf)raw_len;
         if (uncompress(raw, &got, idat, (uLong)idat_len) != Z_OK || got != raw_len) return TISE_PNG_CORRUPT;
@@ -335,10 +364,10 @@ int tise_png_inflate_slot(const uint8_t* file, size_t len, uint8_t* slot, size_t
         if (mode_out) *mode_out = 0;
         return rc;
     }
-    ld_init();
-    if (g_ld_state == 1) {
+    void* const dec = ld_dec();
+    if (dec) {
         size_t got = 0;
-        if (g_ld_zlib(g_ld_dec, idat, idat_len, pay, raw_len, &got) != 0 || got != raw_len) return TISE_PNG_CORRUPT;
+        if (g_ld_zlib(dec, idat, idat_len, pay, raw_len, &got) != 0 || got != raw_len) return TISE_PNG_CORRUPT;
     } else {
         uLongf got = (uLongf)raw_len;
         if (uncompress(pay, &got, idat, (uLong)idat_len) != Z_OK || got != raw_len) return TISE_PNG_CORRUPT;

@@ -17,6 +17,7 @@
 //
 // Bound: neither HBM (3000 images: 1.2 GB in + out, 0.15 ms at 8 TB/s) nor any throughput -- the chain: ~1300 steps per
 // image, three waves per SIMD interleaved.  It runs on the feed's side stream beside the trunk.
+#include <vector>
 #include "common.h"
 
 namespace {
@@ -195,6 +196,110 @@ extern "C" int tise_png_unfilter_rgb8(const uint8_t* slots_dev, int64_t n, int64
     if ((can3 && r3 < 1) || (can4 && r4 < 1)) return TISE_ERR_UNSUPPORTED;       // cannot happen below ROW_MAX
     hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)n), dim3(64), lds, (hipStream_t)stream, slots_dev, slot_stride, h, w,
                        dst_dev, p3, r3, p4, r4);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+
+// ---- images of DIFFERENT sizes in one launch (object crops: O-FID / O-IS, tise_toolbox_amd/crop_feed.py) -------------------
+// The same wave-per-image walk (unfilter_image above) with everything a wave indexes with -- where its slot starts in the
+// arena, where its pixels go, h, w, the slot's mode, the LDS row pitch and the rows per block -- read from ONE entry of a
+// device table the host call builds and checks; nothing is taken from the slot's own header.
+namespace {
+
+struct RaggedImg {          // 48 bytes, 8-byte aligned; the host call fills it, the kernel only reads it
+    int64_t slot_off;       // arena byte offset of the slot ([64-byte header | payload]), a multiple of 4
+    int64_t out_off;        // byte offset of the image's (h, w, 3) pixels in dst
+    int32_t h, w;
+    int32_t mode;           // 0 pixels (copied), 3 / 4 filtered rows of that many bytes per pixel
+    int32_t pitch, rows;    // LDS row pitch and rows per block of modes 3 / 4 (rows >= 1), 0 for mode 0
+    int32_t pad_[3];
+};
+static_assert(sizeof(RaggedImg) == 48, "table entry layout");
+
+__global__ __launch_bounds__(64) void png_unfilter_ragged_kernel(const uint8_t* __restrict__ arena, const RaggedImg* __restrict__ table,
+                                                                  uint8_t* __restrict__ dst) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const RaggedImg t = table[blockIdx.x];
+    const uint8_t* pay = arena + t.slot_off + HDR;
+    uint8_t* out = dst + t.out_off;
+    if (t.mode == 3) {
+        unfilter_image<3>(pay, out, t.h, t.w, lds, t.pitch, t.rows);
+    } else if (t.mode == 4) {
+        unfilter_image<4>(pay, out, t.h, t.w, lds, t.pitch, t.rows);
+    } else {
+        // pixels decoded on the host: copy (dwords when the destination allows it; the payload is dword aligned)
+        const int64_t nbytes = (int64_t)t.h * t.w * 3;
+        if ((reinterpret_cast<uintptr_t>(out) & 3) == 0) {
+            const int64_t nd = nbytes >> 2;
+            for (int64_t i = threadIdx.x; i < nd; i += 64) reinterpret_cast<uint32_t*>(out)[i] = reinterpret_cast<const uint32_t*>(pay)[i];
+            for (int64_t i = (nd << 2) + threadIdx.x; i < nbytes; i += 64) out[i] = pay[i];
+        } else {
+            for (int64_t i = threadIdx.x; i < nbytes; i += 64) out[i] = pay[i];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int tise_png_unfilter_ragged_rgb8(const uint8_t* arena_dev, int64_t arena_bytes, int64_t n, const int64_t* slot_offsets_host,
+                                             const int32_t* hwm_host, const int64_t* out_offsets_host, uint8_t* dst_dev,
+                                             int64_t dst_bytes, uint8_t* table_dev, int64_t table_bytes, uint8_t* table_host_pinned,
+                                             void* stream) {
+    if (n < 0 || arena_bytes < 0 || dst_bytes < 0 || table_bytes < 0) return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    if (!arena_dev || !slot_offsets_host || !hwm_host || !out_offsets_host || !dst_dev || !table_dev) return TISE_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(arena_dev) & 3) return TISE_ERR_INVALID_ARG;                       // dword staging
+    if (reinterpret_cast<uintptr_t>(table_dev) & 7) return TISE_ERR_INVALID_ARG;
+    if (n > (1 << 20)) return TISE_ERR_UNSUPPORTED;
+    if (table_bytes < n * (int64_t)sizeof(RaggedImg)) return TISE_ERR_INVALID_ARG;
+    std::vector<RaggedImg> own;
+    RaggedImg* table = reinterpret_cast<RaggedImg*>(table_host_pinned);
+    if (!table) {
+        own.resize((size_t)n);
+        table = own.data();
+    } else if (reinterpret_cast<uintptr_t>(table_host_pinned) & 7) {
+        return TISE_ERR_INVALID_ARG;
+    }
+    size_t lds = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t off = slot_offsets_host[i], oo = out_offsets_host[i];
+        const int64_t h = hwm_host[3 * i], w = hwm_host[3 * i + 1];
+        const int mode = hwm_host[3 * i + 2];
+        if (h <= 0 || w <= 0 || h > 65535 || w > 65535) return TISE_ERR_INVALID_ARG;
+        if (mode != 0 && mode != 3 && mode != 4) return TISE_ERR_INVALID_ARG;
+        if (off < 0 || (off & 3) || oo < 0) return TISE_ERR_INVALID_ARG;
+        const int64_t px = h * w * 3;
+        if (oo > dst_bytes - px) return TISE_ERR_INVALID_ARG;                                          // the image's pixels inside dst
+        RaggedImg& t = table[(size_t)i];
+        t.slot_off = off; t.out_off = oo; t.h = (int32_t)h; t.w = (int32_t)w; t.mode = mode;
+        t.pitch = 0; t.rows = 0; t.pad_[0] = t.pad_[1] = t.pad_[2] = 0;
+        if (mode == 0) {
+            if (off > arena_bytes - HDR - px) return TISE_ERR_INVALID_ARG;
+            continue;
+        }
+        // a filtered slot: rows within the kernel's limit, the whole payload + the 8 bytes the dword staging may read past it
+        // inside the arena, and at least one row per block -- a slot that fails any of these must have been decoded on the host
+        const int64_t rb = w * mode + 1;
+        if (rb > ROW_MAX) return TISE_ERR_INVALID_ARG;
+        if (off > arena_bytes - HDR - h * rb - 8) return TISE_ERR_INVALID_ARG;
+        const int pitch = lds_pitch((int)(w * mode));
+        int rows = LDS_BYTES / pitch - 1;
+        rows = rows > 64 ? 64 : rows;
+        rows = rows > (int)h ? (int)h : rows;
+        if (rows < 1) return TISE_ERR_UNSUPPORTED;                                                     // cannot happen below ROW_MAX
+        t.pitch = pitch; t.rows = rows;
+        const size_t l = (size_t)pitch * (rows + 1);
+        lds = l > lds ? l : lds;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (table_host_pinned) {
+        TISE_HIP_CHECK(hipMemcpyAsync(table_dev, table, (size_t)n * sizeof(RaggedImg), hipMemcpyHostToDevice, st));
+    } else {
+        TISE_HIP_CHECK(hipMemcpyWithStream(table_dev, table, (size_t)n * sizeof(RaggedImg), hipMemcpyHostToDevice, st));
+    }
+    hipLaunchKernelGGL(png_unfilter_ragged_kernel, dim3((unsigned)n), dim3(64), lds, st, arena_dev,
+                       reinterpret_cast<const RaggedImg*>(table_dev), dst_dev);
     TISE_LAUNCH_CHECK();
     return TISE_OK;
 }

@@ -450,3 +450,275 @@ extern "C" int tise_resize_u8(const uint8_t* src_dev, int n, int h, int w, float
                               const float* lut, uint8_t* u8_out_dev, int filter, void* stream) {
     return resize_u8_impl(src_dev, n, h, w, dst_dev, oh, ow, nhwc, lut, u8_out_dev, filter, stream);
 }
+
+
+// ---- images of DIFFERENT sizes into one (n, oh, ow, 3) uint8 batch, one launch (object crops: O-FID / O-IS) ---------------
+// RealismEngine.features_from_u8_list resized a ragged device batch with one launch per crop (~1000 launches of ~19 workgroups
+// in front of one trunk pass).  Here a workgroup still produces the RT output rows of ONE image exactly as
+// resize_bilinear_u8_kernel does -- same staging, same two integer passes, same plans from the same cache -- but learns which
+// image and which row tile from a tile -> image map and a per-image descriptor, so any mix of sizes is one grid.  uint8 output
+// only (the stem convolution applies the input table).
+namespace {
+
+struct RaggedSrc {           // 64 bytes; built and checked by tise_resize_ragged_u8, read-only in the kernel
+    const uint8_t* src;      // (h, w, 3) uint8, any alignment
+    const int* plan;         // the size's DevPlan table
+    int h, w, ksx, ksy;
+    int off_kx, off_by, off_ky, off_t0;
+    int rt, span, tile0;     // tile0: the image's first workgroup in the grid
+    int pad_;
+};
+static_assert(sizeof(RaggedSrc) == 64, "descriptor layout");
+
+template <bool SMALLK>
+__device__ __forceinline__ void resize_ragged_tile(const RaggedSrc& d, int img, int tile, uint8_t* __restrict__ u8_out, int oh, int ow,
+                                                   unsigned char* smem) {
+    const int h = d.h, w = d.w, ksx = d.ksx, ksy = d.ksy, rt = d.rt, span = d.span;
+    const int src_pitch = (w * 3 + 15) & ~15;
+    const int tmp_pitch = (ow * 3 + 3) & ~3;
+    unsigned char* srow = smem;                                          // span x src_pitch
+    unsigned char* trow = srow + (size_t)span * src_pitch;               // span x tmp_pitch
+    const int* bx = d.plan;
+    const int* kx = d.plan + d.off_kx;
+    const int* by = d.plan + d.off_by;
+    const int* ky = d.plan + d.off_ky;
+
+    const int oy0 = tile * rt;
+    const int oy1 = min(oy0 + rt, oh);
+    const int ys0 = d.plan[d.off_t0 + tile];
+    int ys1 = 0;                                                         // last source row needed by this tile
+    for (int y = oy0; y < oy1; ++y) ys1 = max(ys1, by[2 * y] + by[2 * y + 1]);
+    const int nrows = ys1 - ys0;
+    const int tid = threadIdx.x;
+    const int rowlen = ow * 3;
+
+    // stage source rows [ys0, ys1): rows are contiguous in memory (w*3 bytes each); a crop that is a view into a feed's
+    // output buffer starts wherever its offset says -- the byte loop takes what the 16-byte loop cannot
+    const uint8_t* sbase = d.src + (size_t)ys0 * (size_t)w * 3;
+    const int row_bytes = w * 3;
+    if ((((uintptr_t)sbase) & 15) == 0 && (row_bytes & 15) == 0) {
+        const int vec_per_row = row_bytes >> 4;
+        for (int i = tid; i < nrows * vec_per_row; i += 256) {
+            const int r = i / vec_per_row, c = i - r * vec_per_row;
+            *reinterpret_cast<uint4*>(srow + (size_t)r * src_pitch + c * 16) =
+                *reinterpret_cast<const uint4*>(sbase + (size_t)r * row_bytes + c * 16);
+        }
+    } else {
+        const size_t tot = (size_t)nrows * row_bytes;
+        for (size_t i = tid; i < tot; i += 256) {
+            const int r = (int)(i / row_bytes), c = (int)(i - (size_t)r * row_bytes);
+            srow[(size_t)r * src_pitch + c] = sbase[i];
+        }
+    }
+
+    // per-thread element descriptors (as resize_bilinear_u8_kernel)
+    int e_off[RS_MAXE];
+    int e_k[RS_MAXE][3];
+    int e_cnt[RS_MAXE];
+    int ne = 0;
+#pragma unroll
+    for (int j = 0; j < RS_MAXE; ++j) {
+        const int e = tid + 256 * j;
+        e_off[j] = 0; e_cnt[j] = 0;
+        e_k[j][0] = e_k[j][1] = e_k[j][2] = 0;
+        if (e < rowlen) {
+            ne = j + 1;
+            const int ox = e / 3, c = e - 3 * ox;
+            const int xmin = (w == ow) ? ox : bx[2 * ox];
+            e_off[j] = xmin * 3 + c;
+            e_cnt[j] = (w == ow) ? 1 : bx[2 * ox + 1];
+            if (SMALLK && w != ow) {
+                const int* k = kx + ox * ksx;
+                e_k[j][0] = k[0];
+                e_k[j][1] = e_cnt[j] > 1 ? k[1] : 0;
+                e_k[j][2] = e_cnt[j] > 2 ? k[2] : 0;
+            }
+        }
+    }
+    __syncthreads();
+
+    // horizontal pass LDS -> LDS (uint8 intermediate, as Pillow).  When w == ow Pillow skips this pass.
+    for (int r = 0; r < nrows; ++r) {
+        const unsigned char* sr = srow + (size_t)r * src_pitch;
+        unsigned char* tr = trow + (size_t)r * tmp_pitch;
+#pragma unroll
+        for (int j = 0; j < RS_MAXE; ++j) {
+            if (j >= ne) break;
+            const int e = tid + 256 * j;
+            if (e >= rowlen) break;
+            const unsigned char* sp = sr + e_off[j];
+            if (w == ow) {
+                tr[e] = sp[0];
+            } else if (SMALLK) {
+                const int c1 = e_cnt[j] > 1 ? 3 : 0, c2 = e_cnt[j] > 2 ? 6 : 0;
+                const int ss = (1 << (PRECISION_BITS - 1)) + __mul24((int)sp[0], e_k[j][0]) + __mul24((int)sp[c1], e_k[j][1]) +
+                               __mul24((int)sp[c2], e_k[j][2]);
+                tr[e] = clip8(ss);
+            } else {
+                const int ox = e / 3;
+                const int* k = kx + ox * ksx;
+                int ss = 1 << (PRECISION_BITS - 1);
+                for (int x = 0; x < e_cnt[j]; ++x) ss += __mul24((int)sp[x * 3], k[x]);
+                tr[e] = clip8(ss);
+            }
+        }
+    }
+    __syncthreads();
+
+    // vertical pass with <= 3 taps: four output bytes per lane (as the uint8-only branch of resize_bilinear_u8_kernel)
+    if (h != oh && ksy <= 3) {
+        const int nd = (rowlen + 3) >> 2;
+        for (int y = oy0; y < oy1; ++y) {
+            const int ymin = by[2 * y], cnt = by[2 * y + 1];
+            const int* k = ky + y * ksy;
+            const int k0 = k[0], k1 = cnt > 1 ? k[1] : 0, k2 = cnt > 2 ? k[2] : 0;
+            const unsigned char* tbase = trow + (size_t)(ymin - ys0) * tmp_pitch;
+            const int p1 = cnt > 1 ? tmp_pitch : 0, p2 = cnt > 2 ? 2 * tmp_pitch : 0;
+            uint8_t* urow = u8_out + ((size_t)img * oh + y) * (size_t)rowlen;
+            for (int dw = tid; dw < nd; dw += 256) {
+                const unsigned t0 = *reinterpret_cast<const unsigned*>(tbase + 4 * dw);
+                const unsigned t1 = *reinterpret_cast<const unsigned*>(tbase + p1 + 4 * dw);
+                const unsigned t2 = *reinterpret_cast<const unsigned*>(tbase + p2 + 4 * dw);
+                unsigned outw = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int ss = (1 << (PRECISION_BITS - 1)) + __mul24((int)((t0 >> (8 * b)) & 255u), k0) +
+                                   __mul24((int)((t1 >> (8 * b)) & 255u), k1) + __mul24((int)((t2 >> (8 * b)) & 255u), k2);
+                    outw |= (unsigned)clip8(ss) << (8 * b);
+                }
+                if (4 * dw + 3 < rowlen) {
+                    __builtin_memcpy(urow + 4 * dw, &outw, 4);
+                } else {
+                    for (int b = 0; b < 4; ++b)
+                        if (4 * dw + b < rowlen) urow[4 * dw + b] = (uint8_t)(outw >> (8 * b));
+                }
+            }
+        }
+        return;
+    }
+
+    // any tap count, and h == oh (Pillow skips the vertical pass): one output row at a time
+    for (int y = oy0; y < oy1; ++y) {
+        const int ymin = (h == oh) ? y : by[2 * y];
+        const int cnt = (h == oh) ? 1 : by[2 * y + 1];
+        const int* k = ky + y * ksy;
+        const unsigned char* tbase = trow + (size_t)(ymin - ys0) * tmp_pitch;
+        uint8_t* urow = u8_out + ((size_t)img * oh + y) * (size_t)rowlen;
+#pragma unroll
+        for (int j = 0; j < RS_MAXE; ++j) {
+            if (j >= ne) break;
+            const int e = tid + 256 * j;
+            if (e >= rowlen) break;
+            const unsigned char* tp = tbase + e;
+            uint8_t v;
+            if (h == oh) {
+                v = tp[0];
+            } else {
+                int ss = 1 << (PRECISION_BITS - 1);
+                for (int yy = 0; yy < cnt; ++yy) ss += __mul24((int)tp[(size_t)yy * tmp_pitch], k[yy]);
+                v = clip8(ss);
+            }
+            urow[e] = v;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void resize_ragged_u8_kernel(const RaggedSrc* __restrict__ descs, const int* __restrict__ tile_img,
+                                                                uint8_t* __restrict__ u8_out, int oh, int ow) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int img = tile_img[blockIdx.x];
+    const RaggedSrc d = descs[img];
+    const int tile = (int)blockIdx.x - d.tile0;
+    if (d.ksx <= 3) resize_ragged_tile<true>(d, img, tile, u8_out, oh, ow, smem);       // workgroup-uniform
+    else resize_ragged_tile<false>(d, img, tile, u8_out, oh, ow, smem);
+}
+
+constexpr int64_t RAGGED_CHUNK = 4096;   // images per launch: at most half of PLAN_CACHE_CAP distinct sizes, so gathering a
+                                         // launch's plans (each use moves a plan to the cache's front, eviction takes the back)
+                                         // can never evict a plan gathered for the same launch
+static_assert(RAGGED_CHUNK * 2 <= (int64_t)PLAN_CACHE_CAP, "a launch's plans must fit the plan cache twice");
+
+// Would get_plan refuse (h -> oh beside w -> ow)?  It refuses when even one output row per workgroup does not fit its LDS
+// budget.  span at one row per workgroup is at most ksy, a closed form: only sizes that fail THAT bound pay for the exact
+// answer (the coefficient table of the vertical pass), so the check costs nothing for crops.
+bool plan_refused(int h, int w, int oh, int ow, int filter) {
+    const size_t per_row = (size_t)((w * 3 + 15) & ~15) + (size_t)((ow * 3 + 3) & ~3);
+    const size_t budget = 144 * 1024 - 3 * 256 * 4;
+    const double scale = (double)h / oh, fs = scale < 1.0 ? 1.0 : scale;
+    const size_t ksy = (size_t)((int)ceil((filter == 1 ? 2.0 : 1.0) * fs) * 2 + 1);
+    if (ksy * per_row <= budget) return false;
+    CoeffTable ty;
+    precompute_coeffs(h, oh, ty, filter);
+    int span = 0;
+    for (int y = 0; y < oh; ++y) span = ty.bounds[y * 2 + 1] > span ? ty.bounds[y * 2 + 1] : span;
+    return (size_t)span * per_row > budget;
+}
+
+}  // namespace
+
+extern "C" int tise_resize_ragged_u8(const uint8_t* const* src_ptrs_host, const int32_t* h_host, const int32_t* w_host, int64_t n,
+                                     uint8_t* dst_dev, int oh, int ow, int filter, uint8_t* ws_dev, int64_t ws_bytes,
+                                     uint8_t* table_host_pinned, int64_t* bad_index, void* stream) {
+    if (bad_index) *bad_index = -1;
+    if (n < 0 || oh <= 0 || ow <= 0 || ws_bytes < 0 || (filter != 0 && filter != 1)) return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    if (!src_ptrs_host || !h_host || !w_host || !dst_dev || !ws_dev) return TISE_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(ws_dev) & 15) || (reinterpret_cast<uintptr_t>(table_host_pinned) & 15)) return TISE_ERR_INVALID_ARG;
+    if (ow * 3 > 256 * RS_MAXE || oh > 65535) return TISE_ERR_UNSUPPORTED;
+    if (n > (1 << 24)) return TISE_ERR_UNSUPPORTED;
+    // table: n descriptors, then one int per workgroup (at most oh row tiles per image); each launch's part ends on 16 bytes
+    const int64_t need = n * (int64_t)sizeof(RaggedSrc) + n * (int64_t)oh * 4 + 16 * ((n + RAGGED_CHUNK - 1) / RAGGED_CHUNK);
+    if (ws_bytes < need) return TISE_ERR_INVALID_ARG;
+    // everything that can be refused is refused here, before anything is enqueued
+    for (int64_t i = 0; i < n; ++i) {
+        const int h = h_host[i], w = w_host[i];
+        if (!src_ptrs_host[i] || h <= 0 || w <= 0) { if (bad_index) *bad_index = i; return TISE_ERR_INVALID_ARG; }
+        if (h > (1 << 20) || w > (1 << 20) || plan_refused(h, w, oh, ow, filter)) { if (bad_index) *bad_index = i; return TISE_ERR_UNSUPPORTED; }
+    }
+    std::vector<unsigned char> own;
+    unsigned char* host = table_host_pinned;
+    if (!host) {
+        own.resize((size_t)need);
+        host = own.data();
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int64_t pos = 0;                                           // bytes of the table used by the launches so far
+    for (int64_t c0 = 0; c0 < n; c0 += RAGGED_CHUNK) {
+        const int64_t cn = (n - c0 < RAGGED_CHUNK) ? n - c0 : RAGGED_CHUNK;
+        RaggedSrc* descs = reinterpret_cast<RaggedSrc*>(host + pos);
+        int* tiles = reinterpret_cast<int*>(host + pos + cn * (int64_t)sizeof(RaggedSrc));
+        int64_t ntiles = 0;
+        size_t lds = 0;
+        for (int64_t i = 0; i < cn; ++i) {
+            const int h = h_host[c0 + i], w = w_host[c0 + i];
+            DevPlan p;
+            const int rc = get_plan(h, w, oh, ow, filter, &p);
+            if (rc != TISE_OK) { if (bad_index) *bad_index = c0 + i; return rc; }
+            RaggedSrc& d = descs[i];
+            d.src = src_ptrs_host[c0 + i]; d.plan = p.dev; d.h = h; d.w = w; d.ksx = p.ksx; d.ksy = p.ksy;
+            d.off_kx = p.off_kx; d.off_by = p.off_by; d.off_ky = p.off_ky; d.off_t0 = p.off_t0;
+            d.rt = p.rt; d.span = p.span; d.tile0 = (int)ntiles; d.pad_ = 0;
+            if (p.ntiles > oh) { if (bad_index) *bad_index = c0 + i; return TISE_ERR_UNSUPPORTED; }   // (rt >= 1: cannot happen)
+            for (int t = 0; t < p.ntiles; ++t) tiles[ntiles + t] = (int)i;
+            ntiles += p.ntiles;
+            const size_t l = (size_t)p.span * (size_t)(((w * 3 + 15) & ~15) + ((ow * 3 + 3) & ~3));
+            lds = l > lds ? l : lds;
+        }
+        const int64_t bytes = ((cn * (int64_t)sizeof(RaggedSrc) + ntiles * 4) + 15) & ~(int64_t)15;
+        if (table_host_pinned) {
+            TISE_HIP_CHECK(hipMemcpyAsync(ws_dev + pos, host + pos, (size_t)bytes, hipMemcpyHostToDevice, st));
+        } else {
+            TISE_HIP_CHECK(hipMemcpyWithStream(ws_dev + pos, host + pos, (size_t)bytes, hipMemcpyHostToDevice, st));
+        }
+        if (lds > 48 * 1024)
+            TISE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_ragged_u8_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(resize_ragged_u8_kernel, dim3((unsigned)ntiles), dim3(256), lds, st,
+                           reinterpret_cast<const RaggedSrc*>(ws_dev + pos),
+                           reinterpret_cast<const int*>(ws_dev + pos + cn * (int64_t)sizeof(RaggedSrc)),
+                           dst_dev + (size_t)c0 * (size_t)oh * (size_t)ow * 3, oh, ow);
+        TISE_LAUNCH_CHECK();
+        pos += bytes;
+    }
+    return TISE_OK;
+}

@@ -238,6 +238,62 @@ def resize_u8_only(src_u8, out_hw=(299, 299), out=None):
     return u8
 
 
+_RAGGED_TABLES = {}        # device index -> [[pinned table, event of the launch that last read it], ...] (two, used in turn)
+
+
+def resize_ragged_u8(crops, out_hw=(299, 299), out=None, filter="bilinear"):
+    """List of (H_i,W_i,3) uint8 CUDA tensors of any sizes -> the Pillow-exact resized uint8 batch (B,oh,ow,3) in ONE launch
+    (tise_resize_ragged_u8), byte for byte what ``resize_u8_only`` gives crop by crop.  A crop inside Pillow's vertical-first
+    rule (pillow_vertical_first: more than 100 times taller than wide) gets its vertical pass in a launch of its own first, as
+    there.  A size the plan builder refuses raises before anything of the batch is enqueued, naming the crop."""
+    if len(crops) == 0:
+        raise ValueError("empty batch")
+    oh, ow = out_hw
+    dev = crops[0].device
+    srcs = []
+    for i, c in enumerate(crops):
+        _require_cuda(c)
+        if c.dim() == 4 and c.shape[0] == 1:
+            c = c[0]
+        if c.dtype != torch.uint8 or c.dim() != 3 or c.shape[2] != 3:
+            raise ValueError(f"crop {i} must be (H,W,3) uint8")
+        c = c.contiguous()
+        if pillow_vertical_first(c.shape[0], c.shape[1], oh):
+            c = _vertical_pass_first(c.unsqueeze(0), oh, filter)[0]
+        srcs.append(c)
+    n = len(srcs)
+    if out is None:
+        out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n, oh, ow, 3) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("out must be a contiguous (N,oh,ow,3) uint8 CUDA tensor")
+    ptrs = np.fromiter((c.data_ptr() for c in srcs), dtype=np.uint64, count=n)
+    hs = np.fromiter((c.shape[0] for c in srcs), dtype=np.int32, count=n)
+    ws = np.fromiter((c.shape[1] for c in srcs), dtype=np.int32, count=n)
+    need = n * (64 + 4 * oh) + 16 * (n // 4096 + 1)
+    ws_dev = torch.empty(need, dtype=torch.uint8, device=dev)
+    # the table is built in page-locked memory and copied asynchronously (the host does not wait for the stream: the trunk
+    # passes of earlier batches are still queued there); two buffers in turn, each reused once its last copy has run
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    ring = _RAGGED_TABLES.setdefault(key, [[None, None], [None, None]])
+    slot = ring.pop(0)
+    ring.append(slot)
+    if slot[1] is not None:
+        slot[1].synchronize()
+    if slot[0] is None or slot[0].numel() < need:
+        slot[0] = torch.empty(max(need, 1 << 16), dtype=torch.uint8).pin_memory()
+    bad = ctypes.c_int64(-1)
+    st = _lib.load().tise_resize_ragged_u8(ptrs.ctypes.data, hs.ctypes.data, ws.ctypes.data, n, _ptr(out), oh, ow, _FILTERS[filter],
+                                           _ptr(ws_dev), need, slot[0].data_ptr(), ctypes.byref(bad), _stream())
+    if st != _lib.TISE_OK:
+        if bad.value >= 0:
+            raise _lib.TiseStatusError(f"tise_resize_ragged_u8 (image {bad.value} of the batch, {int(hs[bad.value])} x {int(ws[bad.value])})",
+                                       st, _lib.load().tise_status_string(st).decode())
+        _lib.check("tise_resize_ragged_u8", st)
+    slot[1] = torch.cuda.Event()
+    slot[1].record(torch.cuda.current_stream(dev))
+    return out
+
+
 def read_split_overflow():
     """Read-and-clear the range guard of the split-fp16 activation format (csrc/common.h): True when any kernel
     since the last read converted a value above the fp16 range (65504) or a NaN into a split tensor.  Synchronises

@@ -186,15 +186,12 @@ class RealismEngine:
     @torch.no_grad()
     def features_from_u8_list(self, crops):
         """Ragged batch: list of (H_i,W_i,3) uint8 tensors (object crops of different sizes, O-FID / O-IS) ->
-        pool3 (B,dims) [and logits].  Each crop is resized (Pillow-exact) into its row of ONE (B,299,299,3) uint8
-        buffer -- one small launch per crop, resize plans cached per size -- and the trunk runs ONCE on the batch."""
+        pool3 (B,dims) [and logits].  Every crop is resized (Pillow-exact) into its row of ONE (B,299,299,3) uint8
+        buffer by ONE launch for the whole list (device.resize_ragged_u8: resize plans cached per size, the same bytes as
+        a launch per crop) and the trunk runs ONCE on the batch."""
         if len(crops) == 0:
             raise ValueError("empty batch")
-        u8 = torch.empty((len(crops), 299, 299, 3), dtype=torch.uint8, device=self.device)
-        for i, c in enumerate(crops):
-            if c.dim() == 4:
-                c = c[0]
-            device.resize_u8_only(c.to(self.device, non_blocking=True).unsqueeze(0), (299, 299), out=u8[i:i + 1])
+        u8 = device.resize_ragged_u8([(c[0] if c.dim() == 4 else c).to(self.device, non_blocking=True) for c in crops], (299, 299))
         if self._u8_stem:
             return self._trunk_u8(u8)
         lut = self.lut_dev.view(3, 256)

@@ -117,6 +117,11 @@ def _build_parser():
                              "of this process and reconstructed on the GPU (jpeg_feed.py; images may differ in size); pillow: such "
                              "directories take the path of every other file (Pillow in the --png-feed workers).  Default: native for "
                              "directories whose images differ in size, pillow for directories of one size (the faster one of each, DESIGN.md)")
+    parser.add_argument("--crop-feed", type=str, default=None, choices=["native", "dataloader"],
+                        help="native: PNG directories whose images differ in size (object crops, O-FID) are inflated by threads of this "
+                             "process and their row filters reversed on the GPU (crop_feed.py); dataloader: torch DataLoader workers, one "
+                             "copy per crop.  Default: --per-class takes the native feed when the shard's first file is a PNG of the "
+                             "native subset; a plain directory takes it only when asked (otherwise --png-feed decides)")
     return parser
 
 
@@ -293,6 +298,7 @@ U8_CACHE_NAME = ".tise_u8_cache.npy"
 
 _PNG_FEED = {"mode": "ring"}        # --png-feed
 _JPEG_FEED = {"mode": None}         # --jpeg-feed (None: native for ragged JPEG directories, pillow for directories of one size)
+_CROP_FEED = {"mode": None}         # --crop-feed (None: native for --per-class when the shard's first file is a native-subset PNG; plain directories only on request)
 _RING_PREFETCH = {}                  # directory -> PngRingLoader whose workers are already decoding (started before the model was built)
 _RING_LOCK = __import__("threading").Lock()   # the second directory's prefetch is started from the first loader's feeder thread
 
@@ -322,7 +328,7 @@ def prefetch_png_ring(path, batch_size, num_workers=0):
     """Start the decode workers of an image directory NOW (before the model is built / while the other side is still in
     the network): _compute_statistics_of_path picks the running loader up.  No GPU call is made here."""
     from . import png_ring
-    if _PNG_FEED["mode"] != "ring" or path.endswith(".npz") or not os.path.isdir(path):
+    if _PNG_FEED["mode"] != "ring" or _CROP_FEED["mode"] == "native" or path.endswith(".npz") or not os.path.isdir(path):
         return None
     with _RING_LOCK:
         if path in _RING_PREFETCH:
@@ -405,6 +411,21 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         if tdist.is_main():
             print(loader.feed_line(time.perf_counter() - t0), file=sys.stderr)
         _compute_statistics_of_path.last_jpeg_loader = loader
+        return out
+    if _CROP_FEED["mode"] == "native" and shard:
+        # --crop-feed native: decode threads -> page-locked arenas of packed inflate-only slots -> side-stream H2D -> the row
+        # filters on the GPU (crop_feed.py); PNG directories of any sizes, under torchrun as well.  Items are loader batches
+        # as the DataLoader's collate_u8 makes them, so the statistics are the --png-feed dataloader path's to the last bit
+        from . import crop_feed
+        loader = crop_feed.CropFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers)
+        t0 = time.perf_counter()
+        try:
+            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda)
+        finally:
+            loader.close()
+        if tdist.is_main():
+            print(loader.feed_line(time.perf_counter() - t0), file=sys.stderr)
+        _compute_statistics_of_path.last_crop_loader = loader
         return out
     if _PNG_FEED["mode"] == "ring":
         # decode workers -> shared page-locked ring -> side-stream H2D (png_ring.py).  A directory with images of different
@@ -605,10 +626,18 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None):
     lo, hi = tdist.shard_range(len(files), rank, world)
     engine = _engine_for(model, dims)
     accs = {c: device.StatsAccumulator(dims, engine.device) for c in names}
-    dataset = img_data.Dataset(path, transform=None, file_names=files[lo:hi])
-    loader = torch.utils.data.DataLoader(dataset=dataset, batch_size=batch_size, shuffle=False, drop_last=False,
-                                         num_workers=min(32, _num_workers(num_workers, world)), collate_fn=img_data.collate_u8,
-                                         pin_memory=True, worker_init_fn=img_data.worker_init)
+    from . import crop_feed
+    feed = None
+    if crop_feed.use_native(files[lo:hi], _CROP_FEED["mode"]):
+        # the crop feed (crop_feed.py): same loader batches, same order, every crop used -- the same class statistics to the last bit
+        loader = feed = crop_feed.CropFeedLoader(files[lo:hi], batch_size, engine.device, workers=_num_workers(num_workers, world),
+                                                 drop_last=False)
+    else:
+        dataset = img_data.Dataset(path, transform=None, file_names=files[lo:hi])
+        loader = torch.utils.data.DataLoader(dataset=dataset, batch_size=batch_size, shuffle=False, drop_last=False,
+                                             num_workers=min(32, _num_workers(num_workers, world)), collate_fn=img_data.collate_u8,
+                                             pin_memory=True, worker_init_fn=img_data.worker_init)
+    t_feed = time.perf_counter()
     # The pool3 rows of the directory stay on the device (8 KB per crop); once the walk is complete they are sorted by class
     # and folded into the 80 accumulators by ONE grouped launch (device.stats_update_grouped): every class's S is
     # read-modify-written once per directory.  Round 4 ran one index_select + one 528-workgroup covariance launch per class
@@ -642,6 +671,11 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None):
         if kept_rows >= FLUSH_ROWS:
             flush()
     flush()
+    if feed is not None:
+        feed.close()
+        if tdist.is_main():
+            print(feed.feed_line(time.perf_counter() - t_feed), file=sys.stderr)
+        _class_statistics.last_crop_loader = feed
     engine.check_numerics()                                # split-fp16 range guard, agreed on by all ranks before the reductions
     # every class is OWNED by one rank (``owner``: class -> rank, the same map on every rank and for both image sets):
     # its 33.57 MB buffer is reduced to that rank only, which alone finalises and solves it (calculate_per_class_fid) --
@@ -782,6 +816,7 @@ def main(argv=None):
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)        # reference: CUDA_VISIBLE_DEVICES = args.gpu (:243)
     _PNG_FEED["mode"] = args.png_feed
     _JPEG_FEED["mode"] = args.jpeg_feed
+    _CROP_FEED["mode"] = args.crop_feed
     if args.conv is not None:
         os.environ["TISE_CONV"] = "miopen" if args.conv == "exact" else "split"
     kind = tweights.inception_kind(args.network, args.label == "O-FID" and args.num_classes == 80)

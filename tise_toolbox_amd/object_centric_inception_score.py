@@ -57,11 +57,14 @@ def _engine(weights, num_classes, seed):
 
 
 def inception_score(imgs, cuda=True, batch_size=32, resize=False, splits=1, weights=None, num_classes=80, seed=0,
-                    temperature=T_OIS, num_workers=8):
+                    temperature=T_OIS, num_workers=8, crop_feed=None):
     """Computes the inception score of the generated images imgs (object_centric_inception_score.py:17).
 
     imgs -- dataset of uint8 (H,W,3) images (``IgnoreLabelDataset``) or of (3,H,W) float tensors already
             normalised to [-1, 1] (the reference convention; ``resize`` then upsamples them to 299x299, :49)
+    crop_feed -- "native": the crops of an ``IgnoreLabelDataset`` are inflated by threads of this process and their row filters
+            reversed on the GPU (crop_feed.py); "dataloader": DataLoader workers; None: native when this rank's first file is a PNG
+            of the native subset.  Both routes form the same batches: the score is the same to the last bit.
     Returns (mean, std) over the splits, np.float64 like the reference.
     """
     N = len(imgs)
@@ -73,10 +76,22 @@ def inception_score(imgs, cuda=True, batch_size=32, resize=False, splits=1, weig
     eng = _engine(weights, num_classes, seed)
     rank, world, _ = tdist.env_world()
     lo, hi = tdist.shard_range(N, rank, world)
-    subset = torch.utils.data.Subset(imgs, range(lo, hi))
-    loader = torch.utils.data.DataLoader(subset, batch_size=batch_size, num_workers=num_workers,
-                                         collate_fn=img_data.collate_u8 if isinstance(imgs, IgnoreLabelDataset) else None,
-                                         worker_init_fn=img_data.worker_init)
+    feed = None
+    if isinstance(imgs, IgnoreLabelDataset):
+        from . import crop_feed as _cf
+        files = [os.path.join(imgs.imgspath, name) for name in imgs.namelist[lo:hi]]
+        if _cf.use_native(files, crop_feed):
+            feed = _cf.CropFeedLoader(files, batch_size, eng.device, drop_last=False)
+    if feed is not None:
+        loader = feed
+    else:
+        subset = torch.utils.data.Subset(imgs, range(lo, hi))
+        loader = torch.utils.data.DataLoader(subset, batch_size=batch_size, num_workers=num_workers,
+                                             collate_fn=img_data.collate_u8 if isinstance(imgs, IgnoreLabelDataset) else None,
+                                             worker_init_fn=img_data.worker_init)
+    import sys
+    import time
+    t_feed = time.perf_counter()
     eng.begin(n_total=N, temperature=temperature, splits=splits, rule="ois")
     base = lo
     # batch_size (32 in the reference's call, :122) is the loader's batch; a trunk pass takes up to
@@ -94,6 +109,11 @@ def inception_score(imgs, cuda=True, batch_size=32, resize=False, splits=1, weig
             feats, logits = eng._trunk(x.contiguous(memory_format=torch.channels_last), prenormalized=True)
         eng.is_acc.update(logits, base)
         base += logits.shape[0]
+    if feed is not None:
+        feed.close()
+        if tdist.is_main():
+            print(feed.feed_line(time.perf_counter() - t_feed), file=sys.stderr)
+        inception_score.last_crop_loader = feed
     eng.check_numerics()                                                      # split-fp16 range guard
     tdist.all_reduce_sum_(eng.is_acc.acc)
     mean, std, _ = eng.is_acc.finalize()
@@ -109,6 +129,9 @@ def parse_args(argv=None):
     parser.add_argument("--synthetic-weights", action="store_true",
                         help="seeded stand-in parameters (plumbing / throughput only; results are tagged)")
     parser.add_argument("--seed", default=0, type=int, help="seed of the --synthetic-weights parameters")
+    parser.add_argument("--crop-feed", default=None, type=str, choices=["native", "dataloader"],
+                        help="native: crops are inflated by threads of this process and unfiltered on the GPU (crop_feed.py); "
+                             "dataloader: DataLoader workers; default: native when the first file is a PNG of the native subset")
     return parser.parse_args(argv)
 
 
@@ -123,7 +146,7 @@ def main(argv=None):
     print("Calculating Inception Score...")
     from .engine import run_with_exact_fallback
     IS_mean, IS_std = run_with_exact_fallback(lambda: inception_score(imgs, cuda=True, batch_size=32, resize=False, splits=10,      # :122
-                                                                      weights=wpath, seed=args.seed), "the O-IS")
+                                                                      weights=wpath, seed=args.seed, crop_feed=args.crop_feed), "the O-IS")
     if tdist.is_main():
         if args.saved_file:
             with open(args.saved_file, "w") as f:
