@@ -187,6 +187,36 @@ int tise_stats_buffer(tise_stats_t* h, double** buf_dev, size_t* n_doubles);
 int tise_stats_finalize(tise_stats_t* h, double* mu_dev, double* sigma_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Kernel Inception Distance: grouped sums of the polynomial kernel k(a, b) = (a.b / d + 1)^3 (csrc/mmd.hip).
+ * No counterpart in the reference (it has FID only); the estimator is the one of Binkowski et al. 2018 as torch-fidelity,
+ * the StyleGAN2-ADA metrics and clean-fid compute it on the host with numpy.  For every group g, from fp32 rows on the device:
+ *     out_dev[3 g + 0] = Sxx = sum_{i != j} k(x_i, x_j)     out_dev[3 g + 1] = Syy = sum_{i != j} k(y_i, y_j)
+ *     out_dev[3 g + 2] = Sxy = sum_{i, j} k(x_i, y_j)
+ * with the dot products in fp64 on the matrix cores; no Gram matrix is materialised.  All groups, the three blocks of each and
+ * all their 64 x 64 tiles go in ONE launch (a work list of exactly the tiles that exist), followed by one small launch that
+ * adds the tiles' partial sums in a fixed order: no floating-point atomics, two calls on the same inputs give the same bits.
+ *   x_dev, y_dev        fp32 feature matrices, rows_* rows of ld_* floats, d columns used (ld >= d, ld % 4 == 0, 16-byte
+ *                       aligned base; NULL only with rows == 0)
+ *   offsets_*_host      HOST arrays of n_groups + 1 ascending entries, per side (as tise_stats_update_grouped's row_offsets)
+ *   index_*_dev         NULL: group g of that side is the contiguous rows offsets[g] .. offsets[g + 1] - 1;
+ *                       else n_index_* int64 row numbers on the DEVICE and group g is the rows index[offsets[g] .. offsets[g + 1] - 1]
+ *   A group may have different sizes on the two sides; a side with 0 rows yields zeros for the sums it enters.
+ *   out_dev             3 * n_groups doubles
+ *   ws_dev              ws_bytes >= tise_mmd_poly3_workspace_bytes(...) of device scratch, 8-byte aligned (segment table + one
+ *                       double per tile); the call copies its table there and waits for that copy before it launches
+ * Rejected before any HIP call (TISE_ERR_INVALID_ARG): a NULL pointer, d <= 0, ld < d, ld % 4 != 0 or a base that is not 16-byte
+ * aligned, negative counts, descending offsets, a group that reaches past the rows (or past the index), a workspace too small.
+ * TISE_ERR_UNSUPPORTED: a group above 2^24 rows or more than 2^31 - 1 tiles in all.
+ * The VALUES of a device index array are NOT checked here and are trusted to lie in [0, rows): the caller validates them on
+ * the host before it uploads them (tise_toolbox_amd.device.PolynomialMMD does).
+ * ------------------------------------------------------------------------------------------ */
+int tise_mmd_poly3_workspace_bytes(const int64_t* offsets_x_host, const int64_t* offsets_y_host, int n_groups, size_t* bytes);
+int tise_mmd_poly3_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, const int64_t* index_x_dev, int64_t n_index_x,
+                           const int64_t* offsets_x_host, const float* y_dev, int64_t rows_y, int64_t ld_y,
+                           const int64_t* index_y_dev, int64_t n_index_y, const int64_t* offsets_y_host, int n_groups, int d,
+                           double* out_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a6) Frechet distance.
  * Replaces calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps)
  *                                           image_realism/FID/fid_score.py:121-171

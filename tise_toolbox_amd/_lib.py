@@ -71,6 +71,9 @@ SIGNATURES = {
     "tise_stats_update_grouped": (c_int, [POINTER(c_void_p), c_int, c_void_p, POINTER(c_int64), c_int64, c_void_p]),
     "tise_stats_buffer": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_size_t)]),
     "tise_stats_finalize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "tise_mmd_poly3_workspace_bytes": (c_int, [POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_size_t)]),
+    "tise_mmd_poly3_grouped": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64, c_int64,
+                                        c_void_p, c_int64, POINTER(c_int64), c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tise_frechet_create": (c_int, [c_int, POINTER(c_void_p)]),
     "tise_frechet_destroy": (c_int, [c_void_p]),
     "tise_frechet_distance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),

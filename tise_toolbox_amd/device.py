@@ -402,6 +402,97 @@ def stats_update_grouped(accs, feats_sorted, offsets):
     _lib.call("tise_stats_update_grouped", handles, ng, _ptr(feats_sorted), arr, feats_sorted.stride(0), _stream())
 
 
+def mmd_offsets(offsets, limit, what):
+    """Host check of one side's group offsets: n_groups + 1 ascending entries from >= 0 up to at most ``limit`` -> int64 array."""
+    offs = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if offs.size < 1 or offs[0] < 0 or np.any(np.diff(offs) < 0) or offs[-1] > limit:
+        raise ValueError(f"{what}: offsets must ascend from >= 0 to at most {limit} (got {offs[:4].tolist()}.. {offs[-1:].tolist()})")
+    return np.ascontiguousarray(offs)
+
+
+def mmd_index(index, rows, what):
+    """Host check of a row index BEFORE it is uploaded (the kernel trusts a device index: include/tise_hip.h): integers in
+    [0, rows), one dimension -> contiguous int64 array.  Runs without a GPU."""
+    if isinstance(index, torch.Tensor):
+        if index.is_cuda:
+            raise TypeError(f"{what}: pass the index as a host array; it is validated on the host and uploaded here")
+        index = index.numpy()
+    idx = np.asarray(index)
+    if idx.ndim != 1 or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError(f"{what}: the index must be a one-dimensional integer array")
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= rows):
+        raise ValueError(f"{what}: index values must lie in [0, {rows}) (got {int(idx.min())} .. {int(idx.max())})")
+    return idx
+
+
+class PolynomialMMD:
+    """Grouped sums of the KID kernel k(a, b) = (a.b / d + 1)^3 on resident fp32 rows (tise_mmd_poly3_grouped in
+    include/tise_hip.h): every group's Sxx, Syy, Sxy from one launch pair, bitwise reproducible."""
+
+    def __init__(self, device=None):
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise _lib.TiseLibraryError("PolynomialMMD needs a HIP device")
+        self._ws = None
+
+    def _side(self, t, what):
+        _require_cuda(t)
+        if t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError(f"{what} must be a (rows, d) float32 tensor")
+        if t.shape[0] and (t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16):
+            t = t.contiguous()
+            if t.stride(0) % 4 or t.data_ptr() % 16:                 # d % 4 != 0: pad the rows to the fetch's alignment
+                p = torch.zeros((t.shape[0], (t.shape[1] + 3) // 4 * 4), dtype=torch.float32, device=t.device)
+                p[:, :t.shape[1]] = t
+                t = p[:, :t.shape[1]]
+        return t
+
+    def sums(self, X, Y, offsets_x, offsets_y, index_x=None, index_y=None):
+        """X (rows_x, d), Y (rows_y, d): fp32 CUDA tensors (row stride may exceed d).  offsets_*: n_groups + 1 host integers
+        per side.  index_* (host integer arrays, optional): with an index, group g of that side is the rows
+        index[offsets[g]:offsets[g + 1]], else the contiguous rows offsets[g]:offsets[g + 1].  -> (n_groups, 3) fp64 CUDA tensor
+        [Sxx, Syy, Sxy]; the groups' sizes come back as two int64 arrays in ``last_counts``."""
+        X, Y = self._side(X, "X"), self._side(Y, "Y")
+        if X.shape[1] != Y.shape[1] or X.shape[1] < 1:
+            raise ValueError("X and Y must have the same, positive number of columns")
+        ix = mmd_index(index_x, X.shape[0], "index_x") if index_x is not None else None
+        iy = mmd_index(index_y, Y.shape[0], "index_y") if index_y is not None else None
+        ox = mmd_offsets(offsets_x, ix.size if ix is not None else X.shape[0], "offsets_x")
+        oy = mmd_offsets(offsets_y, iy.size if iy is not None else Y.shape[0], "offsets_y")
+        if ox.size != oy.size:
+            raise ValueError("both sides need the same number of groups")
+        ng = ox.size - 1
+        self.last_counts = (np.diff(ox), np.diff(oy))
+        out = torch.zeros((ng, 3), dtype=torch.float64, device=self.device)
+        if ng == 0:
+            return out
+        with torch.cuda.device(self.device):
+            ixd = torch.from_numpy(ix).to(self.device) if ix is not None else None           # ONE upload per side
+            iyd = torch.from_numpy(iy).to(self.device) if iy is not None else None
+            pox = ox.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+            poy = oy.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+            nbytes = ctypes.c_size_t()
+            _lib.call("tise_mmd_poly3_workspace_bytes", pox, poy, ng, ctypes.byref(nbytes))
+            if self._ws is None or self._ws.numel() < nbytes.value:
+                self._ws = torch.empty(max(256, nbytes.value), dtype=torch.uint8, device=self.device)
+            _lib.call("tise_mmd_poly3_grouped",
+                      _ptr(X), X.shape[0], X.stride(0) if X.shape[0] else X.shape[1] + (-X.shape[1]) % 4, _ptr(ixd) if ixd is not None else None,
+                      ix.size if ix is not None else 0, pox,
+                      _ptr(Y), Y.shape[0], Y.stride(0) if Y.shape[0] else Y.shape[1] + (-Y.shape[1]) % 4, _ptr(iyd) if iyd is not None else None,
+                      iy.size if iy is not None else 0, poy, ng, int(X.shape[1]), _ptr(out), _ptr(self._ws), self._ws.numel(), _stream())
+        return out
+
+    def mmd2(self, X, Y, offsets_x, offsets_y, index_x=None, index_y=None):
+        """The unbiased estimator per group, Sxx / (n (n - 1)) + Syy / (m (m - 1)) - 2 Sxy / (n m): (n_groups,) fp64 CUDA tensor;
+        NaN -- not an exception -- for a group with n < 2 or m < 2 (the callers decide what a skipped group means)."""
+        s = self.sums(X, Y, offsets_x, offsets_y, index_x, index_y)
+        n = torch.from_numpy(self.last_counts[0].astype(np.float64)).to(self.device)
+        m = torch.from_numpy(self.last_counts[1].astype(np.float64)).to(self.device)
+        v = s[:, 0] / (n * (n - 1.0)) + s[:, 1] / (m * (m - 1.0)) - 2.0 * s[:, 2] / (n * m)
+        return torch.where((n < 2) | (m < 2), torch.full_like(v, float("nan")), v)
+
+
 def _wrap_device_doubles(ptr, n, device, owner=None):
     """Zero-copy torch view of `n` doubles at device address `ptr` (__cuda_array_interface__)."""
     class _Holder:

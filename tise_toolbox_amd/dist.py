@@ -155,6 +155,35 @@ def reduce_sum_(t, dst):
     return t
 
 
+def all_gather_rows(t, counts=None):
+    """Rows of every rank in GLOBAL index order (rank 0's rows, then rank 1's, ...): ``t`` is this rank's (rows, width) tensor,
+    ``counts`` the rows of every rank (None: exchanged first; shard sizes may differ, a rank may hold none).  The KID's retained
+    pool3 rows travel this way: shards are contiguous index ranges (shard_files / shard_range), so the result is the walk
+    order of the one-process run, bit for bit, on every rank.  Identity for one process."""
+    if not _collective():
+        return t
+    world = dist.get_world_size()
+    if counts is None:
+        on_dev = t.is_cuda and dist.get_backend() == "nccl"
+        c = torch.zeros(world, dtype=torch.int64, device=t.device if on_dev else "cpu")
+        c[dist.get_rank()] = t.shape[0]
+        dist.all_reduce(c, op=dist.ReduceOp.SUM)
+        counts = c.tolist()
+    counts = [int(c) for c in counts]
+    if len(counts) != world or counts[dist.get_rank()] != t.shape[0]:
+        raise ValueError(f"counts {counts} do not describe this rank's {t.shape[0]} rows in a group of {world}")
+    # equal-sized pieces (all_gather's contract on every backend): pad to the largest shard, cut the padding off afterwards
+    home = t.device
+    if t.is_cuda and dist.get_backend() != "nccl":       # gloo gathers host tensors only (tests on a single-GPU box)
+        t = t.cpu()
+    width, most = tuple(t.shape[1:]), max(counts)
+    mine = t.new_zeros((most,) + width)
+    mine[:t.shape[0]] = t
+    pieces = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(pieces, mine)
+    return torch.cat([p[:n] for p, n in zip(pieces, counts)], dim=0).to(home)
+
+
 def class_owners(names, world):
     """Per-class O-FID (fid_score.calculate_per_class_fid): class i of the SORTED class list is owned by rank i mod world --
     its statistics are reduced to that rank only, which solves it.  The same map on every rank (the list comes from

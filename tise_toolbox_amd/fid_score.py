@@ -122,6 +122,14 @@ def _build_parser():
                              "process and their row filters reversed on the GPU (crop_feed.py); dataloader: torch DataLoader workers, one "
                              "copy per crop.  Default: --per-class takes the native feed when the shard's first file is a PNG of the "
                              "native subset; a plain directory takes it only when asked (otherwise --png-feed decides)")
+    parser.add_argument("--kid", action="store_true",
+                        help="also report the Kernel Inception Distance (kid.py: unbiased MMD^2, kernel (x.y/d + 1)^3) from the "
+                             "same pass over the images; --save-stats then also stores the feature rows, and an .npz input must hold them")
+    parser.add_argument("--kid-subsets", type=int, default=100, help="number of random subsets of the KID estimate")
+    parser.add_argument("--kid-subset-size", type=int, default=1000,
+                        help="rows per subset and side (capped at the smaller set); 0 = the full-set estimator, no subsets")
+    parser.add_argument("--kid-seed", type=int, default=0, help="seed of numpy.random.RandomState for the subsets")
+    parser.add_argument("--kid-saved-file", type=str, default="", help="write the KID line(s) to this file")
     return parser
 
 
@@ -237,13 +245,15 @@ def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
 
 
 def calculate_activation_statistics(images, model, batch_size=64, dims=2048, cuda=True, verbose=True,
-                                    return_device=False):
+                                    return_device=False, keep_features=False):
     """mu = mean(act), sigma = cov(act) of the pool_3 activations (fid_score.py:174-196).
 
     Unlike the reference no (N, dims) float64 array is ever materialised: every batch is folded
     into fp64 {n, sum x, sum x x^T} on the device and (mu, sigma) are finalised there.  Under
     torchrun each rank passes ITS shard of the batches; the sums are all-reduced over RCCL.
     Returns numpy float64 arrays (or CUDA tensors with ``return_device``).
+    ``keep_features`` (KID, opt-in): the fp32 pool3 rows of the images used are also kept on the device (8 KB per image) and
+    returned as a third value, in global index order on every rank (dist.all_gather_rows).  Without it nothing is retained.
     """
     _check_cuda(cuda)
     model.eval()
@@ -267,9 +277,13 @@ def calculate_activation_statistics(images, model, batch_size=64, dims=2048, cud
         limit = device_batch_images(batch_size)
         batches = coalesce_u8(_first(images, n_batches), engine.device, limit, (n_batches * batch_size, batch_size))
     err = None
+    kept = []
     try:
         for batch in batches:
-            stats.update(_forward_batch(engine, model, batch))
+            f = _forward_batch(engine, model, batch)
+            stats.update(f)
+            if keep_features:
+                kept.append(f.reshape(f.shape[0], -1).clone())
     except Exception as e:                                # noqa: BLE001 -- re-raised below, on EVERY rank
         err = e
     # A rank whose image loop failed (an unreadable file, a directory of ragged sizes, a dead decode worker) must not leave
@@ -288,9 +302,12 @@ def calculate_activation_statistics(images, model, batch_size=64, dims=2048, cud
     mu, sigma = stats.finalize()
     if verbose:
         print(" done")
-    if return_device:
-        return mu, sigma
-    return mu.cpu().numpy(), sigma.cpu().numpy()
+    if not return_device:
+        mu, sigma = mu.cpu().numpy(), sigma.cpu().numpy()
+    if keep_features:
+        rows = torch.cat(kept) if kept else torch.empty((0, dims), dtype=torch.float32, device=engine.device)
+        return mu, sigma, tdist.all_gather_rows(rows)
+    return mu, sigma
 
 
 U8_CACHE_NAME = ".tise_u8_cache.npy"
@@ -343,17 +360,31 @@ def prefetch_png_ring(path, batch_size, num_workers=0):
         return loader
 
 
-def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers=8, u8_cache=False):
+def kid_features_of_npz(path):
+    """The ``features`` array of a statistics file (float32, n_used x dims, global walk order: what --kid --save-stats
+    stores beside mu and sigma).  KID needs the rows themselves; a {mu, sigma} file cannot serve it."""
+    with np.load(path, allow_pickle=True) as f:
+        if "features" not in f.files:
+            raise RuntimeError(f"{path}: no 'features' array in this statistics file, and --kid needs the feature rows; "
+                               "make the file with --kid --save-stats")
+        return np.ascontiguousarray(f["features"], dtype=np.float32)
+
+
+def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers=8, u8_cache=False, keep_features=False):
     """fid_score.py:199-220: an .npz holds (mu, sigma); a directory is walked and pushed through the net.
     ``u8_cache``: decode the directory ONCE into ``<path>/.tise_u8_cache.npy`` ((N,H,W,3) uint8, walk order) and feed
     later runs -- and every rank of a data-parallel run -- from it through a double-buffered pinned host->device
-    pipeline (img_data.U8CacheLoader) instead of PNG-decoding DataLoader workers."""
+    pipeline (img_data.U8CacheLoader) instead of PNG-decoding DataLoader workers.
+    ``keep_features`` (KID): a third value, the fp32 feature rows of the n_used images in global walk order -- a device tensor
+    from a directory, the ``features`` array of an .npz."""
     if path.endswith(".npz"):
         f = np.load(path, allow_pickle=True)              # :201-203
         m, s = f["mu"][:], f["sigma"][:]
         tag = str(f["network"]) if "network" in f.files else None
         f.close()
         check_stats_network(path, tag, getattr(model, "network", "torchvision"))
+        if keep_features:
+            return m, s, kid_features_of_npz(path)
         return m, s
     files = img_data.get_filenames(path)                  # os.walk order (img_data.py:27-35)
     rank, world, _ = tdist.env_world()
@@ -379,7 +410,7 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         group = device_batch_images(batch_size, int(np.prod(shape[1:]))) // batch_size
         loader = img_data.U8CacheLoader(cache, batch_size, engine.device, rows=(lo * batch_size, hi * batch_size), group=group)
         t0 = time.perf_counter()
-        out = calculate_activation_statistics(loader, model, batch_size, dims, cuda)
+        out = calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
         wall = time.perf_counter() - t0
         n_img = len(loader) * batch_size
         if tdist.is_main() and n_img:
@@ -405,7 +436,7 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         loader = jpeg_feed.JpegFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers)
         t0 = time.perf_counter()
         try:
-            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda)
+            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
         finally:
             loader.close()
         if tdist.is_main():
@@ -420,7 +451,7 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         loader = crop_feed.CropFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers)
         t0 = time.perf_counter()
         try:
-            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda)
+            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
         finally:
             loader.close()
         if tdist.is_main():
@@ -446,7 +477,7 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         thr0 = cfs_throttle()
         err, out = None, None
         try:
-            out = calculate_activation_statistics(loader if loader is not None else [], model, batch_size, dims, cuda)
+            out = calculate_activation_statistics(loader if loader is not None else [], model, batch_size, dims, cuda, keep_features=keep_features)
         except png_ring.RaggedImages as e:
             if world > 1:
                 raise RuntimeError(f"--png-feed ring under torchrun needs images of one size ({e}); use --png-feed dataloader") from e
@@ -479,7 +510,7 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
                                              num_workers=dl_workers, collate_fn=img_data.collate_u8,
                                              pin_memory=True, worker_init_fn=img_data.worker_init)
     t0 = time.perf_counter()
-    out = calculate_activation_statistics(dataloader, model, batch_size, dims, cuda)
+    out = calculate_activation_statistics(dataloader, model, batch_size, dims, cuda, keep_features=keep_features)
     wall = time.perf_counter() - t0
     if tdist.is_main() and len(shard):
         print(f"[tise] png feed: {len(shard)} images in {wall:.2f} s ({len(shard) / wall:.0f} images/s on this rank, {dl_workers} "
@@ -500,8 +531,12 @@ def check_stats_network(path, tag, network):
         raise RuntimeError(f"{path}: statistics of network {tag!r}, this run uses --network {network}")
 
 
-def save_stats_npz(path, mu, sigma, network="torchvision"):
-    np.savez(path, mu=np.asarray(mu), sigma=np.asarray(sigma), **stats_network_tag(network))
+def save_stats_npz(path, mu, sigma, network="torchvision", features=None):
+    """``features`` (only under --kid): the float32 rows KID needs, beside mu and sigma; without it the file is exactly
+    {mu, sigma[, network]}."""
+    extra = {} if features is None else {"features": np.ascontiguousarray(
+        features.cpu().numpy() if isinstance(features, torch.Tensor) else features, dtype=np.float32)}
+    np.savez(path, mu=np.asarray(mu), sigma=np.asarray(sigma), **stats_network_tag(network), **extra)
 
 
 def _build_model(dims, weights, num_classes, seed, network="torchvision"):
@@ -539,9 +574,39 @@ def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_c
                               save_stats="", num_workers=8, u8_cache=False, network="torchvision"):
     """Calculates the FID of two paths (fid_score.py:223-238).  ``weights=None`` = seeded stand-in parameters (the
     CLI only allows that behind --synthetic-weights)."""
+    return _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache,
+                                network, None)[0]
+
+
+def calculate_fid_and_kid_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0, save_stats="",
+                                      num_workers=8, u8_cache=False, network="torchvision", subsets=100, subset_size=1000,
+                                      kid_seed=0):
+    """FID and KID of two paths from ONE pass over each directory -> (fid, (kid_mean, kid_std)).  The pool3 rows of the images
+    FID uses are kept on the device (8 KB per image) and handed to kid.kid_from_features; ``save_stats`` then also stores them
+    (``features``), and an .npz path must hold them.  ``kid_seed`` seeds the subsets (``seed`` is the stand-in weights')."""
+    return _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache,
+                                network, {"subsets": subsets, "subset_size": subset_size, "seed": kid_seed})
+
+
+def calculate_kid_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0, save_stats="",
+                              num_workers=8, u8_cache=False, network="torchvision", subsets=100, subset_size=1000, kid_seed=0):
+    """Kernel Inception Distance of two paths -> (mean, std) over the subsets (kid.py; std is NaN for subset_size = 0)."""
+    return calculate_fid_and_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers,
+                                             u8_cache, network, subsets, subset_size, kid_seed)[1]
+
+
+def _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache, network,
+                         kid_args):
+    """calculate_fid_given_paths; with ``kid_args`` (subsets, subset_size, seed) the feature rows of both sides are retained and
+    the KID is evaluated after the Frechet distance -> (fid, None | (mean, std)).  Without it: the launches of the FID alone."""
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError("Invalid path: %s" % p)    # :225-227
+    keep = kid_args is not None
+    if keep:
+        for p in paths:                                   # a {mu, sigma} file cannot serve KID: say so before anything is computed
+            if p.endswith(".npz"):
+                kid_features_of_npz(p)
     _check_cuda(cuda)
     if not u8_cache:
         # the decode workers of the first directory start now: PNG decode overlaps building the model (weights, BatchNorm
@@ -561,7 +626,7 @@ def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_c
     with _own_model(dims, weights, num_classes, seed, network) as model:
         _engine_for(model, dims)                               # fold BatchNorm, pack the split weights, load the code objects
         t = _timing("model + engine ready", t)
-        m1, s1 = _compute_statistics_of_path(paths[0], model, batch_size, dims, cuda, num_workers, u8_cache)
+        m1, s1, *f1 = _compute_statistics_of_path(paths[0], model, batch_size, dims, cuda, num_workers, u8_cache, keep)
         t = _timing("first side done", t)
         # the first side's covariance is complete: factor it on a side stream while the second side's images are decoded
         # and pushed through the network (Tr sqrtm(S1 S2) is symmetric in its arguments; csrc/frechet.hip)
@@ -570,26 +635,35 @@ def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_c
         use_pf = tuple(np.shape(s1)) == (dims, dims) and tuple(np.shape(m1)) == (dims,)
         if use_pf:
             solver.prefactor(torch.as_tensor(np.ascontiguousarray(s1, dtype=np.float64), device=dev))
-        m2, s2 = _compute_statistics_of_path(paths[1], model, batch_size, dims, cuda, num_workers, u8_cache)
+        m2, s2, *f2 = _compute_statistics_of_path(paths[1], model, batch_size, dims, cuda, num_workers, u8_cache, keep)
         t = _timing("second side done", t)
         if save_stats and tdist.is_main():
-            save_stats_npz(save_stats, m2, s2, network)
-        if not use_pf or np.shape(m1) != np.shape(m2) or np.shape(s1) != np.shape(s2):
-            return calculate_frechet_distance(m1, s1, m2, s2)     # generic path (shape asserts :149-150 included)
-        try:
-            res = solver.distance_prefactored(np.atleast_1d(m1), np.atleast_1d(m2), np.atleast_2d(s2))
-        except _lib.TiseStatusError:
-            # the factor is gone: the process-wide solver of this (dims, device) served another distance / factorisation
-            # between prefactor() and here (a model's forward hook, a second thread).  The one-call form needs nothing kept.
-            return calculate_frechet_distance(m1, s1, m2, s2)
-        if res["flags"] & _lib.TISE_FLAG_NONFINITE:          # :156-160 (eps retry) lives in calculate_frechet_distance
-            return calculate_frechet_distance(m1, s1, m2, s2)
-        calculate_frechet_distance.last_result = res
-        return np.float64(res["fid"])
+            save_stats_npz(save_stats, m2, s2, network, f2[0] if keep else None)
+
+        def solve():
+            if not use_pf or np.shape(m1) != np.shape(m2) or np.shape(s1) != np.shape(s2):
+                return calculate_frechet_distance(m1, s1, m2, s2)     # generic path (shape asserts :149-150 included)
+            try:
+                res = solver.distance_prefactored(np.atleast_1d(m1), np.atleast_1d(m2), np.atleast_2d(s2))
+            except _lib.TiseStatusError:
+                # the factor is gone: the process-wide solver of this (dims, device) served another distance / factorisation
+                # between prefactor() and here (a model's forward hook, a second thread).  The one-call form needs nothing kept.
+                return calculate_frechet_distance(m1, s1, m2, s2)
+            if res["flags"] & _lib.TISE_FLAG_NONFINITE:          # :156-160 (eps retry) lives in calculate_frechet_distance
+                return calculate_frechet_distance(m1, s1, m2, s2)
+            calculate_frechet_distance.last_result = res
+            return np.float64(res["fid"])
+
+        fid = solve()
+        if not keep:
+            return fid, None
+        # every rank holds the same rows in the same order (all_gather_rows) and evaluates the (cheap) KID itself: no broadcast
+        from . import kid
+        return fid, kid.kid_from_features(f1[0], f2[0], kid_args["subsets"], kid_args["subset_size"], kid_args["seed"])
 
 
 def save_statistics_of_path(path, out_npz, batch_size, cuda, dims, weights=None, num_classes=None, seed=0,
-                            num_workers=8, u8_cache=False, network="torchvision"):
+                            num_workers=8, u8_cache=False, network="torchvision", keep_features=False):
     """STATS-ONLY mode: the step BEFORE the reference path -- write the ``.npz {mu, sigma}`` that
     ``_compute_statistics_of_path`` (fid_score.py:200-203) reads (the reference ships such files,
     download_evaluation_data.py:11-12, but no script that makes them).  No Frechet distance is solved."""
@@ -599,9 +673,9 @@ def save_statistics_of_path(path, out_npz, batch_size, cuda, dims, weights=None,
     if not u8_cache:
         prefetch_png_ring(path, batch_size, num_workers)   # decode overlaps building the model
     with _own_model(dims, weights, num_classes, seed, network) as model:
-        mu, sigma = _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers, u8_cache)
+        mu, sigma, *feats = _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers, u8_cache, keep_features)
         if tdist.is_main():
-            save_stats_npz(out_npz, mu, sigma, network)
+            save_stats_npz(out_npz, mu, sigma, network, feats[0] if keep_features else None)   # --kid: the rows KID needs, too
         return mu, sigma
 
 
@@ -616,9 +690,10 @@ def class_of_crop(filename):
     return parts[1]
 
 
-def _class_statistics(path, model, batch_size, dims, num_workers, owner=None):
+def _class_statistics(path, model, batch_size, dims, num_workers, owner=None, keep_features=False):
     """One pass over a crop directory -> {class: StatsAccumulator}.  Every crop is used (no drop-last: a class is
-    not a DataLoader); batches are formed over the walk-ordered list and each row is folded into its class."""
+    not a DataLoader); batches are formed over the walk-ordered list and each row is folded into its class.
+    ``keep_features`` (per-class KID): -> (accumulators, the fp32 rows of ALL crops in walk order, on every rank)."""
     files = img_data.get_filenames(path)
     classes = [class_of_crop(f) for f in files]
     names = sorted(set(classes))
@@ -647,6 +722,7 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None):
     index_of = {c: i for i, c in enumerate(names)}
     acc_list = [accs[c] for c in names]
     kept, kept_rows = [], 0
+    walk = []
     base = lo
 
     def flush():
@@ -666,6 +742,8 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None):
     for batch in coalesce_batches(loader, engine.device, device_batch_images(batch_size)):
         feats = _forward_batch(engine, model, batch)
         kept.append(feats)
+        if keep_features:
+            walk.append(feats.clone())
         kept_rows += feats.shape[0]
         base += feats.shape[0]
         if kept_rows >= FLUSH_ROWS:
@@ -695,6 +773,10 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None):
     if parked:
         torch.cuda.current_stream(engine.device).synchronize()
         parked.clear()
+    if keep_features:
+        # shards are contiguous ranges of the walk (shard_range), so the gathered rows are the one-process walk order
+        rows = torch.cat(walk) if walk else torch.empty((0, dims), dtype=torch.float32, device=engine.device)
+        return accs, tdist.all_gather_rows(rows)
     return accs
 
 
@@ -703,6 +785,28 @@ def calculate_per_class_fid(paths, batch_size, cuda, dims, weights=None, num_cla
     """EXTENSION (BASELINE configs[4]; the reference computes ONE O-FID over all crops): a Frechet
     distance per object class.  Returns (OrderedDict class -> fid, skipped) where ``skipped`` lists classes with
     fewer than ``min_count`` crops on either side (covariance undefined)."""
+    return _per_class(paths, batch_size, cuda, dims, weights, num_classes, seed, num_workers, min_count, network, False)[:2]
+
+
+def calculate_per_class_kid(paths, batch_size, cuda, dims, weights=None, num_classes=80, seed=0, num_workers=8,
+                            min_count=2, network="torchvision"):
+    """One full-set KID per object class (kid.per_class_kid: unbiased, so classes with different crop counts compare).
+    Returns (OrderedDict class -> kid, skipped) like calculate_per_class_fid."""
+    return _per_class(paths, batch_size, cuda, dims, weights, num_classes, seed, num_workers, min_count, network, True)[2:]
+
+
+def _class_sorted(feats_walk, path, names):
+    """Walk-ordered rows of a crop directory -> (rows sorted by class, walk order kept inside a class; offsets over ``names``)."""
+    index_of = {c: i for i, c in enumerate(names)}
+    cidx = np.array([index_of[class_of_crop(f)] for f in img_data.get_filenames(path)], dtype=np.int64)
+    order = np.argsort(cidx, kind="stable")
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(cidx, minlength=len(names)))]).astype(np.int64)
+    return feats_walk.index_select(0, torch.from_numpy(order).to(feats_walk.device)), offsets
+
+
+def _per_class(paths, batch_size, cuda, dims, weights, num_classes, seed, num_workers, min_count, network, with_kid):
+    """The per-class pass: -> (fids, skipped, kids | None, kid_skipped | None).  ``with_kid`` retains the crops' rows during
+    the same pass (all-gathered in walk order under torchrun: every rank evaluates the 80 small groups itself)."""
     from collections import OrderedDict
     for p in paths:
         if not os.path.isdir(p):
@@ -715,8 +819,10 @@ def calculate_per_class_fid(paths, batch_size, cuda, dims, weights=None, num_cla
         names = sorted(present[0] | present[1])
         world, me = tdist.world_size(), tdist.rank()
         owner = tdist.class_owners(names, world)
-        a1 = _class_statistics(paths[0], model, batch_size, dims, num_workers, owner)
-        a2 = _class_statistics(paths[1], model, batch_size, dims, num_workers, owner)
+        a1 = _class_statistics(paths[0], model, batch_size, dims, num_workers, owner, with_kid)
+        a2 = _class_statistics(paths[1], model, batch_size, dims, num_workers, owner, with_kid)
+        if with_kid:
+            (a1, w1), (a2, w2) = a1, a2
         dev = torch.device("cuda", torch.cuda.current_device())
         mine = []
         status = torch.zeros((len(names), 3), dtype=torch.float64, device=dev)       # [fid, solved, skipped] per class
@@ -738,7 +844,12 @@ def calculate_per_class_fid(paths, batch_size, cuda, dims, weights=None, num_cla
                 out[c] = float(st[i, 0])
             else:
                 skipped.append(c)
-        return out, skipped
+        if not with_kid:
+            return out, skipped, None, None
+        from . import kid
+        kids, kid_skipped = kid.per_class_kid(*_class_sorted(w1, paths[0], names), *_class_sorted(w2, paths[1], names), names,
+                                              min_count)
+        return out, skipped, kids, kid_skipped
 
 
 _CLASS_SOLVERS = {}
@@ -826,17 +937,18 @@ def main(argv=None):
             print([args.path2])
         mu, sigma = run_with_exact_fallback(lambda: save_statistics_of_path(
             args.path2, args.save_stats, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.num_workers,
-            args.u8_cache, args.network), "the statistics pass")
+            args.u8_cache, args.network, args.kid), "the statistics pass")
         if tdist.is_main():
             print(f"statistics of {args.path2} -> {args.save_stats}{tag}")
         return None
     paths = [args.path1, args.path2]
     if tdist.is_main():
         print(paths)                                                   # :247
+    klabel = "O-KID" if args.label == "O-FID" else "KID"
     if args.per_class:
-        per, skipped = run_with_exact_fallback(lambda: calculate_per_class_fid(
-            paths, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.num_workers,
-            network=args.network), "the per-class FID")
+        per, skipped, kids, kid_skipped = run_with_exact_fallback(lambda: _per_class(
+            paths, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.num_workers, 2,
+            args.network, args.kid), "the per-class FID")
         mean = float(np.mean(list(per.values()))) if per else float("nan")
         if tdist.is_main():
             lines = [f"{args.label}[{c}]: {v}{tag}" for c, v in per.items()]
@@ -847,15 +959,33 @@ def main(argv=None):
                 with open(args.saved_file, "w") as f:
                     f.write("\n".join(lines))
             print("\n".join(lines))
+            if args.kid:
+                kmean = float(np.mean(list(kids.values()))) if kids else float("nan")
+                klines = [f"O-KID[{c}]: {v}{tag}" for c, v in kids.items()]
+                klines.append(f"O-KID (mean of {len(kids)} classes): {kmean}{tag}")
+                if kid_skipped:
+                    klines.append("skipped (fewer than 2 crops on a side): " + ", ".join(kid_skipped))
+                if args.kid_saved_file:
+                    with open(args.kid_saved_file, "w") as f:
+                        f.write("\n".join(klines))
+                print("\n".join(klines))
         return per
-    fid_value = run_with_exact_fallback(lambda: calculate_fid_given_paths(
+    kid_args = {"subsets": args.kid_subsets, "subset_size": args.kid_subset_size, "seed": args.kid_seed} if args.kid else None
+    fid_value, kid_value = run_with_exact_fallback(lambda: _fid_kid_given_paths(
         paths, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.save_stats, args.num_workers,
-        args.u8_cache, args.network), "the FID").item()
+        args.u8_cache, args.network, kid_args), "the FID")
+    fid_value = fid_value.item()
     if tdist.is_main():
         if args.saved_file:
             with open(args.saved_file, "w") as f:
                 f.write(f"{args.label}: {fid_value}{tag}")             # :251-252 (no trailing newline)
         print(f"{args.label}: {fid_value}{tag}")                       # :254
+        if args.kid:
+            kline = f"{klabel}: {kid_value[0]} +- {kid_value[1]}{tag}"
+            if args.kid_saved_file:
+                with open(args.kid_saved_file, "w") as f:
+                    f.write(kline)                                     # no trailing newline, like --saved_file
+            print(kline)
     return fid_value
 
 
