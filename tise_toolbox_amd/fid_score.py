@@ -428,36 +428,30 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         return out
     shard, _ = tdist.shard_files(files, batch_size, rank, world)       # drop_last=True (:215-217), whole batches
     num_workers = _num_workers(num_workers, world)
+    def through_arena_feed(loader, remember_as):
+        t0 = time.perf_counter()
+        try:
+            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
+        finally:
+            loader.close()
+        if tdist.is_main():
+            print(loader.feed_line(time.perf_counter() - t0), file=sys.stderr)
+        setattr(_compute_statistics_of_path, remember_as, loader)
+        return out
     if _native_jpeg_shard(shard):
         # decode threads -> page-locked coefficient arenas -> side-stream H2D -> IDCT / upsampling / colour on the GPU
         # (jpeg_feed.py).  Items are loader batches as the DataLoader's collate_u8 makes them (dense or ragged), so the
         # statistics below are the DataLoader path's to the last bit; images may differ in size, under torchrun as well
         from . import jpeg_feed
-        loader = jpeg_feed.JpegFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers)
-        t0 = time.perf_counter()
-        try:
-            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
-        finally:
-            loader.close()
-        if tdist.is_main():
-            print(loader.feed_line(time.perf_counter() - t0), file=sys.stderr)
-        _compute_statistics_of_path.last_jpeg_loader = loader
-        return out
+        return through_arena_feed(jpeg_feed.JpegFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers),
+                                  "last_jpeg_loader")
     if _CROP_FEED["mode"] == "native" and shard:
         # --crop-feed native: decode threads -> page-locked arenas of packed inflate-only slots -> side-stream H2D -> the row
         # filters on the GPU (crop_feed.py); PNG directories of any sizes, under torchrun as well.  Items are loader batches
         # as the DataLoader's collate_u8 makes them, so the statistics are the --png-feed dataloader path's to the last bit
         from . import crop_feed
-        loader = crop_feed.CropFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers)
-        t0 = time.perf_counter()
-        try:
-            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
-        finally:
-            loader.close()
-        if tdist.is_main():
-            print(loader.feed_line(time.perf_counter() - t0), file=sys.stderr)
-        _compute_statistics_of_path.last_crop_loader = loader
-        return out
+        return through_arena_feed(crop_feed.CropFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers),
+                                  "last_crop_loader")
     if _PNG_FEED["mode"] == "ring":
         # decode workers -> shared page-locked ring -> side-stream H2D (png_ring.py).  A directory with images of different
         # sizes: one process falls back to the DataLoader path below; under torchrun the rank that meets the odd file raises
