@@ -96,21 +96,26 @@ __global__ __launch_bounds__(256) void cosine_top1_kernel(const T* __restrict__ 
         if (lane == 0) lg[j] = logit;
         m = fmaxf(m, logit);
     }
-    // softmax over the c stored logits (fp32 arithmetic, output rounded to the dtype), first maximum of the OUTPUT
+    // softmax over the c stored logits (output rounded to the dtype), first maximum of the OUTPUT.  logit - max is taken
+    // in fp64, where it is one correctly rounded operation of two exact numbers: an fp32 difference of two fp32 logits
+    // is rounded again, by up to 2^-24 of the larger one, and exp() carries that into the probability
     double s = 0.0;
-    for (int j = lane; j < c; j += 64) s += exp((double)(lg[j] - m));
+    for (int j = lane; j < c; j += 64) s += exp((double)lg[j] - (double)m);
     s = wave_sum(s);
     const float pmax = rnd<T>((float)(1.0 / s));
     int first = 0x7fffffff;
     for (int j = lane; j < c; j += 64) {
-        const float pj = rnd<T>((float)(exp((double)(lg[j] - m)) / s));
+        const float pj = rnd<T>((float)(exp((double)lg[j] - (double)m) / s));
         if (pj == pmax && j < first) first = j;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off, 64));
+    // A NaN logit, or one at +inf (inf - inf), makes every probability NaN: no pj equals pmax.  np.argmax of an all-NaN
+    // vector is 0, so the reference counts such an item as retrieved; p0 is NaN, which PA's `> 0.6` rejects.
+    if (first == 0x7fffffff) first = 0;
     if (lane == 0) {
         top1[item] = first;
-        if (p0) p0[item] = rnd<T>((float)(exp((double)(lg[0] - m)) / s));
+        if (p0) p0[item] = rnd<T>((float)(exp((double)lg[0] - (double)m) / s));
     }
 }
 

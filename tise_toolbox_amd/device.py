@@ -721,6 +721,9 @@ def cosine_top1(img_emb, txt_emb, txt_index=None, normalize=True, logit_scale=10
 
     img_emb (n, d), txt_emb (rows, d): fp32 or fp16 device tensors; txt_index (n, c) int32 rows of txt_emb per item,
     candidate 0 = true caption (None: txt_emb is (n*c, d), item-major).  Returns (top1 int32 (n,), p0 fp32 (n,) or None).
+    An item with a non-finite logit gets what the reference's np.argmax of all-NaN probabilities gives: top1 0, p0 NaN.
+    Raises ValueError, before anything is launched, when txt_index names a row outside the table (one min/max
+    reduction and a host sync per call) or when the contiguous form's table does not hold exactly n * c rows.
     """
     _require_cuda(img_emb, txt_emb, txt_index)
     assert img_emb.dim() == 2 and txt_emb.dim() == 2 and img_emb.shape[1] == txt_emb.shape[1]
@@ -731,9 +734,14 @@ def cosine_top1(img_emb, txt_emb, txt_index=None, normalize=True, logit_scale=10
         assert txt_index.dtype == torch.int32 and txt_index.dim() == 2 and txt_index.shape[0] == n
         txt_index = txt_index.contiguous()
         c = txt_index.shape[1]
+        if txt_index.numel():
+            lo, hi = (int(v) for v in torch.aminmax(txt_index))
+            if lo < 0 or hi >= txt_emb.shape[0]:
+                raise ValueError(f"txt_index holds values in [{lo}, {hi}]: outside the {txt_emb.shape[0]} rows of txt_emb")
     else:
-        assert txt_emb.shape[0] % max(n, 1) == 0
         c = txt_emb.shape[0] // max(n, 1)
+        if n and (c == 0 or c * n != txt_emb.shape[0]):
+            raise ValueError(f"txt_emb has {txt_emb.shape[0]} rows: not n * c for n = {n} items")
     top1 = torch.empty(n, dtype=torch.int32, device=img_emb.device)
     p0 = torch.empty(n, dtype=torch.float32, device=img_emb.device) if want_p0 else None
     _lib.call("tise_cosine_top1", _ptr(img_emb), _ptr(txt_emb), _ptr(txt_index) if txt_index is not None else None,
