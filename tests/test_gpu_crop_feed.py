@@ -292,7 +292,7 @@ def test_clis_give_the_dataloader_routes_values(cuda_device, tmp_path, capfd):
     --per-class with the flag unset (native) == --crop-feed dataloader for every class; O-IS identical on both routes; two
     ranks on this GPU reproduce the one-process per-class values (as test_ragged_crops_one_trunk_pass_and_per_class_fid)."""
     from tests.test_gpu_pipeline import _run_ranks
-    from tise_toolbox_amd import fid_score, object_centric_inception_score as ois
+    from tise_toolbox_amd import feeds, fid_score, object_centric_inception_score as ois
     ref, gen = _crop_dirs(tmp_path)
     base = ["--batch-size", "8", "--path1", ref, "--path2", gen, "--label", "O-FID", "--num-classes", "80", "--num-workers", "0",
             "--synthetic-weights"]
@@ -300,7 +300,8 @@ def test_clis_give_the_dataloader_routes_values(cuda_device, tmp_path, capfd):
     a = fid_score.main(base + ["--crop-feed", "native"])
     err = capfd.readouterr().err
     assert err.count("[tise] crop feed:") == 2 and "falling back" not in err, err
-    ld = fid_score._compute_statistics_of_path.last_crop_loader
+    assert feeds.last.kind == "crop"
+    ld = feeds.last.loader
     assert (ld.native, ld.pillow, ld.alone) == (40, 0, 0)                                   # 46 files, batch 8, drop-last
     b = fid_score.main(base + ["--png-feed", "dataloader"])
     assert "crop feed" not in capfd.readouterr().err
@@ -310,7 +311,8 @@ def test_clis_give_the_dataloader_routes_values(cuda_device, tmp_path, capfd):
     pa = fid_score.main(base + ["--per-class"])
     err = capfd.readouterr().err
     assert err.count("[tise] crop feed:") == 2, err
-    ld = fid_score._class_statistics.last_crop_loader
+    assert feeds.last.kind == "crop"
+    ld = feeds.last.loader
     assert (ld.native, ld.pillow) == (46, 0)                                                # every crop is used
     pb = fid_score.main(base + ["--per-class", "--crop-feed", "dataloader"])
     assert "crop feed" not in capfd.readouterr().err
@@ -320,7 +322,7 @@ def test_clis_give_the_dataloader_routes_values(cuda_device, tmp_path, capfd):
     # O-IS
     ia = ois.main(["--image_dir", gen, "--gpu_id", "0", "--synthetic-weights"])
     assert "[tise] crop feed:" in capfd.readouterr().err
-    assert (ois.inception_score.last_crop_loader.native, ois.inception_score.last_crop_loader.pillow) == (46, 0)
+    assert feeds.last.kind == "crop" and (feeds.last.loader.native, feeds.last.loader.pillow) == (46, 0)
     ib = ois.main(["--image_dir", gen, "--gpu_id", "0", "--synthetic-weights", "--crop-feed", "dataloader"])
     assert "crop feed" not in capfd.readouterr().err
     ic = ois.main(["--image_dir", gen, "--gpu_id", "0", "--synthetic-weights", "--crop-feed", "native"])

@@ -424,15 +424,14 @@ def _write_set(root, sizes, n, seed=0):
 
 
 def _fid_stats(path, batch_size, jpeg_feed, png_feed="ring"):
-    from tise_toolbox_amd import fid_score
-    fid_score._JPEG_FEED["mode"], fid_score._PNG_FEED["mode"] = jpeg_feed, png_feed
-    fid_score._compute_statistics_of_path.last_jpeg_loader = None
+    from tise_toolbox_amd import feeds, fid_score
+    fid_score._FEED = feeds.Options(png_feed=png_feed, jpeg_feed=jpeg_feed)
     try:
         with fid_score._own_model(2048, None, None, 0) as model:
             mu, sigma = fid_score._compute_statistics_of_path(path, model, batch_size, 2048, True, num_workers=4)
-        return np.asarray(mu), np.asarray(sigma), fid_score._compute_statistics_of_path.last_jpeg_loader
+        return np.asarray(mu), np.asarray(sigma), feeds.last.loader if feeds.last.kind == "jpeg" else None
     finally:
-        fid_score._JPEG_FEED["mode"], fid_score._PNG_FEED["mode"] = None, "ring"
+        fid_score._FEED = feeds.Options()
 
 
 @pytest.mark.gpu
@@ -445,15 +444,14 @@ def test_fid_statistics_and_is_of_one_size_set_equal_the_pillow_path_bit_for_bit
     assert none is None
     print("one size: max |dmu|", np.abs(mu_n - mu_p).max(), "max |dsigma|", np.abs(sig_n - sig_p).max())
     assert np.array_equal(mu_n, mu_p) and np.array_equal(sig_n, sig_p)
-    from tise_toolbox_amd import inception_score as isc
+    from tise_toolbox_amd import feeds, inception_score as isc
     from tise_toolbox_amd import img_data
     files = img_data.get_filenames(root)
     res = {}
     for mode in ("native", "pillow"):
         isc.configure(jpeg_feed=mode, batch_size=50)
-        isc.feed_images.last_jpeg_loader = None
         res[mode] = isc.get_inception_score(files, splits=10)
-        assert (isc.feed_images.last_jpeg_loader is not None) == (mode == "native")
+        assert (feeds.last.kind == "jpeg") == (mode == "native")
     isc.configure(jpeg_feed=None)
     print("IS*", res)
     assert res["native"] == res["pillow"]

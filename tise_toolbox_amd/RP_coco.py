@@ -25,7 +25,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, clip_model, device, dist as tdist, img_data, weights as tweights
+from . import _lib, clip_model, device, dist as tdist, feeds, weights as tweights
 
 
 def parse_args(argv=None):
@@ -172,28 +172,17 @@ def embed_paths(model, paths, dev, batch, workers=0, feed="ring", convert_first=
     preprocess (``preprocess(Image.open(p).convert("RGB"))``: what the ring's workers do); PA.py:34 does not
     (``preprocess(Image.open(p))``: clip resizes first and Pillow resamples RGBA premultiplied), so there only plain RGB files
     may take the ring.  Files of different sizes (or, for PA, not plain RGB) take the DataLoader path."""
-    from . import png_ring
     out = []
 
-    def consume(x):
-        f = model.encode_image(x.half())
-        out.append(f / f.norm(dim=-1, keepdim=True))
-    workers = int(workers) if workers and int(workers) > 0 else png_ring.auto_workers(tdist.world_size())
-    if feed == "ring" and len(paths):
-        ring = png_ring.PngRingLoader(paths, 1, dev, group=batch, workers=workers, rgb_only=not convert_first)
-        try:
-            for u8 in ring:
-                consume(clip_model.preprocess_device(u8))
-            return torch.cat(out).contiguous()
-        except png_ring.RaggedImages as e:
-            print(f"[tise] png feed: {e}; falling back to the DataLoader path", file=sys.stderr)
-            out.clear()
-        finally:
-            ring.close()
-    loader = torch.utils.data.DataLoader(_Paths(paths, convert_first), batch_size=batch, shuffle=False, num_workers=min(32, workers),
-                                         worker_init_fn=img_data.worker_init)
-    for x in loader:
-        consume(x.to(dev))
+    def consume(loader):
+        out.clear()                                           # the DataLoader pass after a ring that met an odd file starts afresh
+        for x in loader:
+            # the ring delivers uint8 (clip's preprocess on the device), the DataLoader's workers preprocessed fp32
+            f = model.encode_image((clip_model.preprocess_device(x) if x.dtype == torch.uint8 else x.to(dev)).half())
+            out.append(f / f.norm(dim=-1, keepdim=True))
+    feeds.run(feeds.CLIP, paths, feeds.Options(png_feed=feed, num_workers=workers), consume, dev, batch, tdist.world_size(),
+              loader_args={"ring": {"batch_size": 1, "group": batch, "rgb_only": not convert_first},
+                           "dataloader": {"dataset": _Paths(paths, convert_first), "pin_memory": False, "collate": None}})
     return torch.cat(out).contiguous() if out else torch.empty((0, 512), dtype=torch.float16, device=dev)
 
 

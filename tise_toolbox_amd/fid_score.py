@@ -32,12 +32,12 @@ import time
 _T_IMPORT0 = time.time()
 import warnings
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
+from dataclasses import replace
 
 import numpy as np
 import torch
-import torch.utils.data
 
-from . import _lib, device, dist as tdist, img_data, weights as tweights
+from . import _lib, device, dist as tdist, feeds, img_data, weights as tweights
 from .engine import (RealismEngine, coalesce_batches, coalesce_u8, device_batch_images, frechet_solver, require_gpu,
                      run_with_exact_fallback)
 from .inception import NETWORK_CLASSES, NETWORKS, InceptionV3
@@ -313,51 +313,12 @@ def calculate_activation_statistics(images, model, batch_size=64, dims=2048, cud
 U8_CACHE_NAME = ".tise_u8_cache.npy"
 
 
-_PNG_FEED = {"mode": "ring"}        # --png-feed
-_JPEG_FEED = {"mode": None}         # --jpeg-feed (None: native for ragged JPEG directories, pillow for directories of one size)
-_CROP_FEED = {"mode": None}         # --crop-feed (None: native for --per-class when the shard's first file is a native-subset PNG; plain directories only on request)
-_RING_PREFETCH = {}                  # directory -> PngRingLoader whose workers are already decoding (started before the model was built)
-_RING_LOCK = __import__("threading").Lock()   # the second directory's prefetch is started from the first loader's feeder thread
-
-
-def _native_jpeg_shard(shard):
-    """--jpeg-feed native applies: the shard's first file probes as a JPEG of the native subset (and --png-feed was not
-    turned to the DataLoader)."""
-    if _PNG_FEED["mode"] != "ring" or not shard:
-        return False
-    from . import jpeg_feed
-    return jpeg_feed.use_native(shard, _JPEG_FEED["mode"])
-
-
-def _num_workers(num_workers, world=1):
-    from . import png_ring
-    return int(num_workers) if num_workers and int(num_workers) > 0 else png_ring.auto_workers(world)
-
-
-def _shard_of_path(path, batch_size):
-    files = img_data.get_filenames(path)                  # os.walk order (img_data.py:27-35)
-    rank, world, _ = tdist.env_world()
-    shard, _ = tdist.shard_files(files, batch_size, rank, world)       # drop_last=True (:215-217), whole batches
-    return shard, world
+_FEED = feeds.Options()             # --png-feed / --jpeg-feed / --crop-feed of this process (main sets them; --num-workers travels as an argument)
 
 
 def prefetch_png_ring(path, batch_size, num_workers=0):
-    """Start the decode workers of an image directory NOW (before the model is built / while the other side is still in
-    the network): _compute_statistics_of_path picks the running loader up.  No GPU call is made here."""
-    from . import png_ring
-    if _PNG_FEED["mode"] != "ring" or _CROP_FEED["mode"] == "native" or path.endswith(".npz") or not os.path.isdir(path):
-        return None
-    with _RING_LOCK:
-        if path in _RING_PREFETCH:
-            return _RING_PREFETCH[path]
-        shard, world = _shard_of_path(path, batch_size)
-        if not shard or _native_jpeg_shard(shard):
-            return None
-        group = device_batch_images(batch_size) // batch_size
-        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_initialized() else torch.device("cuda", tdist.env_world()[2])
-        loader = png_ring.PngRingLoader(shard, batch_size, dev, group=group, workers=_num_workers(num_workers, world), start=True)
-        _RING_PREFETCH[path] = loader
-        return loader
+    """feeds.prefetch_png_ring under this module's flags: the decode workers start NOW, _compute_statistics_of_path picks them up."""
+    return feeds.prefetch_png_ring(path, batch_size, replace(_FEED, num_workers=num_workers))
 
 
 def kid_features_of_npz(path):
@@ -388,128 +349,54 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         return m, s
     files = img_data.get_filenames(path)                  # os.walk order (img_data.py:27-35)
     rank, world, _ = tdist.env_world()
+    engine = _engine_for(model, dims)
+
+    def consume(loader):
+        return calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
     if u8_cache:
-        cache = os.path.join(path, U8_CACHE_NAME)          # the name holds neither "png" nor "jpg": never walked
-        # valid only for exactly these files as they are on disk now (relative path, size, mtime_ns of every file in
-        # walk order, img_data.files_fingerprint): images regenerated under the same names rebuild it
-        err = None
-        if tdist.is_main() and not img_data.u8_cache_is_current(cache, files, path):
-            try:
-                img_data.build_u8_cache(files, cache, _num_workers(num_workers, world), root=path)
-            except Exception as e:                         # the other ranks must not wait in a barrier for a cache that never comes
-                err = e
-        failed = tdist.any_rank(err is not None)
-        if err is not None:
-            raise err
-        if failed:
-            raise RuntimeError(f"--u8-cache: rank 0 could not build {cache}")
-        n_used = tdist.n_used_images(len(files), batch_size)
-        lo, hi = tdist.shard_range(n_used // batch_size, rank, world)
-        engine = _engine_for(model, dims)
-        shape = np.load(cache, mmap_mode="r").shape
-        group = device_batch_images(batch_size, int(np.prod(shape[1:]))) // batch_size
-        loader = img_data.U8CacheLoader(cache, batch_size, engine.device, rows=(lo * batch_size, hi * batch_size), group=group)
-        t0 = time.perf_counter()
-        out = calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
-        wall = time.perf_counter() - t0
-        n_img = len(loader) * batch_size
-        if tdist.is_main() and n_img:
-            steady = ""
-            sec = loader.steady_seconds()
-            if sec and n_img > loader.first_item_rows:
-                # without the first device batch (first-use costs of the process: code objects, allocator, resize plans):
-                # device events at the end of the first and of the last device batch's work (the host time at
-                # which the consumer came back for the second item still contained most of the first batch's device time)
-                rest = n_img - loader.first_item_rows
-                steady = f"; after the first device batch {rest / sec:.0f} images/s"
-            print(f"[tise] u8 cache feed: {n_img} images in {wall:.2f} s ({n_img / wall:.0f} images/s on this rank{steady}); host side "
-                  f"(page cache -> pinned buffer -> H2D enqueue) {loader.h2d_seconds:.2f} s, the rest is the device pipeline",
-                  file=sys.stderr)
-        return out
+        loader, line = _u8_cache_loader(path, files, batch_size, engine.device, num_workers, rank, world)
+        return feeds.session("u8cache", loader, consume, line)
+    # jpeg / crop: items are loader batches as the DataLoader's collate_u8 makes them (dense or ragged): the DataLoader path's statistics
+    # to the last bit, for images of any sizes.  ring: a ragged directory falls back to the DataLoader in one process; under torchrun the
+    # rank that meets the odd file raises inside calculate_activation_statistics, which agrees on the failure collectively (feeds.run)
     shard, _ = tdist.shard_files(files, batch_size, rank, world)       # drop_last=True (:215-217), whole batches
-    num_workers = _num_workers(num_workers, world)
-    def through_arena_feed(loader, remember_as):
-        t0 = time.perf_counter()
+    return feeds.run(feeds.FID, shard, replace(_FEED, num_workers=num_workers), consume, engine.device, batch_size, world, prefetch_key=path)
+
+
+def _u8_cache_loader(path, files, batch_size, dev, num_workers, rank, world):
+    """--u8-cache: (U8CacheLoader over this rank's rows of the cache, its feed line); rank 0 first builds a missing or stale cache."""
+    cache = os.path.join(path, U8_CACHE_NAME)              # the name holds neither "png" nor "jpg": never walked
+    # valid only for exactly these files as they are on disk now (relative path, size, mtime_ns of every file in
+    # walk order, img_data.files_fingerprint): images regenerated under the same names rebuild it
+    err = None
+    if tdist.is_main() and not img_data.u8_cache_is_current(cache, files, path):
         try:
-            out = calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
-        finally:
-            loader.close()
-        if tdist.is_main():
-            print(loader.feed_line(time.perf_counter() - t0), file=sys.stderr)
-        setattr(_compute_statistics_of_path, remember_as, loader)
-        return out
-    if _native_jpeg_shard(shard):
-        # decode threads -> page-locked coefficient arenas -> side-stream H2D -> IDCT / upsampling / colour on the GPU
-        # (jpeg_feed.py).  Items are loader batches as the DataLoader's collate_u8 makes them (dense or ragged), so the
-        # statistics below are the DataLoader path's to the last bit; images may differ in size, under torchrun as well
-        from . import jpeg_feed
-        return through_arena_feed(jpeg_feed.JpegFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers),
-                                  "last_jpeg_loader")
-    if _CROP_FEED["mode"] == "native" and shard:
-        # --crop-feed native: decode threads -> page-locked arenas of packed inflate-only slots -> side-stream H2D -> the row
-        # filters on the GPU (crop_feed.py); PNG directories of any sizes, under torchrun as well.  Items are loader batches
-        # as the DataLoader's collate_u8 makes them, so the statistics are the --png-feed dataloader path's to the last bit
-        from . import crop_feed
-        return through_arena_feed(crop_feed.CropFeedLoader(shard, batch_size, _engine_for(model, dims).device, workers=num_workers),
-                                  "last_crop_loader")
-    if _PNG_FEED["mode"] == "ring":
-        # decode workers -> shared page-locked ring -> side-stream H2D (png_ring.py).  A directory with images of different
-        # sizes: one process falls back to the DataLoader path below; under torchrun the rank that meets the odd file raises
-        # RaggedImages inside calculate_activation_statistics, which agrees on the failure collectively -- every rank raises
-        # (the others a generic RuntimeError) instead of waiting in the all-reduce
-        from . import png_ring
-        with _RING_LOCK:
-            loader = _RING_PREFETCH.pop(path, None)
-            if loader is None and shard:
-                engine = _engine_for(model, dims)
-                loader = png_ring.PngRingLoader(shard, batch_size, engine.device, group=device_batch_images(batch_size) // batch_size,
-                                                workers=num_workers, start=True)
-        if loader is not None:
-            loader.device = _engine_for(model, dims).device
-        t0 = time.perf_counter()
-        from .hostinfo import cfs_throttle
-        thr0 = cfs_throttle()
-        err, out = None, None
-        try:
-            out = calculate_activation_statistics(loader if loader is not None else [], model, batch_size, dims, cuda, keep_features=keep_features)
-        except png_ring.RaggedImages as e:
-            if world > 1:
-                raise RuntimeError(f"--png-feed ring under torchrun needs images of one size ({e}); use --png-feed dataloader") from e
+            img_data.build_u8_cache(files, cache, feeds.resolve_workers(num_workers, world), root=path)
+        except Exception as e:                             # the other ranks must not wait in a barrier for a cache that never comes
             err = e
-        finally:
-            if loader is not None:
-                loader.close()                             # stops and joins the feeder thread before the ring is unregistered
-        if err is None:
-            wall = time.perf_counter() - t0
-            if tdist.is_main() and len(shard):
-                sec = loader.steady_seconds()
-                steady = f"; after the first device batch {(len(shard) - loader.first_item_rows) / sec:.0f} images/s" if sec else ""
-                dec = f", all decoded {loader.decode_seconds:.2f} s after the workers started" if loader.decode_seconds else ""
-                thr1 = cfs_throttle()
-                if os.environ.get("TISE_ALLOC_TRACE") == "1":               # probe: how much of the loop went into hipMalloc (caching allocator misses)
-                    st = torch.cuda.memory_stats()
-                    dec += (f"; allocator: {st.get('num_device_alloc', 0)} device allocations, {st.get('reserved_bytes.all.peak', 0) / 2**30:.1f} GiB reserved, "
-                            f"{st.get('num_alloc_retries', 0)} retries")
-                dec += (f"; feeder waited {loader.wait_decode_seconds:.2f} s for decode, {loader.wait_buffer_seconds:.2f} s for a device buffer, "
-                        f"{loader.wait_copy_seconds + loader.enqueue_seconds:.2f} s on copies; cgroup CPU throttling during the loop: "
-                        f"{thr1[0] - thr0[0]} periods, {(thr1[1] - thr0[1]) / 1e3:.0f} ms")
-                print(f"[tise] png feed: {len(shard)} images in {wall:.2f} s ({len(shard) / wall:.0f} images/s on this rank{steady}; "
-                      f"{loader.workers} decode processes -> shared pinned ring{dec}; loader batch {batch_size}, device batch "
-                      f"{device_batch_images(batch_size)})", file=sys.stderr)
-            return out
-        print(f"[tise] png feed: images of different sizes ({err}); falling back to the DataLoader path", file=sys.stderr)
-    dl_workers = min(num_workers, 32)
-    dataset = img_data.Dataset(path, transform=None, file_names=shard)
-    dataloader = torch.utils.data.DataLoader(dataset=dataset, batch_size=batch_size, shuffle=False, drop_last=True,
-                                             num_workers=dl_workers, collate_fn=img_data.collate_u8,
-                                             pin_memory=True, worker_init_fn=img_data.worker_init)
-    t0 = time.perf_counter()
-    out = calculate_activation_statistics(dataloader, model, batch_size, dims, cuda, keep_features=keep_features)
-    wall = time.perf_counter() - t0
-    if tdist.is_main() and len(shard):
-        print(f"[tise] png feed: {len(shard)} images in {wall:.2f} s ({len(shard) / wall:.0f} images/s on this rank, {dl_workers} "
-              f"DataLoader decode workers, loader batch {batch_size}, device batch {device_batch_images(batch_size)})", file=sys.stderr)
-    return out
+    failed = tdist.any_rank(err is not None)
+    if err is not None:
+        raise err
+    if failed:
+        raise RuntimeError(f"--u8-cache: rank 0 could not build {cache}")
+    n_used = tdist.n_used_images(len(files), batch_size)
+    lo, hi = tdist.shard_range(n_used // batch_size, rank, world)
+    shape = np.load(cache, mmap_mode="r").shape
+    group = device_batch_images(batch_size, int(np.prod(shape[1:]))) // batch_size
+    loader = img_data.U8CacheLoader(cache, batch_size, dev, rows=(lo * batch_size, hi * batch_size), group=group)
+    n_img = len(loader) * batch_size
+
+    def line(wall):
+        steady = ""
+        sec = loader.steady_seconds()
+        if sec and n_img > loader.first_item_rows:
+            # without the first device batch (first-use costs of the process: code objects, allocator, resize plans):
+            # device events at the end of the first and of the last device batch's work (ADVICE r4: the host time at
+            # which the consumer came back for the second item still contained most of the first batch's device time)
+            steady = f"; after the first device batch {(n_img - loader.first_item_rows) / sec:.0f} images/s"
+        return (f"[tise] u8 cache feed: {n_img} images in {wall:.2f} s ({n_img / wall:.0f} images/s on this rank{steady}); host side "
+                f"(page cache -> pinned buffer -> H2D enqueue) {loader.h2d_seconds:.2f} s, the rest is the device pipeline")
+    return loader, (line if n_img else None)
 
 
 def stats_network_tag(network):
@@ -695,18 +582,6 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None, ke
     lo, hi = tdist.shard_range(len(files), rank, world)
     engine = _engine_for(model, dims)
     accs = {c: device.StatsAccumulator(dims, engine.device) for c in names}
-    from . import crop_feed
-    feed = None
-    if crop_feed.use_native(files[lo:hi], _CROP_FEED["mode"]):
-        # the crop feed (crop_feed.py): same loader batches, same order, every crop used -- the same class statistics to the last bit
-        loader = feed = crop_feed.CropFeedLoader(files[lo:hi], batch_size, engine.device, workers=_num_workers(num_workers, world),
-                                                 drop_last=False)
-    else:
-        dataset = img_data.Dataset(path, transform=None, file_names=files[lo:hi])
-        loader = torch.utils.data.DataLoader(dataset=dataset, batch_size=batch_size, shuffle=False, drop_last=False,
-                                             num_workers=min(32, _num_workers(num_workers, world)), collate_fn=img_data.collate_u8,
-                                             pin_memory=True, worker_init_fn=img_data.worker_init)
-    t_feed = time.perf_counter()
     # The pool3 rows of the directory stay on the device (8 KB per crop); once the walk is complete they are sorted by class
     # and folded into the 80 accumulators by ONE grouped launch (device.stats_update_grouped): every class's S is
     # read-modify-written once per directory.  Round 4 ran one index_select + one 528-workgroup covariance launch per class
@@ -733,21 +608,20 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None, ke
         device.stats_update_grouped(acc_list, feats_sorted, offsets)
         kept, kept_rows = [], 0
 
-    for batch in coalesce_batches(loader, engine.device, device_batch_images(batch_size)):
-        feats = _forward_batch(engine, model, batch)
-        kept.append(feats)
-        if keep_features:
-            walk.append(feats.clone())
-        kept_rows += feats.shape[0]
-        base += feats.shape[0]
-        if kept_rows >= FLUSH_ROWS:
-            flush()
-    flush()
-    if feed is not None:
-        feed.close()
-        if tdist.is_main():
-            print(feed.feed_line(time.perf_counter() - t_feed), file=sys.stderr)
-        _class_statistics.last_crop_loader = feed
+    def consume(loader):
+        nonlocal kept_rows, base
+        for batch in coalesce_batches(loader, engine.device, device_batch_images(batch_size)):
+            feats = _forward_batch(engine, model, batch)
+            kept.append(feats)
+            if keep_features:
+                walk.append(feats.clone())
+            kept_rows += feats.shape[0]
+            base += feats.shape[0]
+            if kept_rows >= FLUSH_ROWS:
+                flush()
+        flush()
+    # the crop feed (crop_feed.py) forms the DataLoader's batches in its order, every crop used: the same class statistics to the last bit
+    feeds.run(feeds.CROPS, files[lo:hi], replace(_FEED, num_workers=num_workers), consume, engine.device, batch_size, world)
     engine.check_numerics()                                # split-fp16 range guard, agreed on by all ranks before the reductions
     # every class is OWNED by one rank (``owner``: class -> rank, the same map on every rank and for both image sets):
     # its 33.57 MB buffer is reduced to that rank only, which alone finalises and solves it (calculate_per_class_fid) --
@@ -907,6 +781,7 @@ def _solve_classes(pairs, dims, dev, eps=1e-6):
 
 
 def main(argv=None):
+    global _FEED
     parser = _build_parser()
     args = parser.parse_args(argv)
     if args.num_classes is None:
@@ -919,9 +794,7 @@ def main(argv=None):
     rank, world, local_rank = tdist.init_from_env()
     if world == 1:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)        # reference: CUDA_VISIBLE_DEVICES = args.gpu (:243)
-    _PNG_FEED["mode"] = args.png_feed
-    _JPEG_FEED["mode"] = args.jpeg_feed
-    _CROP_FEED["mode"] = args.crop_feed
+    _FEED = feeds.Options(args.png_feed, args.jpeg_feed, args.crop_feed)
     if args.conv is not None:
         os.environ["TISE_CONV"] = "miopen" if args.conv == "exact" else "split"
     kind = tweights.inception_kind(args.network, args.label == "O-FID" and args.num_classes == 80)

@@ -18,16 +18,14 @@ softmax, split rule, KL, exp, mean/std -- is the reference's, evaluated on devic
 (csrc/is_score.hip) from fp32 logits.
 """
 import os
-import sys
-import time
 import warnings
 from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser
+from dataclasses import replace
 
 import numpy as np
 import torch
-import torch.utils.data
 
-from . import _lib, device, dist as tdist, img_data, weights as tweights
+from . import _lib, device, dist as tdist, feeds, img_data, weights as tweights
 from .engine import RealismEngine, T_BIRD, T_COCO, T_OIS, require_gpu
 from .inception import NETWORKS, network_classes
 
@@ -35,13 +33,14 @@ warnings.filterwarnings("ignore")
 
 _ENGINE = None
 _CONFIG = {"weights": None, "num_classes": None, "seed": 0, "temperature": T_COCO, "batch_size": 50,
-           "rule": "coco", "drop_first_class": False, "num_workers": 0, "fc_bias": "auto", "png_feed": "ring",
-           "jpeg_feed": None, "network": "torchvision"}
+           "rule": "coco", "drop_first_class": False, "fc_bias": "auto", "network": "torchvision"}
+_FEED = feeds.Options()              # --png-feed / --jpeg-feed / --num-workers (configure(png_feed=..., jpeg_feed=..., num_workers=...))
 
 
 def configure(**kw):
-    """Set weights / temperature / batch size used by the reference-signature functions below."""
-    global _ENGINE
+    """Set weights / temperature / batch size / feed flags used by the reference-signature functions below."""
+    global _ENGINE, _FEED
+    _FEED = replace(_FEED, **{k: kw.pop(k) for k in ("png_feed", "jpeg_feed", "num_workers") if k in kw})
     _CONFIG.update(kw)
     _ENGINE = None
 
@@ -101,18 +100,16 @@ def feed_images(eng, images, lo, hi, begin):
     (called again when the feed falls back to the DataLoader path), then every device batch goes through
     ``eng.step_u8`` / ``eng.step_u8_list``.  The PNG ring feed by default, the DataLoader for images of mixed sizes."""
     bs = _CONFIG["batch_size"]
-    _, world, _ = tdist.env_world()
     # --batch-size is the loader's batch; a trunk pass takes up to engine.device_batch_images of them (split membership
     # is by global index, so batching changes nothing: tests/test_gpu_kernels.py batch invariance)
-    from . import png_ring
-    from .engine import coalesce_batches, device_batch_images
-    workers = _CONFIG["num_workers"] if _CONFIG["num_workers"] and _CONFIG["num_workers"] > 0 else png_ring.auto_workers(world)
+    from .engine import STAGING_BYTES_CAP, coalesce_batches, device_batch_images, item_schedule
 
-    def run(feed):
+    def consume(loader):
         begin()
         eng.reserve_activations(min(hi - lo, device_batch_images(bs)))     # one allocation of the passes' peak (engine.reserve_activations)
         base = lo
-        for batch in feed:
+        # the ring and the JPEG feed (item_rows below) deliver device batches; the DataLoader's batches are gathered into them
+        for batch in coalesce_batches(loader, eng.device, device_batch_images(bs)) if isinstance(loader, torch.utils.data.DataLoader) else loader:
             if isinstance(batch, (list, tuple)):              # images of different sizes: one trunk pass for the batch
                 eng.step_u8_list(batch, base)
                 base += len(batch)
@@ -120,52 +117,19 @@ def feed_images(eng, images, lo, hi, begin):
                 eng.step_u8(batch.to(eng.device, non_blocking=True), base)
                 base += batch.shape[0]
 
-    def dataloader_feed():
-        dataset = img_data.Dataset(None, transform=None, file_names=images[lo:hi])
-        loader = torch.utils.data.DataLoader(dataset, batch_size=bs, shuffle=False, drop_last=False,
-                                             num_workers=min(32, workers), collate_fn=img_data.collate_u8, pin_memory=True,
-                                             worker_init_fn=img_data.worker_init)
-        return coalesce_batches(loader, eng.device, device_batch_images(bs))
-
-    if _CONFIG.get("png_feed", "ring") == "ring" and hi > lo:
+    def jpeg_args():
+        # JPEG files (the CUB photographs, COCO val2014; jpeg_feed.py), sizes may differ.  Items = the device batches the PNG ring
+        # would deliver for files of the first one's size (engine.item_schedule over loader batches of 1, clamped to
+        # STAGING_BYTES_CAP of pixels): the same reduction order, the same IS* to the last bit
         from . import jpeg_feed
-        if jpeg_feed.use_native(images[lo:hi], _CONFIG.get("jpeg_feed")):
-            # JPEG files (the CUB photographs, COCO val2014): Huffman decoding in threads of this process, the rest on the GPU
-            # (jpeg_feed.py); every image is used (no drop-last), images may differ in size
-            # items = the device batches the PNG ring would deliver for files of the first one's size (engine.item_schedule over
-            # loader batches of 1, clamped to STAGING_BYTES_CAP of pixels): the same reduction order, the same IS* to the last bit
-            from .engine import STAGING_BYTES_CAP, item_schedule
-            with open(images[lo], "rb") as fh_:
-                _, w0, h0, _ = jpeg_feed.probe(fh_.read())
-            sb = jpeg_feed.pick_slot_bytes(images[lo:hi])                     # the largest of the first files, not the first one
-            rows = item_schedule(hi - lo, 1, min(device_batch_images(1), max(1, STAGING_BYTES_CAP // max(1, h0 * w0 * 3)),
-                                                   max(1, (1 << 29) // sb)))                             # ... and an arena of at most 512 MiB
-            loader = jpeg_feed.JpegFeedLoader(images[lo:hi], 1, eng.device, workers=workers, drop_last=False, item_rows=rows,
-                                              slot_bytes=sb)
-            t0 = time.perf_counter()
-            try:
-                run(loader)
-            finally:
-                loader.close()
-            if tdist.is_main():
-                print(loader.feed_line(time.perf_counter() - t0), file=sys.stderr)
-            feed_images.last_jpeg_loader = loader
-            return
-    if _CONFIG.get("png_feed", "ring") == "ring" and hi > lo:
-        # decode processes -> shared page-locked ring -> side-stream H2D (png_ring.py); every image is used (no drop-last:
-        # inception_score_star_coco.py:44-51 feeds the images one by one), so the ring's loader batch is 1
-        ring = png_ring.PngRingLoader(images[lo:hi], 1, eng.device, group=device_batch_images(1), workers=workers)
-        try:
-            run(ring)
-        except png_ring.RaggedImages as e:
-            if world > 1:
-                raise RuntimeError(f"the ring feed under torchrun needs images of one size ({e})") from e
-            print(f"[tise] png feed: images of different sizes ({e}); falling back to the DataLoader path", file=sys.stderr)
-            run(dataloader_feed())
-        finally:
-            ring.close()
-    else:
-        run(dataloader_feed())
+        with open(images[lo], "rb") as fh_:
+            _, w0, h0, _ = jpeg_feed.probe(fh_.read())
+        sb = jpeg_feed.pick_slot_bytes(images[lo:hi])                     # the largest of the first files, not the first one
+        rows = item_schedule(hi - lo, 1, min(device_batch_images(1), max(1, STAGING_BYTES_CAP // max(1, h0 * w0 * 3)),
+                                               max(1, (1 << 29) // sb)))                             # ... and an arena of at most 512 MiB
+        return {"batch_size": 1, "item_rows": rows, "slot_bytes": sb}
+    # no drop-last (inception_score_star_coco.py:44-51 feeds the images one by one): the ring's and the JPEG feed's loader batch is 1
+    feeds.run(feeds.IS, images[lo:hi], _FEED, consume, eng.device, bs, loader_args={"jpeg": jpeg_args, "ring": {"batch_size": 1}})
 
 
 def get_inception_score(images, splits=10):

@@ -20,7 +20,7 @@ import torch
 import torch.utils.data
 from PIL import Image
 
-from . import device, dist as tdist, img_data, weights as tweights
+from . import device, dist as tdist, feeds, img_data, weights as tweights
 from .engine import RealismEngine, T_OIS, require_gpu
 from .inception import InceptionV3
 
@@ -76,44 +76,33 @@ def inception_score(imgs, cuda=True, batch_size=32, resize=False, splits=1, weig
     eng = _engine(weights, num_classes, seed)
     rank, world, _ = tdist.env_world()
     lo, hi = tdist.shard_range(N, rank, world)
-    feed = None
-    if isinstance(imgs, IgnoreLabelDataset):
-        from . import crop_feed as _cf
-        files = [os.path.join(imgs.imgspath, name) for name in imgs.namelist[lo:hi]]
-        if _cf.use_native(files, crop_feed):
-            feed = _cf.CropFeedLoader(files, batch_size, eng.device, drop_last=False)
-    if feed is not None:
-        loader = feed
-    else:
-        subset = torch.utils.data.Subset(imgs, range(lo, hi))
-        loader = torch.utils.data.DataLoader(subset, batch_size=batch_size, num_workers=num_workers,
-                                             collate_fn=img_data.collate_u8 if isinstance(imgs, IgnoreLabelDataset) else None,
-                                             worker_init_fn=img_data.worker_init)
-    import sys
-    import time
-    t_feed = time.perf_counter()
-    eng.begin(n_total=N, temperature=temperature, splits=splits, rule="ois")
-    base = lo
+    is_files = isinstance(imgs, IgnoreLabelDataset)
+    files = [os.path.join(imgs.imgspath, name) for name in imgs.namelist[lo:hi]] if is_files else []
     # batch_size (32 in the reference's call, :122) is the loader's batch; a trunk pass takes up to
     # engine.device_batch_images of them
     from .engine import coalesce_batches, device_batch_images
-    for batch in coalesce_batches(loader, eng.device, device_batch_images(batch_size)):
-        if isinstance(batch, (list, tuple)):              # crops of different sizes: resized into ONE batch
-            feats, logits = eng.features_from_u8_list(batch)
-        elif batch.dtype == torch.uint8:
-            feats, logits = eng.features_from_u8(batch.to(eng.device, non_blocking=True))
-        else:
-            x = batch.to(eng.device).float()
-            if resize:
-                x = torch.nn.functional.interpolate(x, size=(299, 299), mode="bilinear")         # :38,49
-            feats, logits = eng._trunk(x.contiguous(memory_format=torch.channels_last), prenormalized=True)
-        eng.is_acc.update(logits, base)
-        base += logits.shape[0]
-    if feed is not None:
-        feed.close()
-        if tdist.is_main():
-            print(feed.feed_line(time.perf_counter() - t_feed), file=sys.stderr)
-        inception_score.last_crop_loader = feed
+
+    def consume(loader):
+        eng.begin(n_total=N, temperature=temperature, splits=splits, rule="ois")
+        base = lo
+        for batch in coalesce_batches(loader, eng.device, device_batch_images(batch_size)):
+            if isinstance(batch, (list, tuple)):              # crops of different sizes: resized into ONE batch
+                feats, logits = eng.features_from_u8_list(batch)
+            elif batch.dtype == torch.uint8:
+                feats, logits = eng.features_from_u8(batch.to(eng.device, non_blocking=True))
+            else:
+                x = batch.to(eng.device).float()
+                if resize:
+                    x = torch.nn.functional.interpolate(x, size=(299, 299), mode="bilinear")         # :38,49
+                feats, logits = eng._trunk(x.contiguous(memory_format=torch.channels_last), prenormalized=True)
+            eng.is_acc.update(logits, base)
+            base += logits.shape[0]
+    # the reference's own DataLoader (:33): the caller's dataset (float tensors: default collate), exactly ``num_workers`` processes, no
+    # pinning; the crop feed takes its own count of decode threads
+    own = {"dataset": torch.utils.data.Subset(imgs, range(lo, hi)), "workers": num_workers, "max_workers": None, "pin_memory": False,
+           "collate": img_data.collate_u8 if is_files else None}
+    feeds.run(feeds.CROPS, files, feeds.Options(crop_feed=crop_feed), consume, eng.device, batch_size,
+              loader_args={"crop": {"workers": None}, "dataloader": own})
     eng.check_numerics()                                                      # split-fp16 range guard
     tdist.all_reduce_sum_(eng.is_acc.acc)
     mean, std, _ = eng.is_acc.finalize()

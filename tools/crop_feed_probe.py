@@ -105,7 +105,7 @@ def _features_from_u8_list_per_crop(self, crops):
 
 def gpu_probe(d, modes, pairs, batch_size):
     import torch
-    from tise_toolbox_amd import fid_score, img_data
+    from tise_toolbox_amd import feeds, fid_score, img_data
     from tise_toolbox_amd.engine import RealismEngine
     n = len(img_data.get_filenames(d))
     rates = {m: [] for m in modes}
@@ -113,7 +113,7 @@ def gpu_probe(d, modes, pairs, batch_size):
     with fid_score._own_model(2048, None, 80, 0) as model:
         for rep in range(pairs + 1):                                       # the first round warms page cache, code objects, allocator, plans
             for m in modes:
-                fid_score._CROP_FEED["mode"] = "native" if m == "native" else "dataloader"
+                fid_score._FEED = feeds.Options(crop_feed="native" if m == "native" else "dataloader")
                 RealismEngine.features_from_u8_list = _features_from_u8_list_per_crop if m == "parent" else one_launch
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -123,7 +123,7 @@ def gpu_probe(d, modes, pairs, batch_size):
                 if rep:
                     rates[m].append(n / dt)
                 print(f"  crops run {rep} {m}: {n} images in {dt:.2f} s = {n / dt:.0f} images/s" + ("" if rep else " (warm-up, not counted)"), flush=True)
-    fid_score._CROP_FEED["mode"] = None
+    fid_score._FEED = feeds.Options()
     RealismEngine.features_from_u8_list = one_launch
     for m in modes:
         r = rates[m]
@@ -132,8 +132,8 @@ def gpu_probe(d, modes, pairs, batch_size):
 
 def kernels_only(d, batch_size):
     import torch
-    from tise_toolbox_amd import fid_score
-    fid_score._CROP_FEED["mode"] = "native"
+    from tise_toolbox_amd import feeds, fid_score
+    fid_score._FEED = feeds.Options(crop_feed="native")
     with fid_score._own_model(2048, None, 80, 0) as model:
         fid_score._class_statistics(d, model, batch_size, 2048, 0)
         torch.cuda.synchronize()

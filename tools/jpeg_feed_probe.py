@@ -81,14 +81,14 @@ def host_probe(d, n=300):
 
 def gpu_probe(d, modes, pairs, batch_size):
     import torch
-    from tise_toolbox_amd import fid_score, img_data
+    from tise_toolbox_amd import feeds, fid_score, img_data
     n = len(img_data.get_filenames(d)) // batch_size * batch_size
     rates = {m: [] for m in modes}
     with fid_score._own_model(2048, None, None, 0) as model:
         for rep in range(pairs + 1):                                       # the first round warms page cache, code objects, allocator
             for m in modes:
-                fid_score._JPEG_FEED["mode"] = "pillow" if m == "pillow" else "native"
-                fid_score._PNG_FEED["mode"] = "dataloader" if m == "dataloader" else "ring"
+                fid_score._FEED = feeds.Options(png_feed="dataloader" if m == "dataloader" else "ring",
+                                                jpeg_feed="pillow" if m == "pillow" else "native")
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 fid_score._compute_statistics_of_path(d, model, batch_size, 2048, True, num_workers=0)
@@ -97,7 +97,7 @@ def gpu_probe(d, modes, pairs, batch_size):
                 if rep:
                     rates[m].append(n / dt)
                 print(f"  {os.path.basename(d)} run {rep} {m}: {n} images in {dt:.2f} s = {n / dt:.0f} images/s" + ("" if rep else " (warm-up, not counted)"), flush=True)
-    fid_score._JPEG_FEED["mode"], fid_score._PNG_FEED["mode"] = None, "ring"
+    fid_score._FEED = feeds.Options()
     for m in modes:
         r = rates[m]
         print(f"{os.path.basename(d)} {m}: median {statistics.median(r):.0f} images/s, spread {max(r) - min(r):.0f} (runs {' '.join(f'{x:.0f}' for x in r)})", flush=True)
