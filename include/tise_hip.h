@@ -217,6 +217,38 @@ int tise_mmd_poly3_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, con
                            double* out_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * k-nearest-neighbour manifold metrics: improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et
+ * al. 2020) (csrc/knn.hip).  No counterpart in the reference; the definitions are those of the `prdc` package, which computes
+ * them on the host with sklearn.  From fp32 rows on the device, with
+ *     d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)     in fp64: a.b on the matrix cores, |.|^2 a fixed-order sum of exact squares
+ * tise_knn_radius2 writes, for every row i of one set, r2[i] = the k-th smallest d2(x_i, x_j) over j != i, and tise_prdc_counts,
+ * for rows R (n, the real side) and F (m, the generated side) with their radii, with strict comparisons on the squared values,
+ *     cnt[i] = #{ j : d2(R_i, F_j) < r2_r[i] }    rec[i] = 1 if some j has d2(R_i, F_j) < r2_f[j], else 0
+ *     prec[j] = 1 if some i has d2(R_i, F_j) < r2_r[i], else 0
+ * No rows x rows matrix is written; the grid is (row tiles of 64) x (S column splits).  d2 of a pair is the same bits in both
+ * calls and for either order of the two rows.  Results combine across workgroups through a selection among candidates and
+ * integer add / or only: two calls on the same inputs give the same bits.
+ *   x_dev, r_dev, f_dev   fp32 feature matrices, rows of ld floats, d columns used (ld >= d, ld % 4 == 0, 16-byte aligned base)
+ *   k                     1 .. 16; rows >= k + 1 (tise_prdc_counts: rows >= 1 per side); rows <= 2^24
+ *   col_splits            S: 0 = ceil(1024 / row tiles) (about four workgroups per compute unit of a 256-unit device when the
+ *                         rows are few), 1 .. 1024 = the caller's value; either is capped at the number of column tiles
+ *   r2_dev                rows doubles (out); r2_r_dev, r2_f_dev: n and m doubles (in)
+ *   cnt_dev, rec_dev      n int32 each (out);  prec_dev: m int32 (out); the call zeroes them first
+ *   ws_dev                device scratch, 8-byte aligned.  tise_knn_radius2: ws_bytes >= tise_knn_workspace_bytes(rows, k,
+ *                         col_splits) = 8 * rows * (S * k + 1) (k candidates per row and split, and the norms);
+ *                         tise_prdc_counts: ws_bytes >= 8 * (rows_r + rows_f) (the norms)
+ * Rejected before any HIP call (TISE_ERR_INVALID_ARG): a NULL pointer, k outside 1 .. 16, rows < k + 1, d <= 0, ld < d,
+ * ld % 4 != 0, a feature base that is not 16-byte aligned, col_splits outside 0 .. 1024, a workspace too small or misaligned.
+ * TISE_ERR_UNSUPPORTED: more than 2^24 rows.
+ * ------------------------------------------------------------------------------------------ */
+int tise_knn_workspace_bytes(int64_t rows, int k, int col_splits, size_t* bytes);
+int tise_knn_radius2(const float* x_dev, int64_t rows, int64_t ld, int d, int k, int col_splits, double* r2_dev, void* ws_dev,
+                     size_t ws_bytes, void* stream);
+int tise_prdc_counts(const float* r_dev, int64_t rows_r, int64_t ld_r, const double* r2_r_dev, const float* f_dev, int64_t rows_f,
+                     int64_t ld_f, const double* r2_f_dev, int d, int col_splits, int32_t* cnt_dev, int32_t* rec_dev,
+                     int32_t* prec_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a6) Frechet distance.
  * Replaces calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps)
  *                                           image_realism/FID/fid_score.py:121-171

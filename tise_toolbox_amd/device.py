@@ -426,6 +426,21 @@ def mmd_index(index, rows, what):
     return idx
 
 
+def _rows_side(t, what):
+    """A (rows, d) float32 CUDA tensor as the gathered-row fetch of csrc/gemm_tile.h needs it: unit column stride, row stride a
+    multiple of 4 and >= d, 16-byte aligned base -- the tensor itself when it already is, else a copy (padded when d % 4 != 0)."""
+    _require_cuda(t)
+    if t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError(f"{what} must be a (rows, d) float32 tensor")
+    if t.shape[0] and (t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16):
+        t = t.contiguous()
+        if t.stride(0) % 4 or t.data_ptr() % 16:                 # d % 4 != 0: pad the rows to the fetch's alignment
+            p = torch.zeros((t.shape[0], (t.shape[1] + 3) // 4 * 4), dtype=torch.float32, device=t.device)
+            p[:, :t.shape[1]] = t
+            t = p[:, :t.shape[1]]
+    return t
+
+
 class PolynomialMMD:
     """Grouped sums of the KID kernel k(a, b) = (a.b / d + 1)^3 on resident fp32 rows (tise_mmd_poly3_grouped in
     include/tise_hip.h): every group's Sxx, Syy, Sxy from one launch pair, bitwise reproducible."""
@@ -437,16 +452,7 @@ class PolynomialMMD:
         self._ws = None
 
     def _side(self, t, what):
-        _require_cuda(t)
-        if t.dim() != 2 or t.dtype != torch.float32:
-            raise ValueError(f"{what} must be a (rows, d) float32 tensor")
-        if t.shape[0] and (t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16):
-            t = t.contiguous()
-            if t.stride(0) % 4 or t.data_ptr() % 16:                 # d % 4 != 0: pad the rows to the fetch's alignment
-                p = torch.zeros((t.shape[0], (t.shape[1] + 3) // 4 * 4), dtype=torch.float32, device=t.device)
-                p[:, :t.shape[1]] = t
-                t = p[:, :t.shape[1]]
-        return t
+        return _rows_side(t, what)
 
     def sums(self, X, Y, offsets_x, offsets_y, index_x=None, index_y=None):
         """X (rows_x, d), Y (rows_y, d): fp32 CUDA tensors (row stride may exceed d).  offsets_*: n_groups + 1 host integers
@@ -491,6 +497,60 @@ class PolynomialMMD:
         m = torch.from_numpy(self.last_counts[1].astype(np.float64)).to(self.device)
         v = s[:, 0] / (n * (n - 1.0)) + s[:, 1] / (m * (m - 1.0)) - 2.0 * s[:, 2] / (n * m)
         return torch.where((n < 2) | (m < 2), torch.full_like(v, float("nan")), v)
+
+
+class KnnManifold:
+    """k-nearest-neighbour radii and the precision / recall / density / coverage counts on resident fp32 rows (tise_knn_radius2
+    and tise_prdc_counts in include/tise_hip.h; csrc/knn.hip).  Owns the workspace; bitwise reproducible."""
+
+    def __init__(self, device=None):
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise _lib.TiseLibraryError("KnnManifold needs a HIP device")
+        self._ws = None
+
+    def _workspace(self, nbytes):
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(max(256, nbytes), dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def radius2(self, X, k, col_splits=0):
+        """X (n, d) fp32 CUDA tensor (row stride may exceed d), n >= k + 1, 1 <= k <= 16 -> (n,) fp64 CUDA tensor: the squared
+        distance from every row to its k-th nearest OTHER row.  ``col_splits``: 0 = chosen by the library."""
+        X = _rows_side(X, "X")
+        k, col_splits = int(k), int(col_splits)
+        if X.shape[1] < 1:
+            raise ValueError("X needs at least one column")
+        if not 1 <= k <= 16 or X.shape[0] < k + 1:
+            raise ValueError(f"radius2 needs 1 <= k <= 16 and at least k + 1 rows (got k = {k}, {X.shape[0]} rows)")
+        r2 = torch.empty(X.shape[0], dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            nbytes = ctypes.c_size_t()
+            _lib.call("tise_knn_workspace_bytes", X.shape[0], k, col_splits, ctypes.byref(nbytes))
+            ws = self._workspace(nbytes.value)
+            _lib.call("tise_knn_radius2", _ptr(X), X.shape[0], X.stride(0), int(X.shape[1]), k, col_splits, _ptr(r2), _ptr(ws),
+                      ws.numel(), _stream())
+        return r2
+
+    def counts(self, R, r2R, F, r2F, col_splits=0):
+        """R (n, d), F (m, d) fp32 CUDA tensors with their squared radii (fp64, from radius2) -> (cnt (n,) int32, rec (n,) bool,
+        prec (m,) bool) CUDA tensors: cnt[i] = number of F rows strictly inside R_i's ball, rec[i] = R_i lies strictly inside
+        some F row's ball, prec[j] = F_j lies strictly inside some R row's ball."""
+        R, F = _rows_side(R, "R"), _rows_side(F, "F")
+        if R.shape[1] != F.shape[1] or R.shape[1] < 1 or not R.shape[0] or not F.shape[0]:
+            raise ValueError("R and F need rows and the same, positive number of columns")
+        r2R = r2R.to(self.device, torch.float64).contiguous()
+        r2F = r2F.to(self.device, torch.float64).contiguous()
+        if r2R.shape != (R.shape[0],) or r2F.shape != (F.shape[0],):
+            raise ValueError("one squared radius per row of each side")
+        cnt = torch.empty(R.shape[0], dtype=torch.int32, device=self.device)
+        rec = torch.empty(R.shape[0], dtype=torch.int32, device=self.device)
+        prec = torch.empty(F.shape[0], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            ws = self._workspace(8 * (R.shape[0] + F.shape[0]))
+            _lib.call("tise_prdc_counts", _ptr(R), R.shape[0], R.stride(0), _ptr(r2R), _ptr(F), F.shape[0], F.stride(0), _ptr(r2F),
+                      int(R.shape[1]), int(col_splits), _ptr(cnt), _ptr(rec), _ptr(prec), _ptr(ws), ws.numel(), _stream())
+        return cnt, rec != 0, prec != 0
 
 
 def _wrap_device_doubles(ptr, n, device, owner=None):

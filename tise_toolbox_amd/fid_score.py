@@ -130,6 +130,14 @@ def _build_parser():
                         help="rows per subset and side (capped at the smaller set); 0 = the full-set estimator, no subsets")
     parser.add_argument("--kid-seed", type=int, default=0, help="seed of numpy.random.RandomState for the subsets")
     parser.add_argument("--kid-saved-file", type=str, default="", help="write the KID line(s) to this file")
+    parser.add_argument("--prdc", action="store_true",
+                        help="also report precision, recall, density and coverage (prdc.py: k-nearest-neighbour manifolds of the pool3 "
+                             "rows) from the same pass over the images; --save-stats then also stores the feature rows, and an .npz "
+                             "input must hold them.  Not available with --per-class")
+    parser.add_argument("--prdc-k", type=int, default=5,
+                        help="nearest neighbours of the manifold estimate, 1 .. 16: 5 is the density / coverage paper's value (the "
+                             "prdc package), 3 the improved precision / recall paper's")
+    parser.add_argument("--prdc-saved-file", type=str, default="", help="write the four precision / recall / density / coverage lines to this file")
     return parser
 
 
@@ -321,13 +329,14 @@ def prefetch_png_ring(path, batch_size, num_workers=0):
     return feeds.prefetch_png_ring(path, batch_size, replace(_FEED, num_workers=num_workers))
 
 
-def kid_features_of_npz(path):
-    """The ``features`` array of a statistics file (float32, n_used x dims, global walk order: what --kid --save-stats
-    stores beside mu and sigma).  KID needs the rows themselves; a {mu, sigma} file cannot serve it."""
+def kid_features_of_npz(path, flag="--kid"):
+    """The ``features`` array of a statistics file (float32, n_used x dims, global walk order: what --kid --save-stats or
+    --prdc --save-stats stores beside mu and sigma).  KID and the k-NN metrics need the rows themselves; a {mu, sigma} file
+    cannot serve them.  ``flag`` names the metric that asks."""
     with np.load(path, allow_pickle=True) as f:
         if "features" not in f.files:
-            raise RuntimeError(f"{path}: no 'features' array in this statistics file, and --kid needs the feature rows; "
-                               "make the file with --kid --save-stats")
+            raise RuntimeError(f"{path}: no 'features' array in this statistics file, and {flag} needs the feature rows; "
+                               "make the file with --kid --save-stats or --prdc --save-stats")
         return np.ascontiguousarray(f["features"], dtype=np.float32)
 
 
@@ -336,8 +345,8 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
     ``u8_cache``: decode the directory ONCE into ``<path>/.tise_u8_cache.npy`` ((N,H,W,3) uint8, walk order) and feed
     later runs -- and every rank of a data-parallel run -- from it through a double-buffered pinned host->device
     pipeline (img_data.U8CacheLoader) instead of PNG-decoding DataLoader workers.
-    ``keep_features`` (KID): a third value, the fp32 feature rows of the n_used images in global walk order -- a device tensor
-    from a directory, the ``features`` array of an .npz."""
+    ``keep_features`` (KID, precision / recall / density / coverage): a third value, the fp32 feature rows of the n_used images
+    in global walk order -- a device tensor from a directory, the ``features`` array of an .npz."""
     if path.endswith(".npz"):
         f = np.load(path, allow_pickle=True)              # :201-203
         m, s = f["mu"][:], f["sigma"][:]
@@ -413,8 +422,8 @@ def check_stats_network(path, tag, network):
 
 
 def save_stats_npz(path, mu, sigma, network="torchvision", features=None):
-    """``features`` (only under --kid): the float32 rows KID needs, beside mu and sigma; without it the file is exactly
-    {mu, sigma[, network]}."""
+    """``features`` (only under --kid or --prdc): the float32 rows those metrics need, beside mu and sigma; without it the file
+    is exactly {mu, sigma[, network]}."""
     extra = {} if features is None else {"features": np.ascontiguousarray(
         features.cpu().numpy() if isinstance(features, torch.Tensor) else features, dtype=np.float32)}
     np.savez(path, mu=np.asarray(mu), sigma=np.asarray(sigma), **stats_network_tag(network), **extra)
@@ -466,7 +475,7 @@ def calculate_fid_and_kid_given_paths(paths, batch_size, cuda, dims, weights=Non
     FID uses are kept on the device (8 KB per image) and handed to kid.kid_from_features; ``save_stats`` then also stores them
     (``features``), and an .npz path must hold them.  ``kid_seed`` seeds the subsets (``seed`` is the stand-in weights')."""
     return _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache,
-                                network, {"subsets": subsets, "subset_size": subset_size, "seed": kid_seed})
+                                network, {"subsets": subsets, "subset_size": subset_size, "seed": kid_seed})[:2]
 
 
 def calculate_kid_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0, save_stats="",
@@ -476,18 +485,30 @@ def calculate_kid_given_paths(paths, batch_size, cuda, dims, weights=None, num_c
                                              u8_cache, network, subsets, subset_size, kid_seed)[1]
 
 
+def calculate_prdc_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0, save_stats="",
+                               num_workers=8, u8_cache=False, network="torchvision", nearest_k=5):
+    """Precision, recall, density and coverage of two paths (paths[0] the real side, paths[1] the generated side) -> OrderedDict
+    (prdc.py).  One pass over each directory, as for KID: the pool3 rows are kept on the device; ``save_stats`` then also stores
+    them (``features``), and an .npz path must hold them."""
+    return _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache,
+                                network, None, nearest_k)[2]
+
+
 def _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache, network,
-                         kid_args):
-    """calculate_fid_given_paths; with ``kid_args`` (subsets, subset_size, seed) the feature rows of both sides are retained and
-    the KID is evaluated after the Frechet distance -> (fid, None | (mean, std)).  Without it: the launches of the FID alone."""
+                         kid_args, prdc_k=None):
+    """calculate_fid_given_paths; with ``kid_args`` (subsets, subset_size, seed) and / or ``prdc_k`` the feature rows of both
+    sides are retained and the KID / the k-NN metrics are evaluated after the Frechet distance
+    -> (fid, None | (mean, std), None | OrderedDict).  Without either: the launches of the FID alone."""
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError("Invalid path: %s" % p)    # :225-227
-    keep = kid_args is not None
+    keep = kid_args is not None or prdc_k is not None
+    if prdc_k is not None and not 1 <= int(prdc_k) <= 16:
+        raise ValueError(f"nearest_k must lie in 1 .. 16 (got {prdc_k})")
     if keep:
-        for p in paths:                                   # a {mu, sigma} file cannot serve KID: say so before anything is computed
+        for p in paths:                                   # a {mu, sigma} file cannot serve them: say so before anything is computed
             if p.endswith(".npz"):
-                kid_features_of_npz(p)
+                kid_features_of_npz(p, "--kid" if kid_args is not None else "--prdc")
     _check_cuda(cuda)
     if not u8_cache:
         # the decode workers of the first directory start now: PNG decode overlaps building the model (weights, BatchNorm
@@ -537,10 +558,16 @@ def _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, se
 
         fid = solve()
         if not keep:
-            return fid, None
-        # every rank holds the same rows in the same order (all_gather_rows) and evaluates the (cheap) KID itself: no broadcast
-        from . import kid
-        return fid, kid.kid_from_features(f1[0], f2[0], kid_args["subsets"], kid_args["subset_size"], kid_args["seed"])
+            return fid, None, None
+        # every rank holds the same rows in the same order (all_gather_rows) and evaluates the KID / the k-NN metrics itself: no broadcast
+        kid_value = prdc_value = None
+        if kid_args is not None:
+            from . import kid
+            kid_value = kid.kid_from_features(f1[0], f2[0], kid_args["subsets"], kid_args["subset_size"], kid_args["seed"])
+        if prdc_k is not None:
+            from . import prdc
+            prdc_value = prdc.prdc_from_features(f1[0], f2[0], int(prdc_k))
+        return fid, kid_value, prdc_value
 
 
 def save_statistics_of_path(path, out_npz, batch_size, cuda, dims, weights=None, num_classes=None, seed=0,
@@ -556,7 +583,7 @@ def save_statistics_of_path(path, out_npz, batch_size, cuda, dims, weights=None,
     with _own_model(dims, weights, num_classes, seed, network) as model:
         mu, sigma, *feats = _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers, u8_cache, keep_features)
         if tdist.is_main():
-            save_stats_npz(out_npz, mu, sigma, network, feats[0] if keep_features else None)   # --kid: the rows KID needs, too
+            save_stats_npz(out_npz, mu, sigma, network, feats[0] if keep_features else None)   # --kid / --prdc: the rows they need, too
         return mu, sigma
 
 
@@ -791,6 +818,10 @@ def main(argv=None):
         _check_cuda(False)
     if args.path1 is None and not args.save_stats:
         parser.error("--path1 is required (omit it only together with --save-stats: statistics-only mode)")
+    if args.prdc and args.per_class:
+        parser.error("--per-class --prdc is not available: a k-nearest-neighbour manifold of some 40 crops per class means nothing")
+    if args.prdc and not 1 <= args.prdc_k <= 16:
+        parser.error("--prdc-k must lie in 1 .. 16")
     rank, world, local_rank = tdist.init_from_env()
     if world == 1:
         os.environ.setdefault("HIP_VISIBLE_DEVICES", args.gpu)        # reference: CUDA_VISIBLE_DEVICES = args.gpu (:243)
@@ -804,7 +835,7 @@ def main(argv=None):
             print([args.path2])
         mu, sigma = run_with_exact_fallback(lambda: save_statistics_of_path(
             args.path2, args.save_stats, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.num_workers,
-            args.u8_cache, args.network, args.kid), "the statistics pass")
+            args.u8_cache, args.network, args.kid or args.prdc), "the statistics pass")
         if tdist.is_main():
             print(f"statistics of {args.path2} -> {args.save_stats}{tag}")
         return None
@@ -838,9 +869,9 @@ def main(argv=None):
                 print("\n".join(klines))
         return per
     kid_args = {"subsets": args.kid_subsets, "subset_size": args.kid_subset_size, "seed": args.kid_seed} if args.kid else None
-    fid_value, kid_value = run_with_exact_fallback(lambda: _fid_kid_given_paths(
+    fid_value, kid_value, prdc_value = run_with_exact_fallback(lambda: _fid_kid_given_paths(
         paths, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.save_stats, args.num_workers,
-        args.u8_cache, args.network, kid_args), "the FID")
+        args.u8_cache, args.network, kid_args, args.prdc_k if args.prdc else None), "the FID")
     fid_value = fid_value.item()
     if tdist.is_main():
         if args.saved_file:
@@ -853,6 +884,13 @@ def main(argv=None):
                 with open(args.kid_saved_file, "w") as f:
                     f.write(kline)                                     # no trailing newline, like --saved_file
             print(kline)
+        if args.prdc:
+            prefix = "O-" if args.label == "O-FID" else ""
+            plines = [f"{prefix}{name.capitalize()}: {prdc_value[name]}{tag}" for name in ("precision", "recall", "density", "coverage")]
+            if args.prdc_saved_file:
+                with open(args.prdc_saved_file, "w") as f:
+                    f.write("\n".join(plines))                         # no trailing newline, like --saved_file
+            print("\n".join(plines))
     return fid_value
 
 
