@@ -217,6 +217,29 @@ int tise_mmd_poly3_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, con
                            double* out_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CLIP maximum mean discrepancy (CMMD; Jayasumana et al. 2024, "Rethinking FID"): grouped sums of the Gaussian kernel (csrc/mmd.hip)
+ *     k(a, b) = exp(-gamma d2(a, b)),      d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)
+ * No counterpart in the reference; the published implementation forms the three n x n kernel matrices in fp32.  The interface is
+ * tise_mmd_poly3_grouped's, argument for argument, plus gamma, and so are the outputs (Sxx and Syy over i != j, Sxy over all pairs),
+ * the single launch over exactly the 64 x 64 tiles that exist, the fixed-order reduction launch after it, and the guarantee: no
+ * floating-point atomics, no n x n matrix, two calls on the same inputs give the same bits.  Numerics: a.b in fp64 on the matrix
+ * cores; |.|^2 from a pre-pass (one more small launch) into the workspace as a fixed-order sum of exact squares, as
+ * tise_knn_radius2 forms it -- with the parentheses above, d2 of a pair is the same bits whichever side each row is on; exp is the
+ * fp64 library function.  The cost of that exp beside the tile's matrix work has NOT been measured.
+ *   gamma               finite and >= 0 (CMMD: 1 / (2 sigma^2), sigma = 10, on L2-normalised rows)
+ *   ws_dev              ws_bytes >= tise_mmd_rbf_workspace_bytes(...) = tise_mmd_poly3_workspace_bytes(...) + 8 bytes for every
+ *                       row that enters a group, per side: 8 * ((offsets_x[n_groups] - offsets_x[0]) + (offsets_y[n_groups] -
+ *                       offsets_y[0]))
+ * Rejected before any HIP call: whatever tise_mmd_poly3_grouped rejects, with the same codes, and a gamma that is NaN, infinite
+ * or negative (TISE_ERR_INVALID_ARG).  Index values are trusted as there (tise_toolbox_amd.device.GaussianMMD validates them).
+ * ------------------------------------------------------------------------------------------ */
+int tise_mmd_rbf_workspace_bytes(const int64_t* offsets_x_host, const int64_t* offsets_y_host, int n_groups, size_t* bytes);
+int tise_mmd_rbf_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, const int64_t* index_x_dev, int64_t n_index_x,
+                         const int64_t* offsets_x_host, const float* y_dev, int64_t rows_y, int64_t ld_y,
+                         const int64_t* index_y_dev, int64_t n_index_y, const int64_t* offsets_y_host, int n_groups, int d,
+                         double gamma, double* out_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * k-nearest-neighbour manifold metrics: improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et
  * al. 2020) (csrc/knn.hip).  No counterpart in the reference; the definitions are those of the `prdc` package, which computes
  * them on the host with sklearn.  From fp32 rows on the device, with

@@ -172,6 +172,13 @@ def embed_paths(model, paths, dev, batch, workers=0, feed="ring", convert_first=
     preprocess (``preprocess(Image.open(p).convert("RGB"))``: what the ring's workers do); PA.py:34 does not
     (``preprocess(Image.open(p))``: clip resizes first and Pillow resamples RGBA premultiplied), so there only plain RGB files
     may take the ring.  Files of different sizes (or, for PA, not plain RGB) take the DataLoader path."""
+    return encode_paths(model, paths, dev, batch, workers, feed, convert_first, lambda f: f / f.norm(dim=-1, keepdim=True), torch.float16)
+
+
+@torch.no_grad()
+def encode_paths(model, paths, dev, batch, workers, feed, convert_first, finish, dtype):
+    """The image loop embed_paths and cmmd.embed_image_dir share: ``finish(model.encode_image(batch))`` of the files ``paths``, in
+    order, every file used -> (len(paths), 512) tensor of ``dtype``."""
     out = []
 
     def consume(loader):
@@ -179,11 +186,11 @@ def embed_paths(model, paths, dev, batch, workers=0, feed="ring", convert_first=
         for x in loader:
             # the ring delivers uint8 (clip's preprocess on the device), the DataLoader's workers preprocessed fp32
             f = model.encode_image((clip_model.preprocess_device(x) if x.dtype == torch.uint8 else x.to(dev)).half())
-            out.append(f / f.norm(dim=-1, keepdim=True))
+            out.append(finish(f))
     feeds.run(feeds.CLIP, paths, feeds.Options(png_feed=feed, num_workers=workers), consume, dev, batch, tdist.world_size(),
               loader_args={"ring": {"batch_size": 1, "group": batch, "rgb_only": not convert_first},
                            "dataloader": {"dataset": _Paths(paths, convert_first), "pin_memory": False, "collate": None}})
-    return torch.cat(out).contiguous() if out else torch.empty((0, 512), dtype=torch.float16, device=dev)
+    return torch.cat(out).contiguous() if out else torch.empty((0, 512), dtype=dtype, device=dev)
 
 
 class _Paths(torch.utils.data.Dataset):

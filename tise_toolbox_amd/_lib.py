@@ -74,6 +74,10 @@ SIGNATURES = {
     "tise_mmd_poly3_workspace_bytes": (c_int, [POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_size_t)]),
     "tise_mmd_poly3_grouped": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64, c_int64,
                                         c_void_p, c_int64, POINTER(c_int64), c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tise_mmd_rbf_workspace_bytes": (c_int, [POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_size_t)]),
+    "tise_mmd_rbf_grouped": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, POINTER(c_int64), c_void_p, c_int64, c_int64,
+                                      c_void_p, c_int64, POINTER(c_int64), c_int, c_int, c_double, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "tise_knn_workspace_bytes": (c_int, [c_int64, c_int, c_int, POINTER(c_size_t)]),
     "tise_knn_radius2": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tise_prdc_counts": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p,

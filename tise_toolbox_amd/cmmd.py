@@ -1,0 +1,257 @@
+#!/usr/bin/env python3
+"""CLIP-space realism metrics on MI355X: CMMD and CLIP-FID on the ViT-B/32 image tower.
+
+The reference toolbox measures realism in Inception pool3 space only.  The two metrics current text-to-image work reports beside
+FID live on CLIP image embeddings:
+
+CMMD (Jayasumana et al., CVPR 2024, "Rethinking FID: Towards a Better Evaluation Metric for Image Generation"): the squared
+maximum mean discrepancy of the two sets of L2-NORMALISED embeddings under the Gaussian kernel
+
+    k(a, b) = exp(-|a - b|^2 / (2 sigma^2)),   sigma = 10   (GAMMA = 1 / 200),   reported x 1000 (SCALE).
+
+With Sxx, Syy the kernel sums over i != j and Sxy the sum over all pairs (``device.GaussianMMD``, csrc/mmd.hip: fp64 matrix
+cores, fp64 exp, fixed summation order, no n x n matrix),
+
+    V-statistic (default):   SCALE ((Sxx + n) / n^2 + (Syy + m) / m^2 - 2 Sxy / (n m))
+    unbiased (--unbiased):   SCALE (Sxx / (n (n - 1)) + Syy / (m (m - 1)) - 2 Sxy / (n m))
+
+The default is what the PUBLISHED IMPLEMENTATION computes -- the mean of each full kernel matrix, diagonal included, every
+diagonal entry taken as exactly 1 (k(a, a)) -- so that figures compare with it; the paper's formula is the unbiased one.  Every
+term lies between 0.98 and 1 and the result is of order 1e-5 .. 1e-2: the published code evaluates it in fp32, here the sums
+are fp64 and two runs give the same bits.
+
+CLIP-FID (Kynkaanniemi et al. 2022, "The Role of ImageNet Classes in Frechet Inception Distance"; clean-fid's
+``clip_vit_b_32`` mode): the Frechet distance of the UN-normalised embeddings -- ``device.StatsAccumulator(512)`` and
+``engine.frechet_solver(512)``, the FID machinery at another width.
+
+THE TOWER.  Both run on CLIP ViT-B/32 (clip_hip.HipTowers.encode_image, csrc/clip_ops.hip) and the result lines say so.  For
+CLIP-FID that is clean-fid's definition.  Published CMMD figures use ViT-L/14 at 336 pixels, whose 577-token sequences and patch
+size 14 are beyond tise_attention_f16 (seq <= 96) and tise_patchify_f16 (patch % 8 == 0): a CMMD from here is NOT comparable
+with those figures, only with other ViT-B/32 ones.
+
+PREPROCESSING is clip._transform as clip_model restates it: convert to RGB, bicubic resize of the short side to 224, centre
+crop.  CMMD's own loader crops the centre square BEFORE the resize; the two are identical for square images and differ by a
+rounding of the crop window otherwise.
+
+Every image of a directory is used (no drop-last).  Under torchrun the files are sharded as contiguous index ranges, the rows
+gathered in walk order on every rank (dist.all_gather_rows, as the --kid path), and rank 0 prints and writes.
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, device, dist as tdist, img_data, weights as tweights
+
+SIGMA = 10.0
+GAMMA = 1 / (2 * SIGMA ** 2)
+SCALE = 1000.0
+DIMS = 512
+NETWORK = "clip-vit-b32"             # the tag of a feature file (fid_score.check_stats_network)
+TOWER = "ViT-B/32"
+
+
+def cmmd_from_sums(sums, n, m, unbiased=False):
+    """(Sxx, Syy, Sxy) of n and m rows -> CMMD x 1000 as a Python float (the module docstring's two estimators).  Host only."""
+    n, m = int(n), int(m)
+    need = 2 if unbiased else 1
+    if n < need or m < need:
+        raise ValueError(f"CMMD needs at least {need} row{'s' if need > 1 else ''} per side (got {n} and {m})")
+    sxx, syy, sxy = (float(v) for v in sums)
+    if unbiased:
+        return SCALE * (sxx / (n * (n - 1)) + syy / (m * (m - 1)) - 2 * sxy / (n * m))
+    return SCALE * ((sxx + n) / (n * n) + (syy + m) / (m * m) - 2 * sxy / (n * m))
+
+
+def normalize_rows(t):
+    """Rows of an fp32 tensor divided by their fp32 L2 norms (the published implementation's rule; NOT the fp16 normalisation of
+    RP_coco.embed_paths, whose rounding of 1e-3 per element would be of the order of the metric)."""
+    if t.dtype != torch.float32:
+        raise ValueError("rows are normalised in float32")
+    return t / t.norm(dim=-1, keepdim=True)
+
+
+def _width(f):
+    shape = tuple(f.shape)
+    if len(shape) != 2:
+        raise ValueError("features must be (rows, dims)")
+    return shape[1]
+
+
+def _to_device_f32(f, dev):
+    if isinstance(f, torch.Tensor):
+        return f.to(dev, torch.float32)
+    return torch.as_tensor(np.ascontiguousarray(f, dtype=np.float32), device=dev)
+
+
+def cmmd_from_features(f1, f2, unbiased=False, sigma=SIGMA):
+    """CMMD x 1000 of two embedding sets (device tensors or numpy arrays, (n, dims), un-normalised) -> Python float.  The rows are
+    widened to fp32 and normalised in fp32 on the device; ONE grouped launch of one group."""
+    if _width(f1) != _width(f2):
+        raise ValueError(f"feature widths differ: {_width(f1)} and {_width(f2)}")
+    if not sigma > 0:
+        raise ValueError(f"sigma must be positive (got {sigma})")
+    from .engine import require_gpu
+    require_gpu()
+    dev = f1.device if isinstance(f1, torch.Tensor) and f1.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    x, y = normalize_rows(_to_device_f32(f1, dev)), normalize_rows(_to_device_f32(f2, dev))
+    n, m = x.shape[0], y.shape[0]
+    cmmd_from_sums((0.0, 0.0, 0.0), n, m, unbiased)                        # too few rows: say so before the launch
+    s = device.GaussianMMD(dev, 1 / (2 * float(sigma) ** 2)).sums(x, y, [0, n], [0, m]).cpu().numpy()
+    return cmmd_from_sums(s[0], n, m, unbiased)
+
+
+@torch.no_grad()
+def embed_image_dir(towers, path, dev, batch, workers=0, feed="ring"):
+    """Un-normalised fp32 (n, 512) embeddings of EVERY image under ``path``, in img_data.get_filenames' walk order, on every
+    rank.  The loop is RP_coco.embed_paths' (feeds.CLIP: the PNG ring + clip_model.preprocess_device, the DataLoader for a
+    ragged directory); the fp16 rows of the tower are widened, not normalised."""
+    from . import RP_coco
+    files = img_data.get_filenames(path)
+    rank, world, _ = tdist.env_world()
+    lo, hi = tdist.shard_range(len(files), rank, world)
+    rows = RP_coco.encode_paths(towers, files[lo:hi], dev, batch, workers, feed, True, lambda f: f.float(), torch.float32)
+    return tdist.all_gather_rows(rows)
+
+
+def clip_statistics(feats):
+    """(mu, sigma) of un-normalised fp32 rows -> fp64 numpy arrays: np.mean / np.cov (ddof 1) on the device."""
+    stats = device.StatsAccumulator(feats.shape[1], feats.device)
+    stats.update(feats)
+    mu, sigma = stats.finalize()
+    out = mu.cpu().numpy(), sigma.cpu().numpy()
+    stats.close()
+    return out
+
+
+def save_features_npz(path, feats, mu, sigma):
+    """The feature file of --save-features: ``features`` (fp32, un-normalised, walk order), ``mu``, ``sigma`` and the network tag."""
+    from . import fid_score
+    fid_score.save_stats_npz(path, mu, sigma, NETWORK, feats)
+
+
+def load_features_npz(path):
+    """-> (features fp32 (n, 512), mu, sigma) of a file --save-features wrote.  A file of another network (or of none: an
+    Inception {mu, sigma} file) and a file without the rows are refused."""
+    from . import fid_score
+    with np.load(path, allow_pickle=True) as f:
+        tag = str(f["network"]) if "network" in f.files else None
+        if tag is None:
+            raise RuntimeError(f"{path}: no network tag: not a feature file of {NETWORK} (make one with cmmd --save-features)")
+        fid_score.check_stats_network(path, tag, NETWORK)
+        if "features" not in f.files:
+            raise RuntimeError(f"{path}: no 'features' array in this file, and CMMD needs the embedding rows; "
+                               "make the file with cmmd --save-features")
+        feats = np.ascontiguousarray(f["features"], dtype=np.float32)
+        if feats.ndim != 2 or feats.shape[1] != DIMS:
+            raise RuntimeError(f"{path}: features of shape {feats.shape}, expected (n, {DIMS})")
+        return feats, f["mu"][:], f["sigma"][:]
+
+
+def _side(path, towers, dev, batch_size, num_workers, feed, with_stats):
+    """-> (fp32 device rows, mu | None, sigma | None) of a directory or a feature file."""
+    if path.endswith(".npz"):
+        feats, mu, sigma = load_features_npz(path)
+        return torch.as_tensor(feats, device=dev), mu, sigma
+    feats = embed_image_dir(towers(), path, dev, batch_size, num_workers, feed)
+    if feats.shape[0] == 0:
+        raise RuntimeError(f"no images under {path}")
+    mu, sigma = clip_statistics(feats) if with_stats else (None, None)
+    return feats, mu, sigma
+
+
+def _given_paths(paths, batch_size, weights, seed, num_workers, feed, unbiased, clip_fid, save_features, want_cmmd=True):
+    for p in paths:
+        if not os.path.exists(p):
+            raise RuntimeError("Invalid path: %s" % p)
+    if not torch.cuda.is_available():
+        raise _lib.TiseLibraryError("cmmd needs an MI355X: there is no CPU path")
+    _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    built = []
+
+    def towers():                                                          # two feature files need no tower at all
+        if not built:
+            built.append(_towers(weights, seed, dev))
+        return built[0]
+    f1, m1, s1 = _side(paths[0], towers, dev, batch_size, num_workers, feed, clip_fid or bool(save_features))
+    if save_features and tdist.is_main():
+        save_features_npz(save_features, f1, m1, s1)
+    f2, m2, s2 = _side(paths[1], towers, dev, batch_size, num_workers, feed, clip_fid)
+    value = cmmd_from_features(f1, f2, unbiased) if want_cmmd else None
+    fid = None
+    if clip_fid:
+        from . import fid_score
+        fid = float(fid_score.calculate_frechet_distance(m1, s1, m2, s2))
+    return value, fid
+
+
+def _towers(weights, seed, dev):
+    """RP_coco.build_towers; the seeded stand-in parameters (``weights`` None) of any ``seed`` (build_towers serves seed 0)."""
+    from . import RP_coco, clip_hip, clip_model
+    if weights is not None or seed == 0:
+        return RP_coco.build_towers(weights, dev)[0]
+    model = clip_model.build_clip(None, seed).to(dev).half()
+    tdist.broadcast_module_(model)
+    return model if os.environ.get("TISE_CLIP", "hip") == "torch" else clip_hip.HipTowers(model, dev)
+
+
+def calculate_cmmd_given_paths(paths, batch_size=50, weights=None, seed=0, num_workers=0, feed="ring", unbiased=False,
+                               save_features=""):
+    """CMMD x 1000 (ViT-B/32) of two paths -- directories or feature files -> Python float.  ``weights=None``: seeded stand-in
+    parameters (the CLI only allows that behind --synthetic-weights).  ``save_features``: the FIRST path's rows (the reference
+    set: embedded once, compared with many generated sets) are written there with their mu and sigma."""
+    return _given_paths(paths, batch_size, weights, seed, num_workers, feed, unbiased, False, save_features)[0]
+
+
+def calculate_clip_fid_given_paths(paths, batch_size=50, weights=None, seed=0, num_workers=0, feed="ring", save_features=""):
+    """CLIP-FID (ViT-B/32; clean-fid's clip_vit_b_32 definition) of two paths -> Python float: the Frechet distance of the
+    un-normalised embeddings' (mu, sigma) from device.StatsAccumulator(512) and engine.frechet_solver(512)."""
+    return _given_paths(paths, batch_size, weights, seed, num_workers, feed, False, True, save_features, want_cmmd=False)[1]
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description="CMMD and CLIP-FID on the CLIP ViT-B/32 image tower")
+    parser.add_argument("--path1", type=str, required=True, help="reference images: a directory, or a feature file of --save-features")
+    parser.add_argument("--path2", type=str, required=True, help="generated images: a directory, or a feature file of --save-features")
+    parser.add_argument("--batch-size", type=int, default=50)
+    parser.add_argument("--weights", default=None, type=str, help="OpenAI CLIP ViT-B/32 state_dict (.pt); default: ~/.cache/clip/ViT-B-32.pt")
+    parser.add_argument("--synthetic-weights", action="store_true",
+                        help="seeded stand-in tower (plumbing / throughput only; results are tagged)")
+    parser.add_argument("--seed", default=0, type=int, help="seed of the stand-in parameters")
+    parser.add_argument("--clip-fid", action="store_true", help="also report the Frechet distance of the un-normalised embeddings")
+    parser.add_argument("--unbiased", action="store_true",
+                        help="the paper's unbiased estimator instead of the published implementation's V-statistic")
+    parser.add_argument("--save-features", default="", type=str,
+                        help="write --path1's embeddings (fp32, un-normalised), mu, sigma and the network tag to this .npz")
+    parser.add_argument("--saved_file", default="", type=str, help="write the result lines here as well")
+    parser.add_argument("--png-feed", default="ring", choices=["ring", "dataloader"])
+    parser.add_argument("--num-workers", default=0, type=int, help="image decode processes (0 = auto)")
+    parser.add_argument("--gpu", default="0", type=str, help="GPU to use")
+    return parser.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if not torch.cuda.is_available():
+        raise _lib.TiseLibraryError("cmmd needs an MI355X: there is no CPU path")
+    rank, world, local_rank = tdist.init_from_env()
+    dev = torch.device(f"cuda:{local_rank}" if world > 1 else f"cuda:{args.gpu}")
+    torch.cuda.set_device(dev)
+    wpath, tag = tweights.resolve(args.weights, args.synthetic_weights, "clip")
+    value, fid = _given_paths([args.path1, args.path2], args.batch_size, wpath, args.seed, args.num_workers, args.png_feed,
+                              args.unbiased, args.clip_fid, args.save_features)
+    lines = [f"CMMD ({TOWER}): {value}{tag}"]
+    if args.clip_fid:
+        lines.append(f"CLIP-FID ({TOWER}): {fid}{tag}")
+    if tdist.is_main():
+        if args.saved_file:
+            with open(args.saved_file, "w") as f:
+                f.write("\n".join(lines))                                  # no trailing newline, like fid_score --saved_file
+        print("\n".join(lines))
+    return value, fid
+
+
+if __name__ == "__main__":
+    tdist.run_cli(main)

@@ -16,10 +16,19 @@
 // segment) adds the segment's partials -- thread t takes tiles t, t + 256, ... in order, then a fixed tree -- and writes the sum.
 // Neither order depends on where a row came from, only on its place in the group.
 //
+// Gaussian kernel (CMMD: Jayasumana et al. 2024, "Rethinking FID"; tise_mmd_rbf_grouped).  The same work list, tile and reductions
+// with another epilogue,
+//     k(a, b) = exp(-gamma d2(a, b)),      d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)
+// d2 by csrc/knn.hip's rule: a.b from the tile, |.|^2 from mmd_row_norm2_kernel (exact squares, that file's fixed order) into the
+// workspace, one double per group position of each side, parenthesised so that d2 of a pair is the same bits whichever side
+// each row is on.  exp is the fp64 library function.  Its cost against the tile's MFMA work has not been measured.
+//
 // Kernels
-//   mmd_poly3_tiles_kernel    bound: fp64 MFMA for d in the thousands (64 * 64 * 2 * d flop per tile against 2 * 64 * d * 4
-//                             bytes fetched, mostly from L2: the rows of a group are shared by all its tiles)
-//   mmd_poly3_reduce_kernel   bound: latency (8 bytes per tile)
+//   mmd_tiles_kernel<MMD_POLY3>   bound: fp64 MFMA for d in the thousands (64 * 64 * 2 * d flop per tile against 2 * 64 * d * 4
+//                                 bytes fetched, mostly from L2: the rows of a group are shared by all its tiles)
+//   mmd_tiles_kernel<MMD_RBF>     the same tile + 16 fp64 exp per thread; bound: not measured
+//   mmd_row_norm2_kernel          one wave per group position; bound: HBM (reads the rows once)
+//   mmd_reduce_kernel             bound: latency (8 bytes per tile)
 #include <vector>
 #include "common.h"
 #include "gemm_tile.h"
@@ -33,11 +42,45 @@ struct MmdSeg {
     int pad[2];
 };
 
-__global__ __launch_bounds__(256, 2) void mmd_poly3_tiles_kernel(const float* __restrict__ X, int64_t ldx,
-                                                                 const int64_t* __restrict__ ix, const float* __restrict__ Y,
-                                                                 int64_t ldy, const int64_t* __restrict__ iy, int d,
-                                                                 const MmdSeg* __restrict__ segs, int nseg,
-                                                                 double* __restrict__ partial) {
+enum { MMD_POLY3 = 0, MMD_RBF = 1 };
+
+// what the Gaussian epilogue needs beside the tile: |.|^2 of group position p of a side at norm[p - first position of that side]
+struct MmdRbf {
+    const double* nx;
+    const double* ny;
+    int64_t x0, y0;
+    double gamma;
+};
+
+// fp64 |row|^2 of every group position of both sides: wave w takes position w of the x side, or w - cx of the y side; lane l adds
+// the exact squares of columns l, l + 64, ... in order, then the fixed butterfly (knn_row_norm2_kernel's order)
+__global__ __launch_bounds__(256) void mmd_row_norm2_kernel(const float* __restrict__ X, int64_t ldx, const int64_t* __restrict__ ix,
+                                                            int64_t x0, int64_t cx, const float* __restrict__ Y, int64_t ldy,
+                                                            const int64_t* __restrict__ iy, int64_t y0, int64_t cy, int d,
+                                                            double* __restrict__ out) {
+    const int64_t w = (int64_t)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (w >= cx + cy) return;                                 // wave-uniform
+    const bool y = w >= cx;
+    const int64_t p = y ? y0 + (w - cx) : x0 + w;
+    const int64_t* idx = y ? iy : ix;
+    const int64_t r = idx ? idx[p] : p;
+    const float* row = (y ? Y : X) + r * (y ? ldy : ldx);
+    double s = 0.0;
+    for (int c = lane; c < d; c += 64) {
+        const double v = (double)row[c];
+        s += v * v;
+    }
+    s = wave_sum(s);
+    if (lane == 0) out[w] = s;
+}
+
+template <int KF>
+__global__ __launch_bounds__(256, 2) void mmd_tiles_kernel(const float* __restrict__ X, int64_t ldx,
+                                                           const int64_t* __restrict__ ix, const float* __restrict__ Y,
+                                                           int64_t ldy, const int64_t* __restrict__ iy, int d,
+                                                           const MmdSeg* __restrict__ segs, int nseg,
+                                                           double* __restrict__ partial, MmdRbf rbf) {
     __shared__ __attribute__((aligned(16))) float lds[GT_ROWS_LDS_FLOATS];
     const int bid = blockIdx.x;
     // the last segment whose first tile is <= bid (empty segments share their successor's number and are passed over)
@@ -72,23 +115,52 @@ __global__ __launch_bounds__(256, 2) void mmd_poly3_tiles_kernel(const float* __
         for (int b = 0; b < 2; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
     gemm_tile_64x64_rows_f32(fa, fb, d, acc, lds);
 
-    // epilogue on the accumulator registers: k = (dot / d + 1)^3 (a true division: 1 / d is not exact for d = 100 or 192 and
-    // its error would not average out over a sum of positive terms), rows / columns beyond the group and i == j masked
-    const double dd = (double)d;
     const bool diag = sym && tm == tn;
     double s = 0.0;
+    if constexpr (KF == MMD_POLY3) {
+        // epilogue on the accumulator registers: k = (dot / d + 1)^3 (a true division: 1 / d is not exact for d = 100 or 192 and
+        // its error would not average out over a sum of positive terms), rows / columns beyond the group and i == j masked
+        const double dd = (double)d;
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+        for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b)
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
+                    const int col = tn * 64 + wc * 32 + b * 16 + (lane & 15);
+                    const double v = acc[a][b][r] / dd + 1.0;
+                    const bool on = row < sg.na && col < sg.nb && !(diag && row == col);
+                    s += on ? v * v * v : 0.0;
+                }
+    } else {
+        // k = exp(-gamma d2) on the accumulator registers, d2 as csrc/knn.hip forms it; the same masks.  A row or column past
+        // the group reads its last position's norm (the tile fetched that row too) and is masked.
+        const double* norm_a = a_is_y ? rbf.ny + (sg.a0 - rbf.y0) : rbf.nx + (sg.a0 - rbf.x0);
+        const double* norm_b = b_is_x ? rbf.nx + (sg.b0 - rbf.x0) : rbf.ny + (sg.b0 - rbf.y0);
+        double na[2][4];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
-                const int col = tn * 64 + wc * 32 + b * 16 + (lane & 15);
-                const double v = acc[a][b][r] / dd + 1.0;
-                const bool on = row < sg.na && col < sg.nb && !(diag && row == col);
-                s += on ? v * v * v : 0.0;
+                na[a][r] = norm_a[row < sg.na ? row : sg.na - 1];
             }
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int col = tn * 64 + wc * 32 + b * 16 + (lane & 15);
+            const double nb = norm_b[col < sg.nb ? col : sg.nb - 1];
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
+                    const double d2 = fmax(0.0, (na[a][r] + nb) - 2.0 * acc[a][b][r]);
+                    const bool on = row < sg.na && col < sg.nb && !(diag && row == col);
+                    s += on ? exp(-rbf.gamma * d2) : 0.0;
+                }
+        }
+    }
     s = wave_sum(s);
     double* wsum = reinterpret_cast<double*>(lds);            // every wave is past the K loop's last barrier
     if (lane == 0) wsum[wave] = s;
@@ -99,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void mmd_poly3_tiles_kernel(const float* __
     }
 }
 
-__global__ __launch_bounds__(256) void mmd_poly3_reduce_kernel(const MmdSeg* __restrict__ segs, const double* __restrict__ partial,
+__global__ __launch_bounds__(256) void mmd_reduce_kernel(const MmdSeg* __restrict__ segs, const double* __restrict__ partial,
                                                                double* __restrict__ out) {
     __shared__ double sh[256];
     const int tile0 = segs[blockIdx.x].tile0, n = segs[blockIdx.x].ntiles;
@@ -174,11 +246,17 @@ static int mmd_side_check(const float* p, int64_t rows, int64_t ld, const int64_
     return TISE_OK;
 }
 
-int tise_mmd_poly3_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, const int64_t* index_x_dev, int64_t n_index_x,
-                           const int64_t* offsets_x_host, const float* y_dev, int64_t rows_y, int64_t ld_y,
-                           const int64_t* index_y_dev, int64_t n_index_y, const int64_t* offsets_y_host, int n_groups, int d,
-                           double* out_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+// rows of one side that enter some group: positions offsets[0] .. offsets[n_groups] - 1 (mmd_plan has checked the order)
+static int64_t mmd_used(const int64_t* off, int n_groups) { return n_groups > 0 ? off[n_groups] - off[0] : 0; }
+
+static size_t mmd_norm_offset(size_t table, int64_t total) { return table + (size_t)total * sizeof(double); }
+
+static int mmd_grouped(int kf, double gamma, const float* x_dev, int64_t rows_x, int64_t ld_x, const int64_t* index_x_dev,
+                       int64_t n_index_x, const int64_t* offsets_x_host, const float* y_dev, int64_t rows_y, int64_t ld_y,
+                       const int64_t* index_y_dev, int64_t n_index_y, const int64_t* offsets_y_host, int n_groups, int d,
+                       double* out_dev, void* ws_dev, size_t ws_bytes, void* stream) {
     if (d <= 0 || d > (1 << 20) || !out_dev) return TISE_ERR_INVALID_ARG;
+    if (kf == MMD_RBF && !(gamma >= 0.0 && gamma <= 1.7976931348623157e308)) return TISE_ERR_INVALID_ARG;   // NaN, inf, < 0
     std::vector<MmdSeg> segs;
     int64_t total = 0;
     int rc = mmd_plan(offsets_x_host, offsets_y_host, n_groups, &segs, &total);
@@ -189,7 +267,9 @@ int tise_mmd_poly3_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, con
     if (rc != TISE_OK) return rc;
     if (n_groups == 0) return TISE_OK;
     const size_t table = mmd_table_bytes(n_groups);
-    if (!ws_dev || (reinterpret_cast<uintptr_t>(ws_dev) & 7) || ws_bytes < table + (size_t)total * sizeof(double)) return TISE_ERR_INVALID_ARG;
+    const int64_t cx = kf == MMD_RBF ? mmd_used(offsets_x_host, n_groups) : 0, cy = kf == MMD_RBF ? mmd_used(offsets_y_host, n_groups) : 0;
+    const size_t need = mmd_norm_offset(table, total) + (size_t)(cx + cy) * sizeof(double);
+    if (!ws_dev || (reinterpret_cast<uintptr_t>(ws_dev) & 7) || ws_bytes < need) return TISE_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     MmdSeg* segs_dev = reinterpret_cast<MmdSeg*>(ws_dev);
     double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(ws_dev) + table);
@@ -197,14 +277,52 @@ int tise_mmd_poly3_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, con
     TISE_HIP_CHECK(hipMemcpyAsync(segs_dev, segs.data(), segs.size() * sizeof(MmdSeg), hipMemcpyHostToDevice, st));
     TISE_HIP_CHECK(hipStreamSynchronize(st));
     const int nseg = 3 * n_groups;
+    MmdRbf rbf = {nullptr, nullptr, 0, 0, 0.0};
+    if (kf == MMD_RBF) {
+        double* norm = partial + total;
+        rbf = {norm, norm + cx, offsets_x_host[0], offsets_y_host[0], gamma};
+        if (cx + cy > 0) {
+            hipLaunchKernelGGL(mmd_row_norm2_kernel, dim3((unsigned)((cx + cy + 3) / 4)), dim3(256), 0, st, x_dev, ld_x, index_x_dev,
+                               rbf.x0, cx, y_dev, ld_y, index_y_dev, rbf.y0, cy, d, norm);
+            TISE_LAUNCH_CHECK();
+        }
+    }
     if (total > 0) {
-        hipLaunchKernelGGL(mmd_poly3_tiles_kernel, dim3((unsigned)total), dim3(256), 0, st, x_dev, ld_x, index_x_dev, y_dev, ld_y,
-                           index_y_dev, d, segs_dev, nseg, partial);
+        if (kf == MMD_RBF)
+            hipLaunchKernelGGL(mmd_tiles_kernel<MMD_RBF>, dim3((unsigned)total), dim3(256), 0, st, x_dev, ld_x, index_x_dev, y_dev, ld_y,
+                               index_y_dev, d, segs_dev, nseg, partial, rbf);
+        else
+            hipLaunchKernelGGL(mmd_tiles_kernel<MMD_POLY3>, dim3((unsigned)total), dim3(256), 0, st, x_dev, ld_x, index_x_dev, y_dev, ld_y,
+                               index_y_dev, d, segs_dev, nseg, partial, rbf);
         TISE_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(mmd_poly3_reduce_kernel, dim3(nseg), dim3(256), 0, st, segs_dev, partial, out_dev);
+    hipLaunchKernelGGL(mmd_reduce_kernel, dim3(nseg), dim3(256), 0, st, segs_dev, partial, out_dev);
     TISE_LAUNCH_CHECK();
     return TISE_OK;
+}
+
+int tise_mmd_poly3_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, const int64_t* index_x_dev, int64_t n_index_x,
+                           const int64_t* offsets_x_host, const float* y_dev, int64_t rows_y, int64_t ld_y,
+                           const int64_t* index_y_dev, int64_t n_index_y, const int64_t* offsets_y_host, int n_groups, int d,
+                           double* out_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+    return mmd_grouped(MMD_POLY3, 0.0, x_dev, rows_x, ld_x, index_x_dev, n_index_x, offsets_x_host, y_dev, rows_y, ld_y, index_y_dev,
+                       n_index_y, offsets_y_host, n_groups, d, out_dev, ws_dev, ws_bytes, stream);
+}
+
+// workspace = the polynomial kernel's + one double per row that enters a group, per side (the squared norms)
+int tise_mmd_rbf_workspace_bytes(const int64_t* offsets_x_host, const int64_t* offsets_y_host, int n_groups, size_t* bytes) {
+    const int rc = tise_mmd_poly3_workspace_bytes(offsets_x_host, offsets_y_host, n_groups, bytes);
+    if (rc != TISE_OK) return rc;
+    *bytes += (size_t)(mmd_used(offsets_x_host, n_groups) + mmd_used(offsets_y_host, n_groups)) * sizeof(double);
+    return TISE_OK;
+}
+
+int tise_mmd_rbf_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, const int64_t* index_x_dev, int64_t n_index_x,
+                         const int64_t* offsets_x_host, const float* y_dev, int64_t rows_y, int64_t ld_y,
+                         const int64_t* index_y_dev, int64_t n_index_y, const int64_t* offsets_y_host, int n_groups, int d,
+                         double gamma, double* out_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+    return mmd_grouped(MMD_RBF, gamma, x_dev, rows_x, ld_x, index_x_dev, n_index_x, offsets_x_host, y_dev, rows_y, ld_y, index_y_dev,
+                       n_index_y, offsets_y_host, n_groups, d, out_dev, ws_dev, ws_bytes, stream);
 }
 
 }  // extern "C"

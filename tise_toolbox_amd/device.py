@@ -441,15 +441,20 @@ def _rows_side(t, what):
     return t
 
 
-class PolynomialMMD:
-    """Grouped sums of the KID kernel k(a, b) = (a.b / d + 1)^3 on resident fp32 rows (tise_mmd_poly3_grouped in
-    include/tise_hip.h): every group's Sxx, Syy, Sxy from one launch pair, bitwise reproducible."""
+class _GroupedMMD:
+    """What the grouped kernel-sum entry points of csrc/mmd.hip share on this side: the workspace, the host checks and ``sums``."""
+
+    _FN = None                                                    # C ABI prefix: <_FN>_workspace_bytes, <_FN>_grouped
 
     def __init__(self, device=None):
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
-            raise _lib.TiseLibraryError("PolynomialMMD needs a HIP device")
+            raise _lib.TiseLibraryError(f"{type(self).__name__} needs a HIP device")
         self._ws = None
+
+    def _kernel_args(self):
+        """The kernel function's own arguments, between ``d`` and ``out_dev`` in the C signature."""
+        return ()
 
     def _side(self, t, what):
         return _rows_side(t, what)
@@ -479,15 +484,23 @@ class PolynomialMMD:
             pox = ox.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
             poy = oy.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
             nbytes = ctypes.c_size_t()
-            _lib.call("tise_mmd_poly3_workspace_bytes", pox, poy, ng, ctypes.byref(nbytes))
+            _lib.call(self._FN + "_workspace_bytes", pox, poy, ng, ctypes.byref(nbytes))
             if self._ws is None or self._ws.numel() < nbytes.value:
                 self._ws = torch.empty(max(256, nbytes.value), dtype=torch.uint8, device=self.device)
-            _lib.call("tise_mmd_poly3_grouped",
+            _lib.call(self._FN + "_grouped",
                       _ptr(X), X.shape[0], X.stride(0) if X.shape[0] else X.shape[1] + (-X.shape[1]) % 4, _ptr(ixd) if ixd is not None else None,
                       ix.size if ix is not None else 0, pox,
                       _ptr(Y), Y.shape[0], Y.stride(0) if Y.shape[0] else Y.shape[1] + (-Y.shape[1]) % 4, _ptr(iyd) if iyd is not None else None,
-                      iy.size if iy is not None else 0, poy, ng, int(X.shape[1]), _ptr(out), _ptr(self._ws), self._ws.numel(), _stream())
+                      iy.size if iy is not None else 0, poy, ng, int(X.shape[1]), *self._kernel_args(), _ptr(out), _ptr(self._ws),
+                      self._ws.numel(), _stream())
         return out
+
+
+class PolynomialMMD(_GroupedMMD):
+    """Grouped sums of the KID kernel k(a, b) = (a.b / d + 1)^3 on resident fp32 rows (tise_mmd_poly3_grouped in
+    include/tise_hip.h): every group's Sxx, Syy, Sxy from one launch pair, bitwise reproducible."""
+
+    _FN = "tise_mmd_poly3"
 
     def mmd2(self, X, Y, offsets_x, offsets_y, index_x=None, index_y=None):
         """The unbiased estimator per group, Sxx / (n (n - 1)) + Syy / (m (m - 1)) - 2 Sxy / (n m): (n_groups,) fp64 CUDA tensor;
@@ -497,6 +510,23 @@ class PolynomialMMD:
         m = torch.from_numpy(self.last_counts[1].astype(np.float64)).to(self.device)
         v = s[:, 0] / (n * (n - 1.0)) + s[:, 1] / (m * (m - 1.0)) - 2.0 * s[:, 2] / (n * m)
         return torch.where((n < 2) | (m < 2), torch.full_like(v, float("nan")), v)
+
+
+class GaussianMMD(_GroupedMMD):
+    """Grouped sums of the Gaussian kernel k(a, b) = exp(-gamma |a - b|^2) on resident fp32 rows (tise_mmd_rbf_grouped in
+    include/tise_hip.h): the kernel of CMMD (cmmd.py).  ``sums`` is PolynomialMMD's, argument for argument; the estimators over
+    the sums are cmmd.cmmd_from_sums."""
+
+    _FN = "tise_mmd_rbf"
+
+    def __init__(self, device=None, gamma=None):
+        if gamma is None or not np.isfinite(gamma) or gamma < 0:
+            raise ValueError(f"gamma must be finite and >= 0 (got {gamma})")
+        super().__init__(device)
+        self.gamma = float(gamma)
+
+    def _kernel_args(self):
+        return (ctypes.c_double(self.gamma),)
 
 
 class KnnManifold:
