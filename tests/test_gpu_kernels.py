@@ -1103,8 +1103,11 @@ def test_split_format_small_value_floor(dev):
 
 
 def test_split_overflow_guard_fires_and_clears(dev):
-    """A value above 65504 (or a NaN) converted into a split tensor raises the device flag: conv epilogue, stem, and the
-    engine turns it into FloatingPointError instead of silently carrying +inf through the trunk."""
+    """A value above 65504 converted into a split tensor raises the device flag: conv epilogue, stem, and the
+    engine turns it into FloatingPointError instead of silently carrying +inf through the trunk.  (A NaN does NOT raise it
+    at these sites -- their ReLU, fmaxf, turns it into 0 first; it reaches the guard's maximum only in split_mean.  The
+    trunks refuse non-finite parameters instead, and elsewhere a NaN can only follow an overflow, which raises the flag
+    first: tests/test_gpu_nonfinite.py.)"""
     from tise_toolbox_amd import device
     from tise_toolbox_amd.conv_split import SplitConv, merge, split
     device.read_split_overflow()

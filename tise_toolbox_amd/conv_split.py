@@ -149,9 +149,16 @@ class SplitConv:
     # measurement hook (bench.py): when a list, every launch appends (start_event, end_event, flop)
     timer = None
 
-    def __init__(self, weight, bias, stride, padding, device, tn=None, variant=None, pipe_cfg=None, korder=None):
-        """weight: (Cout, Cin, KH, KW) fp32 (BatchNorm already folded), bias: (Cout,) fp32."""
+    def __init__(self, weight, bias, stride, padding, device, tn=None, variant=None, pipe_cfg=None, korder=None, name=None,
+                 check=True):
+        """weight: (Cout, Cin, KH, KW) fp32 (BatchNorm already folded), bias: (Cout,) fp32.
+        Non-finite parameters are refused (ValueError naming ``name``): the epilogue's ReLU is max(v, 0) on a NaN-ignoring
+        v_max, so a NaN weight or bias would leave as 0 and the range guard would never see it (csrc/common.h).
+        ``check=False``: the caller has checked them already (the trunks do it for all layers with one device read)."""
         cout, cin, kh, kw = weight.shape
+        if check and not (bool(torch.isfinite(weight).all()) and bool(torch.isfinite(bias).all())):
+            raise ValueError(f"SplitConv{' ' + name if name else ''} ({cout} x {cin} x {kh} x {kw}): non-finite value (NaN or Inf) "
+                             "in the folded weights or bias")
         assert cin % 16 == 0 and cin >= 32, "conv_split needs Cin % 16 == 0 and Cin >= 32"
         self.cout, self.cin, self.kh, self.kw = cout, cin, kh, kw
         self.stride = tuple(stride)
@@ -285,12 +292,12 @@ class SplitConv:
             # rows so short that the window of a 128-pixel tile needs more than the kernel's six pieces per wave (OW < 7
             # at KW = 3): the default kernel serves the layer from its own packing, built on first use
             if self._fallback is None:
-                self._fallback = SplitConv(self._orig[0], self._orig[1], self.stride, self.padding, x.device, tn=self.tn, variant="fast")
+                self._fallback = SplitConv(self._orig[0], self._orig[1], self.stride, self.padding, x.device, tn=self.tn, variant="fast", check=False)
             return self._fallback(x, segs)
         if self.pipe_cfg is not None and out_pad is None and not pipe_fits(w, self.cout):
             # image rows so long that the sliding ring does not fit the LDS (W > ~230): the default kernel, built on first use
             if self._fallback is None:
-                self._fallback = SplitConv(self._orig[0], self._orig[1], self.stride, self.padding, x.device, variant="fast")
+                self._fallback = SplitConv(self._orig[0], self._orig[1], self.stride, self.padding, x.device, variant="fast", check=False)
             return self._fallback(x, segs)
         a = ConvArgs()
         a.x = x.data_ptr()

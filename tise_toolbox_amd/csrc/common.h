@@ -83,13 +83,20 @@ __host__ __device__ inline int tise_ilv_second(int c, int C) { return c < (C & ~
 // kernel that WRITES split tensors keeps the running maximum of what it converts (one v_max per element; all values
 // are post-ReLU, i.e. >= 0) and raises bit 0 of a per-device word when it exceeds the range; the host reads and
 // clears the words with tise_split_overflow_check (capi.hip; the Python mirror raises FloatingPointError).
+// What the guard does NOT see: a NaN.  The writers form v = fmaxf(pre + bias, 0) and vmax = fmaxf(vmax, v), and fmaxf
+// returns the operand that is not NaN, so a NaN leaves the ReLU as 0 and never reaches the running maximum (the split
+// max-pools drop a NaN tap the same way).  Only split_mean (trunk_ops.hip) keeps its maximum with a comparison that a NaN
+// fails, so a NaN input raises the flag there.  That is sufficient because the host refuses non-finite weights, scales,
+// biases and input tables (trunk.py require_finite_params, conv_split.SplitConv, inception.require_finite_state_dict): the
+// network input is a table look-up of a byte, so with finite parameters the first non-finite value of a pass can only be
+// an fp32 result beyond the fp16 range, and that one raises the flag before the NaN (hi = +inf, lo = -inf) it turns into.
 // The library is built without relocatable device code, so each translation unit has its OWN word (unnamed
 // namespace) and exports a reader for it with TISE_DEFINE_SPLIT_FLAG_READER.
 #define TISE_F16_MAX 65504.0f
 namespace {
 __device__ int g_tise_split_overflow_tu;
 __device__ __forceinline__ void tise_flag_split_overflow(float running_max) {
-    if (!(running_max <= TISE_F16_MAX)) atomicOr(&g_tise_split_overflow_tu, 1);     // also catches NaN
+    if (!(running_max <= TISE_F16_MAX)) atomicOr(&g_tise_split_overflow_tu, 1);     // (a NaN maximum would raise it too: only split_mean can pass one)
 }
 }  // namespace
 #define TISE_DEFINE_SPLIT_FLAG_READER(NAME)                                                                          \

@@ -557,7 +557,9 @@ __global__ __launch_bounds__(256) void split_mean_kernel(const _Float16* __restr
             const _Float16 h = (_Float16)v;
             oh[i] = h;
             ol[i] = (_Float16)((v - (float)h) * 2048.f);
-            vmax = (fabsf(v) <= vmax) ? vmax : fabsf(v);          // a NaN lands in vmax (the comparison fails) and raises the flag
+            // a NaN lands in vmax (the comparison fails) and STAYS there (a later finite value fails the comparison against a NaN
+            // maximum too, and used to replace it: only a NaN in a thread's last channel reached the flag)
+            vmax = (fabsf(v) <= vmax) ? vmax : (vmax != vmax ? vmax : fabsf(v));
         }
     }
     if (SPLIT_OUT) {

@@ -296,8 +296,10 @@ def resize_ragged_u8(crops, out_hw=(299, 299), out=None, filter="bilinear"):
 
 def read_split_overflow():
     """Read-and-clear the range guard of the split-fp16 activation format (csrc/common.h): True when any kernel
-    since the last read converted a value above the fp16 range (65504) or a NaN into a split tensor.  Synchronises
-    the current stream."""
+    since the last read converted a value above the fp16 range (65504) into a split tensor.  A NaN raises it only in
+    split_mean (the pool3 row); every other writer's ReLU turns a NaN into 0 first -- the trunks refuse non-finite parameters
+    for that reason, and with finite parameters a NaN can only follow an overflow, which raises the flag.  Synchronises the
+    current stream."""
     flag = ctypes.c_int(0)
     _lib.call("tise_split_overflow_check", ctypes.byref(flag), _stream())
     return bool(flag.value)
@@ -309,7 +311,7 @@ def check_split_overflow(what="InceptionV3 trunk", flag=None):
         flag = read_split_overflow()
     if flag:
         raise FloatingPointError(
-            f"{what}: an activation exceeded the fp16 range of the split-precision format (|v| > 65504) or was NaN; "
+            f"{what}: an activation exceeded the fp16 range of the split-precision format (|v| > 65504); "
             "the CLIs finish such a job on the exact-fp32 path by themselves (engine.run_with_exact_fallback); library callers: "
             "TISE_CONV=miopen / --conv exact")
 

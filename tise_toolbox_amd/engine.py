@@ -101,6 +101,8 @@ class RealismEngine:
         if lut is None:
             lut = device.make_lut(normalize_input=getattr(self.model, "normalize_input", True),
                                   network=getattr(self.model, "network", "torchvision"))
+        if not np.isfinite(np.asarray(lut, dtype=np.float32)).all():
+            raise ValueError("input table (lut): non-finite value (NaN or Inf) in the byte -> network input table of the stem layer")
         self.lut = lut
         # MIOpen convs + hand-written HIP epilogues (trunk.py); TISE_FUSED_TRUNK=0 runs the plain module graph
         self.fused = None

@@ -445,6 +445,19 @@ def _materialize_(net):
     return net
 
 
+def require_finite_state_dict(sd, source):
+    """Refuse a checkpoint with a NaN or an Inf in a tensor the pool3 features or the logits depend on (``AuxLogits`` is
+    not evaluated): ``ValueError`` naming the tensor, and with it the layer.  The reference would print a NaN score for such
+    a file (torch.relu propagates NaN); the trunk's fused ReLUs are max(v, 0) on a NaN-ignoring v_max and would turn the
+    NaN into 0 -- finite, wrong features and no message (csrc/common.h) -- so the file is refused where it is read."""
+    for key, t in sd.items():
+        if torch.is_tensor(t) and t.is_floating_point() and not key.startswith("AuxLogits.") and not bool(torch.isfinite(t).all()):
+            n_bad = int((~torch.isfinite(t)).sum())
+            raise ValueError(f"{source}: tensor {key} (layer {key.rsplit('.', 1)[0]}) holds {n_bad} non-finite value(s) "
+                             "(NaN or Inf); refusing the checkpoint")
+    return sd
+
+
 def build_inception3(weights=None, num_classes=None, seed=0, calibration="fid", network="torchvision"):
     """Construct ``Inception3`` and load ``weights`` (a torchvision-format state_dict
     path) or, when ``weights`` is None, the seeded stand-in parameters.
@@ -466,12 +479,13 @@ def build_inception3(weights=None, num_classes=None, seed=0, calibration="fid", 
     with torch.device("meta"), _no_default_init():
         net = Inception3(num_classes=num_classes, aux_logits=network == "torchvision", network=network)
     if weights is not None and network == "slim":
-        net.load_state_dict(load_slim_checkpoint(weights, net), strict=True, assign=True)
+        net.load_state_dict(require_finite_state_dict(load_slim_checkpoint(weights, net), weights), strict=True, assign=True)
     elif weights is not None:
         sd = torch.load(weights, map_location="cpu")
         if isinstance(sd, dict) and "state_dict" in sd:
             sd = sd["state_dict"]
         net.load_state_dict(sd, strict=True, assign=True)
+        require_finite_state_dict(net.state_dict(), weights)
     else:
         seeded_init_(net, seed, calibration)
         if any(p.is_meta for p in net.parameters()):        # a rank other than 0 of a multi-process run: rank 0 broadcasts

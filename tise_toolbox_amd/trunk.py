@@ -45,18 +45,45 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def finite_flag(*tensors):
+    """0-dim bool tensor, on the tensors' device: every value of every tensor is finite (no host synchronisation)."""
+    f = torch.isfinite(tensors[0]).all()
+    for t in tensors[1:]:
+        f = f & torch.isfinite(t).all()
+    return f
+
+
+def require_finite_params(names, flags, device, what="InceptionV3 trunk"):
+    """Refuse non-finite parameters with ONE device->host read for the whole network: ``flags[i]`` (finite_flag) belongs to
+    the layer ``names[i]``.  Every fused ReLU of the trunk is max(v, 0) on a NaN-ignoring v_max -- a NaN that enters through
+    a weight, a BatchNorm scale or a bias would leave as 0, on the split and on the exact path alike, and the range guard
+    (csrc/common.h) never sees it -- so the parameters are checked where the trunks take them."""
+    if not flags:
+        return
+    ok = torch.stack([f.to(device) for f in flags]).cpu().tolist()
+    bad = [n for n, f in zip(names, ok) if not f]
+    if bad:
+        raise ValueError(f"{what}: non-finite value (NaN or Inf) in the BatchNorm-folded parameters of layer {bad[0]}"
+                         + (f" (and {len(bad) - 1} more: {', '.join(bad[1:4])}{' ...' if len(bad) > 4 else ''})" if len(bad) > 1 else "")
+                         + "; the trunk's fused ReLUs would turn a NaN into 0 silently, so the checkpoint is refused")
+
+
 class _Conv:
-    """Folded conv parameters on the device: weight (Cout,Cin,kh,kw) channels-last, bias (Cout,)."""
+    """Folded conv parameters on the device: weight (Cout,Cin,kh,kw) channels-last, bias (Cout,).  ``finite``: one
+    finite_flag per module of ``mods`` (their folded weight, scale and bias), read by require_finite_params."""
 
-    __slots__ = ("w", "b", "stride", "padding", "cout")
+    __slots__ = ("w", "b", "stride", "padding", "cout", "names", "finite")
 
-    def __init__(self, mods, device):
+    def __init__(self, mods, device, names=None):
         ws, bs = [], []
+        self.names = list(names) if names is not None else [f"conv{i}" for i in range(len(mods))]
+        self.finite = []
         for m in mods:
             bn = m.bn
             scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
             ws.append(m.conv.weight * scale.view(-1, 1, 1, 1))
             bs.append(bn.bias - bn.running_mean * scale)
+            self.finite.append(finite_flag(ws[-1], scale, bs[-1]))
         m0 = mods[0].conv
         for m in mods[1:]:
             assert m.conv.kernel_size == m0.kernel_size and m.conv.stride == m0.stride and m.conv.padding == m0.padding
@@ -75,10 +102,14 @@ class FusedTrunk:
         with torch.no_grad():
             mods = dict(model.named_modules())
 
+            checked = []
+
             def conv(*names):
                 ms = [mods[n] for n in names]
                 assert all(isinstance(m, BasicConv2d) for m in ms)
-                return _Conv(ms, self.device)
+                c = _Conv(ms, self.device, names)
+                checked.append(c)
+                return c
 
             b0, b1, b2, b3 = "blocks.0.", "blocks.1.", "blocks.2.", "blocks.3."
             self.network = getattr(model, "network", "torchvision")
@@ -97,6 +128,13 @@ class FusedTrunk:
             if self.last_block >= 3:
                 for i, kind in enumerate("DEE"):
                     self.blocks.append((kind, self._block_params(kind, b3 + str(i) + ".", conv, mods)))
+            names = [n for c in checked for n in c.names]
+            flags = [f for c in checked for f in c.finite]
+            fc = getattr(model, "fc", None)
+            if fc is not None and not fc.weight.is_meta:        # the classifier layer (IS* logits)
+                names.append("fc")
+                flags.append(finite_flag(fc.weight, *([fc.bias] if fc.bias is not None else [])))
+            require_finite_params(names, flags, self.device)
 
     def _block_params(self, kind, p, conv, mods):
         pool = getattr(mods[p[:-1]], "pool", None)
@@ -311,8 +349,8 @@ class SplitTrunk(FusedTrunk):
         super().__init__(model, device)
         from .conv_split import SplitConv
 
-        def sc(c):
-            return SplitConv(c.w, c.b, c.stride, c.padding, self.device)
+        def sc(c):                                              # c's parameters were checked by FusedTrunk.__init__
+            return SplitConv(c.w, c.b, c.stride, c.padding, self.device, check=False)
 
         self.s2a, self.s2b = sc(self.c2a), sc(self.c2b)
         if self.last_block >= 1:
@@ -323,13 +361,13 @@ class SplitTrunk(FusedTrunk):
         # filter of 32 couts in registers (conv_pipe.hip configuration 34): the input streams through a sliding LDS ring
         # once, nothing else moves.  TISE_CONV_REGW=0: the default kernels (2a: fast, 2b: row window)
         if os.environ.get("TISE_CONV_VARIANT", "auto") in ("auto", "fast") and os.environ.get("TISE_CONV_REGW", "1") != "0":
-            self.s2a = SplitConv(self.c2a.w, self.c2a.b, self.c2a.stride, self.c2a.padding, self.device, variant="pipe", pipe_cfg=34)
+            self.s2a = SplitConv(self.c2a.w, self.c2a.b, self.c2a.stride, self.c2a.padding, self.device, variant="pipe", pipe_cfg=34, check=False)
             # Conv2d_2b's zero padding made physical: Conv2d_2a writes into the interior of a zero-bordered buffer (out_pad)
             # and Conv2d_2b runs as a VALID convolution over it -- no per-lane tap masks in the kernel (bit-identical:
             # the masked taps contributed zeros).  TISE_CONV_PADBUF=0: the padded kernel instance on the plain tensor
             self.pad2b = os.environ.get("TISE_CONV_PADBUF", "1") != "0" and tuple(self.c2b.padding) == (1, 1)
             self.s2b = SplitConv(self.c2b.w, self.c2b.b, self.c2b.stride, (0, 0) if self.pad2b else self.c2b.padding,
-                                 self.device, variant="pipe", pipe_cfg=34)
+                                 self.device, variant="pipe", pipe_cfg=34, check=False)
         # stem weights for the direct kernel: [kh][kw][cin][cout] fp32
         self.stem_w = self.c1a.w.permute(2, 3, 1, 0).contiguous().float()
         assert tuple(self.stem_w.shape) == (3, 3, 3, 32) and self.c1a.stride == (2, 2) and self.c1a.padding == (0, 0)
@@ -360,7 +398,7 @@ class SplitTrunk(FusedTrunk):
         fc = getattr(model, "fc", None)
         if (self.last_block == 3 and fc is not None and fc.in_features % 32 == 0 and os.environ.get("TISE_FC", "hip") == "hip"):
             w = fc.weight.detach().float().reshape(fc.out_features, fc.in_features, 1, 1)
-            self.sfc = SplitConv(w, torch.zeros(fc.out_features), (1, 1), (0, 0), self.device, variant="fast")
+            self.sfc = SplitConv(w, torch.zeros(fc.out_features), (1, 1), (0, 0), self.device, variant="fast", check=False)
             self.fc_bias = fc.bias.detach().float().to(self.device) if fc.bias is not None else None
 
     def fc_logits(self, n, bias=False):
@@ -548,7 +586,7 @@ class SplitTrunk(FusedTrunk):
         if self.pad2b and not (pipe_fits(w, self.s2a.cout) and pipe_fits(ow + 2, self.s2b.cout)):
             # inputs wider than the sliding-window kernels' LDS ring (never the 299 x 299 network input): default kernels
             if getattr(self, "_s2b_wide", None) is None:
-                self._s2b_wide = SplitConv(self.c2b.w, self.c2b.b, self.c2b.stride, self.c2b.padding, self.device, variant="fast")
+                self._s2b_wide = SplitConv(self.c2b.w, self.c2b.b, self.c2b.stride, self.c2b.padding, self.device, variant="fast", check=False)
             a = self._sconv(self._s2b_wide, self._sconv(self.s2a, a))
         elif self.pad2b:
             from .conv_split import pool_output_fits
