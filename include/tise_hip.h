@@ -218,7 +218,7 @@ int tise_mmd_poly3_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, con
 
 /* ------------------------------------------------------------------------------------------
  * CLIP maximum mean discrepancy (CMMD; Jayasumana et al. 2024, "Rethinking FID"): grouped sums of the Gaussian kernel (csrc/mmd.hip)
- *     k(a, b) = exp(-gamma d2(a, b)),      d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)
+ *     k(a, b) = exp(-gamma d2(a, b)),      d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)      (NaN stays NaN: "Non-finite feature rows" below)
  * No counterpart in the reference; the published implementation forms the three n x n kernel matrices in fp32.  The interface is
  * tise_mmd_poly3_grouped's, argument for argument, plus gamma, and so are the outputs (Sxx and Syy over i != j, Sxy over all pairs),
  * the single launch over exactly the 64 x 64 tiles that exist, the fixed-order reduction launch after it, and the guarantee: no
@@ -263,6 +263,20 @@ int tise_mmd_rbf_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, const
  * Rejected before any HIP call (TISE_ERR_INVALID_ARG): a NULL pointer, k outside 1 .. 16, rows < k + 1, d <= 0, ld < d,
  * ld % 4 != 0, a feature base that is not 16-byte aligned, col_splits outside 0 .. 1024, a workspace too small or misaligned.
  * TISE_ERR_UNSUPPORTED: more than 2^24 rows.
+ * Non-finite feature rows (this block and tise_mmd_rbf_grouped / tise_mmd_poly3_grouped above).  A row that holds a NaN or an
+ * infinity is a legal input with a defined result; nothing is rejected and nothing is clamped away.  Its |.|^2 is stored as NaN
+ * and the clamp of d2 keeps a NaN (max(0, NaN) is NaN here, not 0), so d2 of every pair with such a row is NaN:
+ *   tise_knn_radius2 / tise_prdc_counts: every IEEE comparison with NaN is false, so the pair is never a neighbour candidate and
+ *     never inside a ball.  The row itself gets r2 = NaN, cnt = 0, rec = 0, prec = 0; every other row gets exactly the results
+ *     of the same call on the sets WITHOUT that row (the caller must leave k + 1 finite rows for them to be meaningful;
+ *     r2 = +inf where fewer than k finite other rows exist).  A NaN in r2_r_dev / r2_f_dev is a ball that holds nothing.
+ *   tise_mmd_rbf_grouped: k = exp(-gamma NaN) = NaN for the pair, at every gamma including 0.  tise_mmd_poly3_grouped forms no
+ *     d2: a.b, hence k, is NaN or +-inf by IEEE arithmetic.  In both, every sum of a group that has a pair with the row is
+ *     non-finite -- Sxx and Sxy when the row is in X, Syy and Sxy when it is in Y -- while the group's third sum and EVERY other
+ *     group of the launch have the bits of the same launch on finite rows (rows past a group's end are fetched from its last
+ *     row and masked by selection, never by multiplication).
+ * For finite rows neither rule changes a bit.  tise_toolbox_amd.prdc.prdc_from_features turns the NaN radii into a ValueError
+ * (as the prdc package refuses such input); cmmd and kid return the NaN, as their reference implementations do.
  * ------------------------------------------------------------------------------------------ */
 int tise_knn_workspace_bytes(int64_t rows, int k, int col_splits, size_t* bytes);
 int tise_knn_radius2(const float* x_dev, int64_t rows, int64_t ld, int d, int k, int col_splits, double* r2_dev, void* ws_dev,

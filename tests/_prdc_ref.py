@@ -64,3 +64,25 @@ def smallest_margin(ref):
     a = np.abs(cross - ref["r2_real"][:, None].astype(np.float64)) / ref["r2_real"][:, None].astype(np.float64)
     b = np.abs(cross - ref["r2_fake"][None, :].astype(np.float64)) / ref["r2_fake"][None, :].astype(np.float64)
     return float(min(a.min(), b.min()))
+
+
+def nonfinite_rows(a):
+    """Indices of the rows that hold a NaN or an infinity."""
+    return np.flatnonzero(~np.isfinite(np.asarray(a, dtype=np.float64)).all(axis=1))
+
+
+def prdc_dropping_nonfinite(real, fake, k, d2=d2_expansion):
+    """The kernels' rule for rows that hold a NaN or an infinity (include/tise_hip.h), stated through the clean definition: such
+    a row is nobody's neighbour and lies in no ball, so every other row's r2, cnt, rec and prec are those of ``prdc`` on the sets
+    WITHOUT these rows; the row itself gets r2 = NaN, cnt = 0, rec = False, prec = False.  -> dict of full-size cnt, rec, prec,
+    r2_real, r2_fake and the clean sub-problem's result under "clean".  (For a NaN -- not for an infinity -- plain ``prdc`` on the
+    dirty input gives the same arrays: np.maximum keeps a NaN, np.sort puts it last and every comparison with it is False.)"""
+    real, fake = np.asarray(real), np.asarray(fake)
+    bad_r, bad_f = nonfinite_rows(real), nonfinite_rows(fake)
+    keep_r, keep_f = np.setdiff1d(np.arange(len(real)), bad_r), np.setdiff1d(np.arange(len(fake)), bad_f)
+    clean = prdc(real[keep_r], fake[keep_f], k, d2)
+    out = dict(cnt=np.zeros(len(real), np.int64), rec=np.zeros(len(real), bool), prec=np.zeros(len(fake), bool),
+               r2_real=np.full(len(real), np.nan), r2_fake=np.full(len(fake), np.nan), clean=clean)
+    out["cnt"][keep_r], out["rec"][keep_r], out["r2_real"][keep_r] = clean["cnt"], clean["rec"], clean["r2_real"]
+    out["prec"][keep_f], out["r2_fake"][keep_f] = clean["prec"], clean["r2_fake"]
+    return out

@@ -192,3 +192,49 @@ def test_gaussian_mmd_refuses_a_host_device_and_a_bad_gamma():
     for g in (None, float("nan"), -0.5, float("inf")):
         with pytest.raises(ValueError):
             device.GaussianMMD("cuda", g)
+
+
+# ---- the gathered-row tile's width sweep and the non-finite rule: the oracle's side, checked without a GPU ----------------------
+def test_recorded_spread_covers_the_width_sweep():
+    from tests import test_gpu_cmmd
+    worst = test_gpu_cmmd.measure_spread(test_gpu_cmmd.sweep_cases())
+    assert list(worst) == ["the rest"] and worst["the rest"][1] <= test_gpu_cmmd.REL_SPREAD
+    assert test_gpu_cmmd.REL_TOL == 8 * test_gpu_cmmd.REL_SPREAD
+
+
+def test_reference_sums_at_gamma_zero_count_the_pairs():
+    from tests import _rows_tile_cases as tc
+    want = tc.census_expected()
+    for g, (n, m) in enumerate(zip(tc.CENSUS_SIZES_X, tc.CENSUS_SIZES_Y)):
+        assert list(_cmmd_ref.rbf_sums(tc.pool3_like(n, 3, 1), tc.pool3_like(m, 3, 2), 0.0)) == list(want[g])
+
+
+@pytest.mark.parametrize("value", [float("nan"), float("inf"), float("-inf")])
+def test_reference_is_nan_for_a_non_finite_row_and_only_where_the_row_enters(value):
+    """numpy's semantics (np.maximum keeps a NaN where fmax drops it), which the kernel has to match; the textbook forms on full
+    kernel matrices -- the published implementation's arithmetic -- return NaN as well."""
+    from tests import _rows_tile_cases as tc
+    X, Y = tc.mmd_rows(67, "unit")
+    sums = lambda xs, ys: _cmmd_ref.rbf_sums(xs, ys, 1 / 200)
+    clean = tc.group_sums(sums, X, Y)
+    for side, g, pos in tc.mmd_bad_rows():
+        row = int((tc.MMD_OX if side == "x" else tc.MMD_OY)[g]) + pos
+        Xb = tc.with_bad_row(X, row, value) if side == "x" else X
+        Yb = tc.with_bad_row(Y, row, value) if side == "y" else Y
+        with np.errstate(invalid="ignore"):
+            got = tc.group_sums(sums, Xb, Yb)
+        hit = np.zeros(clean.shape, bool)
+        hit[g, [0, 2] if side == "x" else [1, 2]] = True
+        assert not np.any(np.isfinite(got[hit])) and got[~hit].tobytes() == clean[~hit].tobytes(), (side, g, pos)
+        with np.errstate(invalid="ignore"):
+            assert np.isnan(_cmmd_ref.cmmd_v(Xb, Yb)) and np.isnan(_cmmd_ref.cmmd_u(Xb, Yb))
+
+
+def test_an_all_zero_row_becomes_nan_in_normalize_rows_and_in_the_value():
+    import torch
+    from tise_toolbox_amd import cmmd
+    x = torch.ones((3, 4))
+    x[1] = 0
+    n = cmmd.normalize_rows(x)
+    assert bool(torch.isnan(n[1]).all()) and bool(torch.isfinite(n[[0, 2]]).all())
+    assert np.isnan(cmmd.cmmd_from_sums((float("nan"), 1.0, float("nan")), 3, 3))

@@ -7,6 +7,7 @@ relative difference between the two over all groups and all three sums, per fami
 
     unit rows, pool3-scaled rows at gamma = 1/200, equal rows:   SPREAD = 1.097e-15   (pool3-contiguous-d768; REL_SPREAD)
     bound used for the GPU:                                      8 x SPREAD = 8.8e-15 (REL_TOL)
+    the width sweep's cases (sweep_cases(): 140 rows, d = 1 .. 191):  2.502e-16 (sweep-pool3-d61) -- smaller, the constant stays
     pool3-scaled rows at gamma = 4:                              SPREAD = 8.169e-12   (pool3-g4-contiguous-d768; REL_SPREAD_G4)
     bound used for the GPU:                                      8 x SPREAD = 6.5e-11 (REL_TOL_G4)
 
@@ -29,6 +30,7 @@ import numpy as np
 import pytest
 
 from tests import _cmmd_ref
+from tests import _rows_tile_cases as tc
 from tests.test_gpu_kid import SIZES_X, SIZES_Y, _dev, pool3_like
 
 REL_SPREAD = 1.097e-15
@@ -90,9 +92,19 @@ def reference_sums(case, dtype=np.float64):
     return _REFERENCE[key]
 
 
-def measure_spread():
+SWEEP_FAMILIES = ["unit", "pool3"]
+
+
+def sweep_cases(widths=tuple(tc.WIDTHS)):
+    """The width sweep of the gathered-row tile (tests/_rows_tile_cases.py) in sum_cases()' form: three groups of 5, 65 and 70
+    rows per side at every width, unit-norm rows (the metric's input) and pool3-scaled rows, both at the metric's gamma."""
+    return [(f"sweep-{family}-d{d}",) + tc.mmd_rows(d, family) + (tc.MMD_OX, tc.MMD_OY, None, None, 0, GAMMA, family)
+            for d in widths for family in SWEEP_FAMILIES]
+
+
+def measure_spread(cases=None):
     worst = {}
-    for case in sum_cases():
+    for case in (sum_cases() + sweep_cases() if cases is None else cases):
         a, b = reference_sums(case, np.float64), reference_sums(case, np.longdouble)
         nz = a != 0                                           # a sum that is 0 in fp64: every term underflowed (longdouble reaches further down)
         assert np.all(np.abs(b[~nz]) < np.finfo(np.float64).tiny) and np.all(np.abs(a[nz]) > 1e-290)
@@ -136,6 +148,56 @@ def test_sums_match_the_numpy_reference_at_every_tile_edge(cuda_device, d):
         assert got.shape == (len(ox) - 1, 3)
         worst[name] = _check_sums(name, got, reference_sums(case), _tol(family)) / _tol(family)
     assert len(worst) >= 5 and all(w <= 1.0 for w in worst.values()), worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", tc.WIDTHS)
+def test_width_sweep_of_the_row_tile(cuda_device, d):
+    """Every residue of d mod 4 and both sides of the 64-column slab edge through mmd_tiles_kernel<MMD_RBF> and its norm pre-pass:
+    NaN beyond column d and beyond the last row (tests/_rows_tile_gpu.py), the gathered route and the re-laid tensors bit for bit."""
+    from tests import _rows_tile_gpu as tg
+    from tise_toolbox_amd import device
+    for case in sweep_cases((d,)):
+        name, X, Y = case[:3]
+        tg.check_mmd_width("tise_mmd_rbf", device.GaussianMMD(cuda_device, GAMMA), X, Y, reference_sums(case), REL_TOL, cuda_device,
+                           gamma=GAMMA, label=f"rbf {case[9]}")
+
+
+@pytest.mark.gpu
+def test_mask_census_at_gamma_zero_is_exact(cuda_device):
+    """k = exp(-0 d2) = 1 for every pair of finite rows: the sums are the numbers of pairs, exactly, the empty and the 1-row group
+    included."""
+    from tests import _rows_tile_gpu as tg
+    for d in tc.CENSUS_WIDTHS:
+        tg.check_mask_census("tise_mmd_rbf", cuda_device, d, zero_features=False, gamma=0.0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("value", tc.BAD_VALUES, ids=tc.BAD_IDS)
+def test_a_non_finite_row_poisons_its_own_sums_and_nothing_else(cuda_device, value):
+    """fmax(0, NaN) = 0 would make such a row everybody's twin: k = exp(0) = 1 and a finite, wrong result."""
+    from tests import _rows_tile_gpu as tg
+    for d in tc.NONFINITE_WIDTHS:
+        tg.check_mmd_bad_rows("tise_mmd_rbf", cuda_device, d, value, "unit", gamma=GAMMA)
+
+
+@pytest.mark.gpu
+def test_cmmd_from_features_is_nan_for_a_non_finite_or_all_zero_row(cuda_device):
+    """The published implementation returns NaN for such input (NaN propagates through its kernel matrices), and so does this.
+    An all-zero row becomes NaN in normalize_rows (0 / 0)."""
+    import torch
+    from tise_toolbox_amd import cmmd
+    X, Y = tc.mmd_rows(67, "pool3")
+    assert np.isfinite(cmmd.cmmd_from_features(X, Y))
+    zero = np.array(X, copy=True)
+    zero[tc.MMD_ROWS - 1] = 0
+    assert bool(torch.isnan(cmmd.normalize_rows(torch.as_tensor(zero))[-1]).all())
+    for unbiased in (False, True):
+        assert np.isnan(cmmd.cmmd_from_features(zero, Y, unbiased=unbiased))
+        assert np.isnan(cmmd.cmmd_from_features(X, zero, unbiased=unbiased))
+        for value in tc.BAD_VALUES:
+            assert np.isnan(cmmd.cmmd_from_features(tc.with_bad_row(X, 0, value), Y, unbiased=unbiased)), value
+            assert np.isnan(cmmd.cmmd_from_features(torch.as_tensor(X, device=cuda_device), tc.with_bad_row(Y, 64, value), unbiased=unbiased)), value
 
 
 @pytest.mark.gpu

@@ -6,6 +6,7 @@ difference between the two over all groups and all three sums:
 
     largest relative spread, fp64 numpy against longdouble numpy:  SPREAD = 6.875e-16   (contiguous-d768; REL_SPREAD)
     bound used for the GPU:                                        8 x SPREAD = 5.5e-15 (REL_TOL)
+    the width sweep's cases (sweep_cases(): 140 rows, d = 1 .. 191): 2.185e-16 (sweep-d127) -- smaller, the constant stays
 
 The factor 8 covers a different but equally valid summation order and the MFMA's accumulation.  A kernel that needs more is
 wrong.  For the estimator (kid_from_features: mean and std over the subsets) the same relative bound is carried through the
@@ -14,12 +15,14 @@ at most REL_TOL x (|Sxx| / (n (n - 1)) + |Syy| / (m (m - 1)) + 2 |Sxy| / (n m)) 
 largest such amount and the standard deviation (1-Lipschitz in the max norm of the perturbation) by the same; the fp64 reference
 carries an error of the same kind (SPREAD x scale), so the comparison allows (REL_TOL + REL_SPREAD) x scale.
 """
+import functools
 import os
 
 import numpy as np
 import pytest
 
 from tests import _kid_ref
+from tests import _rows_tile_cases as tc
 
 REL_SPREAD = 6.875e-16
 REL_TOL = 8 * REL_SPREAD
@@ -63,9 +66,23 @@ def reference_sums(case, dtype=np.float64):
     return np.array(rows, dtype=dtype)
 
 
-def measure_spread():
+def sweep_cases(widths=tuple(tc.WIDTHS)):
+    """The width sweep of the gathered-row tile (tests/_rows_tile_cases.py) in sum_cases()' form: three groups of 5, 65 and 70
+    rows per side at every width."""
+    return [(f"sweep-d{d}",) + tc.mmd_rows(d) + (tc.MMD_OX, tc.MMD_OY, None, None, 0) for d in widths]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_reference(d):
+    """Computed once per width, shared, never changed."""
+    a = reference_sums(sweep_cases((d,))[0])
+    a.setflags(write=False)
+    return a
+
+
+def measure_spread(cases=None):
     worst = 0.0
-    for case in sum_cases():
+    for case in (sum_cases() + sweep_cases() if cases is None else cases):
         a, b = reference_sums(case, np.float64), reference_sums(case, np.longdouble)
         nz = b != 0
         assert np.all(a[~nz] == 0)
@@ -111,6 +128,52 @@ def test_sums_match_the_numpy_reference_at_every_tile_edge(cuda_device):
         assert got.shape == (len(ox) - 1, 3)
         worst[name] = _check_sums(name, got, reference_sums(case))
     assert all(w <= REL_TOL for w in worst.values()), worst
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", tc.WIDTHS)
+def test_width_sweep_of_the_row_tile(cuda_device, d):
+    """Every residue of d mod 4 and both sides of the 64-column slab edge through mmd_tiles_kernel<MMD_POLY3>: NaN beyond
+    column d and beyond the last row (tests/_rows_tile_gpu.py), the gathered route and the re-laid tensors bit for bit."""
+    from tests import _rows_tile_gpu as tg
+    from tise_toolbox_amd import device
+    X, Y = tc.mmd_rows(d)
+    tg.check_mmd_width("tise_mmd_poly3", device.PolynomialMMD(cuda_device), X, Y, sweep_reference(d), REL_TOL, cuda_device, label="poly3")
+
+
+@pytest.mark.gpu
+def test_mask_census_on_all_zero_features_is_exact(cuda_device):
+    """k = (0 / d + 1)^3 = 1 for every pair: the sums are the numbers of pairs, exactly, the empty and the 1-row group included."""
+    from tests import _rows_tile_gpu as tg
+    for d in tc.CENSUS_WIDTHS:
+        tg.check_mask_census("tise_mmd_poly3", cuda_device, d, zero_features=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("value", tc.BAD_VALUES, ids=tc.BAD_IDS)
+def test_a_non_finite_row_poisons_its_own_sums_and_nothing_else(cuda_device, value):
+    from tests import _rows_tile_gpu as tg
+    for d in tc.NONFINITE_WIDTHS:
+        tg.check_mmd_bad_rows("tise_mmd_poly3", cuda_device, d, value, "pool3")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("value", tc.BAD_VALUES, ids=tc.BAD_IDS)
+def test_kid_from_features_is_non_finite_for_a_non_finite_row(cuda_device, value):
+    """The reference code (numpy on the host) returns a non-finite value here, and so does this: nothing above the kernel hides
+    the row.  Subsets of all rows, so that every subset holds the bad one; the full-set form; and the per-class form, where only
+    the row's class is lost."""
+    from tise_toolbox_amd import kid
+    X, Y = tc.mmd_rows(67)
+    for bad1, bad2 in ((tc.with_bad_row(X, 0, value), Y), (X, tc.with_bad_row(Y, tc.MMD_ROWS - 1, value))):
+        want = _kid_ref.kid_from_features(bad1, bad2, 3, tc.MMD_ROWS, 1)
+        got = kid.kid_from_features(bad1, bad2, 3, tc.MMD_ROWS, 1)
+        assert not np.isfinite(want[0]) and not np.isfinite(got[0]), (want, got)
+        assert not np.isfinite(kid.kid_from_features(bad1, bad2, subset_size=0)[0])
+    names = ["a", "b", "c"]
+    clean, _ = kid.per_class_kid(X, tc.MMD_OX, Y, tc.MMD_OY, names)
+    got, skipped = kid.per_class_kid(tc.with_bad_row(X, int(tc.MMD_OX[1]), value), tc.MMD_OX, Y, tc.MMD_OY, names)
+    assert skipped == [] and not np.isfinite(got["b"]) and got["a"] == clean["a"] and got["c"] == clean["c"], (got, clean)
 
 
 @pytest.mark.gpu

@@ -4,8 +4,10 @@ TOLERANCE OF THE RADII (relative to each r2).  Sized on the CPU, not from the ke
 r2 of exactly the inputs of the radii test below twice -- tests/_prdc_ref.py's fp64 expansion, and direct differences in
 np.longdouble -- and prints the largest relative difference between the two over all sets, rows and k:
 
-    largest relative spread, fp64 expansion against longdouble differences:  SPREAD = 3.420e-15  (n = 1000, d = 192; REL_SPREAD)
-    bound used for the GPU:                                                  8 x SPREAD = 2.736e-14 (REL_TOL)
+    largest relative spread, fp64 expansion against longdouble differences:  SPREAD = 3.426e-15  (REL_SPREAD)
+        the radii test's sets:                              3.420e-15  (n = 1000, d = 192)
+        the width sweep's float sets (d >= 61, 70 and 65 rows):  3.426e-15  (d = 127; measured 3.4253e-15, rounded up)
+    bound used for the GPU:                                                  8 x SPREAD = 2.741e-14 (REL_TOL)
 
 The factor 8 covers a different but equally valid summation order and the MFMA's accumulation.  A kernel that needs more is wrong.
 
@@ -22,13 +24,30 @@ import pytest
 
 from tests import _prdc_cases as cases
 from tests import _prdc_ref
+from tests import _rows_tile_cases as tc
 
-REL_SPREAD = 3.420e-15
+REL_SPREAD = 3.426e-15
 REL_TOL = 8 * REL_SPREAD
 
 
-def measure_spread():
+def measure_sweep_spread():
+    """The float widths of the gathered-row tile's sweep (tests/_rows_tile_cases.py): both sets, both k."""
     worst = 0.0
+    for d in tc.WIDTHS:
+        if tc.prdc_is_exact(d):
+            continue
+        rel = 0.0
+        for X in tc.prdc_rows(d):
+            s64, sl = np.sort(_prdc_ref.d2_expansion(X, X), axis=1), np.sort(_prdc_ref.d2_direct(X, X), axis=1)
+            for k in tc.PRDC_K:
+                rel = max(rel, float(np.max(np.abs(s64[:, k].astype(np.longdouble) - sl[:, k]) / sl[:, k])))
+        print(f"sweep, d = {d:5d}: r2, fp64 expansion vs longdouble differences, largest relative difference {rel:.3e}", flush=True)
+        worst = max(worst, rel)
+    return worst
+
+
+def measure_spread():
+    worst = measure_sweep_spread()
     for d in cases.RADII_D:
         for n in sorted({n for k in cases.RADII_K for n in cases.radii_rows(k)}):
             X, s64 = cases.radii_set(n, d)
@@ -125,6 +144,81 @@ def test_counts_equal_the_reference_exactly_on_integer_inputs_with_ties(cuda_dev
         _check_counts(knn, R, F, k, ref, splits, cuda_device)
     got = prdc.prdc_from_features(R, F, k)
     assert all(got[name] == ref[name] for name in got)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", tc.WIDTHS)
+def test_width_sweep_of_the_row_tile(cuda_device, d):
+    """Every residue of d mod 4 and both sides of the 64-column slab edge through knn_radius2_kernel<4> (k = 1), <8> (k = 5) and
+    prdc_counts_kernel: NaN beyond column d and beyond the last row (tests/_rows_tile_gpu.py), the re-laid tensors bit for bit.
+    Below 61 columns the features are integers and r2, cnt, rec, prec EQUAL the reference, exact ties on both sides included;
+    from 61 on they are floats under this file's rules (REL_TOL on r2, every decision MIN_MARGIN away from its radius)."""
+    from tests import _rows_tile_gpu as tg
+    R, F = tc.prdc_rows(d)
+    exact, worst = tc.prdc_is_exact(d), 0.0
+    for k in tc.PRDC_K:
+        print(f"d = {d}, k = {k}: {'ties (real, generated radii)' if exact else 'smallest margin'} {tc.check_prdc_case_properties(d, k)}")
+        ref = tc.prdc_reference(d, k)
+        for splits in tc.PRDC_SPLITS:
+            got = tg.knn_cabi(R, F, k, splits, cuda_device)
+            worst = max(worst, tg.check_knn_against(got, ref, exact, REL_TOL, (d, k, splits)))
+            for (name, rt), (_, ft) in zip(tg.copy_forcing_layouts(R, cuda_device), tg.copy_forcing_layouts(F, cuda_device)):
+                assert tg.same_bits(tg.knn_device(rt, ft, k, splits, cuda_device), got), (name, d, k, splits)
+    print(f"d = {d}: largest relative error of an r2 {worst:.3e} (bound {0.0 if exact else REL_TOL:.3e})")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("value", tc.BAD_VALUES, ids=tc.BAD_IDS)
+@pytest.mark.parametrize("d", [7, 67])
+def test_a_non_finite_row_is_nobodys_neighbour_and_lies_in_no_ball(cuda_device, d, value):
+    """fmax(0, NaN) = 0 would put such a row at distance 0 from every row: inside every ball of positive radius (coverage
+    exactly 1), everybody's nearest neighbour.  The rule (include/tise_hip.h): the row gets r2 = NaN, cnt = rec = prec = 0 and
+    every other row the results of the sets without it -- exactly on the integer inputs (d = 7), within REL_TOL and with every
+    decision MIN_MARGIN away on the float ones (d = 67)."""
+    from tests import _rows_tile_gpu as tg
+    R, F = tc.prdc_rows(d)
+    exact = tc.prdc_is_exact(d)
+    for side, row in tc.prdc_bad_rows():
+        Rb = tc.with_bad_row(R, row, value) if side == "real" else R
+        Fb = tc.with_bad_row(F, row, value) if side == "fake" else F
+        for k in tc.PRDC_K:
+            ref = _prdc_ref.prdc_dropping_nonfinite(Rb, Fb, k)
+            assert int(np.isnan(ref["r2_real"]).sum() + np.isnan(ref["r2_fake"]).sum()) == 1
+            if not exact:
+                assert _prdc_ref.smallest_margin(ref["clean"]) >= cases.MIN_MARGIN
+            for splits in tc.PRDC_SPLITS:
+                got = tg.knn_cabi(Rb, Fb, k, splits, cuda_device)
+                tg.check_knn_against(got, ref, exact, REL_TOL, (d, value, side, row, k, splits))
+            assert tg.same_bits(tg.knn_device(*(t for _, t in (tg.copy_forcing_layouts(Rb, cuda_device)[1], tg.copy_forcing_layouts(Fb, cuda_device)[2])),
+                                              k, 0, cuda_device), tg.knn_cabi(Rb, Fb, k, 0, cuda_device))
+
+
+@pytest.mark.gpu
+def test_prdc_from_features_refuses_non_finite_rows_as_the_prdc_package_does(cuda_device, tmp_path):
+    """ValueError that names the side, the number of affected rows and the first of them; through fid_score --prdc with a feature
+    file as --path1 as well (its stored ``features`` go straight in)."""
+    import torch
+    from tise_toolbox_amd import fid_score, prdc
+    R, F = tc.prdc_rows(67)
+    assert all(np.isfinite(v) for v in prdc.prdc_from_features(R, F, 5).values())
+    bad = tc.with_bad_row(tc.with_bad_row(R, 69, float("inf")), 12, float("nan"))
+    with pytest.raises(ValueError, match=r"the real side has 2 feature rows with a NaN or an infinity \(the first is row 12\)"):
+        prdc.prdc_from_features(bad, F, 5)
+    with pytest.raises(ValueError, match=r"the fake side has 1 feature row with a NaN or an infinity \(the first is row 64\)"):
+        prdc.prdc_from_features(torch.as_tensor(R, device=cuda_device), tc.with_bad_row(F, 64, float("-inf")), 3)
+    with pytest.raises(ValueError, match=r"the real side has 1 feature row .*row 0\)"):
+        prdc.prdc_from_features(tc.with_bad_row(R, 0, float("nan")), tc.with_bad_row(F, 3, float("nan")), 1)
+    # the CLI: two feature files of 64-wide rows (no image is read), the first with a NaN row
+    R64, F64 = tc.prdc_rows(64)
+    files = []
+    for name, rows in (("bad.npz", tc.with_bad_row(R64, 5, float("nan"))), ("gen.npz", F64), ("real.npz", R64)):
+        a = rows[np.isfinite(rows).all(axis=1)].astype(np.float64)
+        files.append(str(tmp_path / name))
+        fid_score.save_stats_npz(files[-1], a.mean(0), np.cov(a, rowvar=False), "torchvision", rows)
+    args = ["--path2", files[1], "--prdc", "--dims", "64", "--synthetic-weights"]
+    with pytest.raises(ValueError, match=r"the real side has 1 feature row with a NaN or an infinity \(the first is row 5\)"):
+        fid_score.main(["--path1", files[0]] + args)
+    assert fid_score.main(["--path1", files[2]] + args) is not None
 
 
 @pytest.mark.gpu

@@ -209,3 +209,37 @@ def test_all_gather_rows_is_the_identity_for_one_process():
     from tise_toolbox_amd import dist as tdist
     t = torch.arange(12.0).reshape(3, 4)
     assert tdist.all_gather_rows(t) is t
+
+
+# ---- the gathered-row tile's width sweep and the non-finite rule: the oracle's side, checked without a GPU ----------------------
+def test_recorded_spread_covers_the_width_sweep():
+    from tests import test_gpu_kid
+    assert test_gpu_kid.measure_spread(test_gpu_kid.sweep_cases()) <= test_gpu_kid.REL_SPREAD
+    assert test_gpu_kid.REL_TOL == 8 * test_gpu_kid.REL_SPREAD
+
+
+def test_reference_sums_of_a_constant_kernel_count_the_pairs():
+    from tests import _rows_tile_cases as tc
+    want = tc.census_expected()
+    for g, (n, m) in enumerate(zip(tc.CENSUS_SIZES_X, tc.CENSUS_SIZES_Y)):
+        assert list(_kid_ref.poly3_sums(np.zeros((n, 3), np.float32), np.zeros((m, 3), np.float32))) == list(want[g])
+
+
+@pytest.mark.parametrize("value", [float("nan"), float("inf"), float("-inf")])
+def test_reference_is_non_finite_for_a_non_finite_row_and_only_where_the_row_enters(value):
+    """numpy's semantics, which the kernel has to match: the sums that involve the row are non-finite, the group's third sum and
+    every other group keep their bits, and the estimator built on them is non-finite."""
+    from tests import _rows_tile_cases as tc
+    X, Y = tc.mmd_rows(67)
+    clean = tc.group_sums(_kid_ref.poly3_sums, X, Y)
+    for side, g, pos in tc.mmd_bad_rows():
+        row = int((tc.MMD_OX if side == "x" else tc.MMD_OY)[g]) + pos
+        with np.errstate(invalid="ignore"):
+            got = tc.group_sums(_kid_ref.poly3_sums, tc.with_bad_row(X, row, value) if side == "x" else X,
+                                tc.with_bad_row(Y, row, value) if side == "y" else Y)
+        hit = np.zeros(clean.shape, bool)
+        hit[g, [0, 2] if side == "x" else [1, 2]] = True
+        assert not np.any(np.isfinite(got[hit])) and got[~hit].tobytes() == clean[~hit].tobytes(), (side, g, pos)
+    with np.errstate(invalid="ignore"):
+        assert not np.isfinite(_kid_ref.kid_from_features(tc.with_bad_row(X, 0, value), Y, 3, tc.MMD_ROWS, 1)[0])
+        assert not np.isfinite(_kid_ref.kid_from_features(X, tc.with_bad_row(Y, 139, value), subset_size=0)[0])

@@ -10,6 +10,7 @@ import pytest
 
 from tests import _prdc_cases as cases
 from tests import _prdc_ref
+from tests import _rows_tile_cases as tc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("tise_knn_workspace_bytes", "tise_knn_radius2", "tise_prdc_counts")
@@ -155,3 +156,85 @@ def test_prdc_from_features_checks_its_arguments_and_has_no_cpu_path():
     if not torch.cuda.is_available():
         with pytest.raises(_lib.TiseLibraryError):
             prdc.prdc_from_features(x, y)
+
+
+# ---- the gathered-row tile's width sweep and the non-finite rule: what the GPU tests rely on, checked without a GPU -------------
+@pytest.mark.parametrize("d", tc.WIDTHS)
+def test_width_sweep_inputs_have_the_properties_the_gpu_test_relies_on(d):
+    """Integer widths: the reference is exact (it equals its longdouble restatement) and meets exact ties d2 == r2 on both sides.
+    Float widths: the seeds give every decision MIN_MARGIN, and the fp64 r2 lies within the recorded spread of the longdouble one."""
+    from tests import test_gpu_prdc
+    R, F = tc.prdc_rows(d)
+    assert R.shape == (70, d) and F.shape == (65, d) and R.dtype == np.float32
+    for k in tc.PRDC_K:
+        tc.check_prdc_case_properties(d, k)
+        ref, direct = tc.prdc_reference(d, k), _prdc_ref.prdc_direct(R, F, k)
+        for name in ("cnt", "rec", "prec"):
+            assert np.array_equal(ref[name], direct[name]), (d, k, name)
+        if tc.prdc_is_exact(d):
+            assert np.all(np.abs(R) <= 4) and np.array_equal(R, np.round(R))
+            for name in ("r2_real", "r2_fake", "cross"):
+                assert np.array_equal(ref[name], direct[name]), (d, k, name)
+        else:
+            for name in ("r2_real", "r2_fake"):
+                assert np.max(np.abs(ref[name] - direct[name]) / direct[name]) <= test_gpu_prdc.REL_SPREAD, (d, k, name)
+
+
+def test_recorded_spread_covers_the_width_sweep(capsys):
+    from tests import test_gpu_prdc
+    assert test_gpu_prdc.measure_sweep_spread() <= test_gpu_prdc.REL_SPREAD
+    assert test_gpu_prdc.REL_TOL == 8 * test_gpu_prdc.REL_SPREAD
+
+
+@pytest.mark.parametrize("d", [7, 67])
+def test_reference_rule_for_non_finite_rows(d):
+    """prdc_dropping_nonfinite states the kernels' rule through the clean definition.  For a NaN, plain numpy on the dirty input
+    says the same (np.maximum keeps a NaN, np.sort puts it last, comparisons with it are False); for an infinity it does not
+    (inf - inf and inf + inf mix), which is why the rule is stated by dropping the rows."""
+    R, F = tc.prdc_rows(d)
+    for k in tc.PRDC_K:
+        clean = tc.prdc_reference(d, k)
+        for side, row in tc.prdc_bad_rows():
+            for value in tc.BAD_VALUES:
+                Rb = tc.with_bad_row(R, row, value) if side == "real" else R
+                Fb = tc.with_bad_row(F, row, value) if side == "fake" else F
+                assert list(_prdc_ref.nonfinite_rows(Rb)) == ([row] if side == "real" else [])
+                assert list(_prdc_ref.nonfinite_rows(Fb)) == ([row] if side == "fake" else [])
+                ref = _prdc_ref.prdc_dropping_nonfinite(Rb, Fb, k)
+                mine = "r2_real" if side == "real" else "r2_fake"
+                assert np.isnan(ref[mine][row]) and int(np.isnan(ref["r2_real"]).sum() + np.isnan(ref["r2_fake"]).sum()) == 1
+                if side == "real":
+                    assert ref["cnt"][row] == 0 and not ref["rec"][row]
+                    assert np.array_equal(ref["prec"], ref["clean"]["prec"]) and len(ref["clean"]["cnt"]) == len(R) - 1
+                    assert np.array_equal(ref["r2_fake"], clean["r2_fake"])        # the other side's radii do not move
+                else:
+                    assert not ref["prec"][row] and np.array_equal(ref["cnt"], ref["clean"]["cnt"])
+                    assert np.array_equal(ref["r2_real"], clean["r2_real"])
+                if np.isnan(value):
+                    with np.errstate(invalid="ignore"):
+                        plain = _prdc_ref.prdc(Rb, Fb, k)
+                    for name in ("cnt", "rec", "prec"):
+                        assert np.array_equal(plain[name], ref[name]), (d, k, side, row, name)
+                    for name in ("r2_real", "r2_fake"):
+                        assert np.array_equal(plain[name], ref[name], equal_nan=True), (d, k, side, row, name)
+    # what fmax(0, NaN) = 0 did: the NaN row of the generated side sits at distance 0 from every row, inside every ball of
+    # positive radius -- one more hit for every real row (so coverage is exactly 1), and the row itself counts as precise
+    Fb = tc.with_bad_row(F, 0, float("nan"))
+    with np.errstate(invalid="ignore"):
+        wrong = _prdc_ref.prdc(R, Fb, 5, d2=lambda a, b: np.fmax(0.0, _prdc_ref.d2_expansion(a, b)))
+    right = _prdc_ref.prdc_dropping_nonfinite(R, Fb, 5)
+    assert np.all(right["r2_real"] > 0) and np.array_equal(wrong["cnt"], right["cnt"] + 1) and wrong["coverage"] == 1.0
+    assert wrong["prec"][0] and not right["prec"][0] and wrong["r2_fake"][0] == 0
+
+
+def test_refusal_of_non_finite_rows_names_side_count_and_first_row():
+    """The host half of prdc_from_features' refusal (the device half -- NaN radii counted into its one host copy -- is in
+    tests/test_gpu_prdc.py): nothing for clean sides, else ValueError for the first side that has such rows."""
+    from tise_toolbox_amd import prdc
+    assert prdc.refuse_nonfinite_rows((("real", 0, 70), ("fake", 0, 65))) is None
+    with pytest.raises(ValueError, match=r"the real side has 2 feature rows with a NaN or an infinity \(the first is row 12\)"):
+        prdc.refuse_nonfinite_rows((("real", 2, 12), ("fake", 0, 65)))
+    with pytest.raises(ValueError, match=r"the fake side has 1 feature row with a NaN or an infinity \(the first is row 64\)"):
+        prdc.refuse_nonfinite_rows((("real", 0, 70), ("fake", 1, 64)))
+    with pytest.raises(ValueError, match=r"the real side has 1 feature row .*row 0\)"):
+        prdc.refuse_nonfinite_rows((("real", 1, 0), ("fake", 1, 3)))

@@ -170,6 +170,15 @@ struct GtRowFetch {
     }
 };
 
+// The squared distance the callers form from the tile, d2 = max(0, (|a|^2 + |b|^2) - 2 a.b), must not hide a row that holds a
+// NaN or an infinity: fmax returns the operand that is not NaN and would turn such a pair into d2 = 0, the nearest neighbour of
+// every row.  The rule (include/tise_hip.h, "Non-finite feature rows"): the norm pre-pass writes NaN for a row whose sum of
+// squares is not finite, and the clamp keeps a NaN, so d2 of every pair with such a row is NaN and every comparison with it is
+// false.  For finite operands both functions return the bits they were given (the difference is never -0: the norms are sums
+// of squares from +0 and the accumulators start at +0).
+__device__ __forceinline__ double rows_norm2_or_nan(double s) { return __builtin_isfinite(s) ? s : __builtin_nan(""); }
+__device__ __forceinline__ double rows_clamp_d2(double x) { return x < 0.0 ? 0.0 : x; }
+
 // acc[tm][tn] += sum_k A(m, k) B(n, k) over k in [0, d); same wave grid and accumulator layout as gemm_tile_64x64
 __device__ __forceinline__ void gemm_tile_64x64_rows_f32(GtRowFetch& fa, GtRowFetch& fb, int d, double4_t (&acc)[2][2],
                                                          float* lds) {

@@ -2,8 +2,9 @@
 // al. 2020) on fp32 feature rows that stay on the device.  Squared distances come from the expansion
 //     d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)
 // in fp64: a.b from the gathered-row fp64 MFMA tile of gemm_tile.h (every fp32 x fp32 product is exact in fp64), the norms from
-// knn_row_norm2_kernel (exact squares, fixed order).  No N x N matrix is written: a workgroup turns the accumulators of one
-// 64 x 64 tile into d2 and consumes them on the spot.
+// knn_row_norm2_kernel (exact squares, fixed order; NaN for a row that holds a NaN or an infinity, and the clamp keeps a NaN --
+// gemm_tile.h: such a row is nobody's neighbour, lies in no ball, and its own r2 is NaN).  No N x N matrix is written: a
+// workgroup turns the accumulators of one 64 x 64 tile into d2 and consumes them on the spot.
 //
 // One value per pair, whatever the pass.  a.b is accumulated over k in the tile's fixed order, and a step fma(a_k, b_k, acc) does
 // not care which operand is which; |a|^2 + |b|^2 commutes; so d2(x_i, x_j) of the within-set pass, d2(x_j, x_i) of the same pass
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(256) void knn_row_norm2_kernel(const float* __restr
         s += v * v;
     }
     s = wave_sum(s);
-    if (lane == 0) out[row] = s;
+    if (lane == 0) out[row] = rows_norm2_or_nan(s);
 }
 
 // ascending list of the KL smallest values met
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void knn_radius2_kernel(const float* __rest
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int rl = wr * 32 + a * 16 + (lane >> 4) + 4 * r, row = tm * 64 + rl;
-                    const double v = fmax(0.0, (na[a][r] + nb) - 2.0 * acc[a][b][r]);
+                    const double v = rows_clamp_d2((na[a][r] + nb) - 2.0 * acc[a][b][r]);
                     tile[rl * KNN_TP + cl] = (col < n && row != col) ? v : __builtin_inf();
                 }
         }
@@ -125,9 +126,10 @@ __global__ __launch_bounds__(256, 2) void knn_radius2_kernel(const float* __rest
     }
 }
 
-// r2[row] = the k-th smallest of the row's S * k candidates (+inf entries: a split that held fewer than k other rows)
-__global__ __launch_bounds__(256) void knn_merge_kernel(const double* __restrict__ cand, int n, int S, int k,
-                                                        double* __restrict__ r2) {
+// r2[row] = the k-th smallest of the row's S * k candidates (+inf entries: a split that held fewer than k other rows); NaN for a
+// row that holds a non-finite value (its norm is NaN, and no pair with it was a candidate anywhere)
+__global__ __launch_bounds__(256) void knn_merge_kernel(const double* __restrict__ cand, const double* __restrict__ norm, int n,
+                                                        int S, int k, double* __restrict__ r2) {
     const int row = blockIdx.x * 256 + threadIdx.x;
     if (row >= n) return;
     double best[KNN_MAX_K];
@@ -139,7 +141,8 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const double* __restrict
 #pragma unroll
     for (int j = 1; j < KNN_MAX_K; ++j)
         if (j == k - 1) v = best[j];
-    r2[row] = v;
+    const double nr = norm[row];
+    r2[row] = nr == nr ? v : nr;
 }
 
 __global__ __launch_bounds__(256, 2) void prdc_counts_kernel(const float* __restrict__ R, int64_t ldr, int n,
@@ -188,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void prdc_counts_kernel(const float* __rest
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
-                    const double v = fmax(0.0, (na[a][r] + nb) - 2.0 * acc[a][b][r]);
+                    const double v = rows_clamp_d2((na[a][r] + nb) - 2.0 * acc[a][b][r]);
                     const bool on = col_on && row < n;
                     const int in_r = (on && v < ra[a][r]) ? 1 : 0, in_f = (on && v < rb) ? 1 : 0;
                     c_cnt[a][r] += in_r;
@@ -272,7 +275,7 @@ int tise_knn_radius2(const float* x_dev, int64_t rows, int64_t ld, int d, int k,
     else if (k <= 8) hipLaunchKernelGGL(knn_radius2_kernel<8>, grid, dim3(256), 0, st, x_dev, ld, n, d, k, norm, cand);
     else hipLaunchKernelGGL(knn_radius2_kernel<KNN_MAX_K>, grid, dim3(256), 0, st, x_dev, ld, n, d, k, norm, cand);
     TISE_LAUNCH_CHECK();
-    hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cand, n, S, k, r2_dev);
+    hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cand, norm, n, S, k, r2_dev);
     TISE_LAUNCH_CHECK();
     return TISE_OK;
 }

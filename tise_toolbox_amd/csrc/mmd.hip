@@ -21,7 +21,9 @@
 //     k(a, b) = exp(-gamma d2(a, b)),      d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)
 // d2 by csrc/knn.hip's rule: a.b from the tile, |.|^2 from mmd_row_norm2_kernel (exact squares, that file's fixed order) into the
 // workspace, one double per group position of each side, parenthesised so that d2 of a pair is the same bits whichever side
-// each row is on.  exp is the fp64 library function.  Its cost against the tile's MFMA work has not been measured.
+// each row is on.  A row that holds a NaN or an infinity has the norm NaN and the clamp keeps a NaN (gemm_tile.h): every kernel
+// value of a pair with it is NaN, so the sums that involve the row are NaN and no other sum of the launch moves.  exp is the
+// fp64 library function.  Its cost against the tile's MFMA work has not been measured.
 //
 // Kernels
 //   mmd_tiles_kernel<MMD_POLY3>   bound: fp64 MFMA for d in the thousands (64 * 64 * 2 * d flop per tile against 2 * 64 * d * 4
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(256) void mmd_row_norm2_kernel(const float* __restr
         s += v * v;
     }
     s = wave_sum(s);
-    if (lane == 0) out[w] = s;
+    if (lane == 0) out[w] = rows_norm2_or_nan(s);
 }
 
 template <int KF>
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(256, 2) void mmd_tiles_kernel(const float* __restri
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
-                    const double d2 = fmax(0.0, (na[a][r] + nb) - 2.0 * acc[a][b][r]);
+                    const double d2 = rows_clamp_d2((na[a][r] + nb) - 2.0 * acc[a][b][r]);
                     const bool on = row < sg.na && col < sg.nb && !(diag && row == col);
                     s += on ? exp(-rbf.gamma * d2) : 0.0;
                 }

@@ -548,7 +548,8 @@ class KnnManifold:
 
     def radius2(self, X, k, col_splits=0):
         """X (n, d) fp32 CUDA tensor (row stride may exceed d), n >= k + 1, 1 <= k <= 16 -> (n,) fp64 CUDA tensor: the squared
-        distance from every row to its k-th nearest OTHER row.  ``col_splits``: 0 = chosen by the library."""
+        distance from every row to its k-th nearest OTHER row.  ``col_splits``: 0 = chosen by the library.  A row that holds a
+        NaN or an infinity gets NaN and is no other row's neighbour (include/tise_hip.h, "Non-finite feature rows")."""
         X = _rows_side(X, "X")
         k, col_splits = int(k), int(col_splits)
         if X.shape[1] < 1:

@@ -21,6 +21,10 @@ Duplicate rows: for non-integer features the d2 of two identical rows is a round
 rounded sums, the dot product is rounded once per accumulation step), of the order of 1e-16 |a|^2, not 0 -- the sklearn-based
 packages compute the same expansion and behave the same way.  Integer-valued features (all sums exact) give exactly 0.
 
+Non-finite features: a row that holds a NaN or an infinity has no distance to anything.  The kernels give it r2 = NaN and keep
+it out of every other row's neighbours and balls (include/tise_hip.h); ``prdc_from_features`` then raises ValueError, as the
+``prdc`` package does (sklearn's pairwise_distances refuses such input) -- four numbers computed around a hole would look valid.
+
 Limits: 1 <= k <= 16, k + 1 <= rows <= 2^24 per side.  There is no CPU fallback.
 """
 from collections import OrderedDict
@@ -30,6 +34,15 @@ import torch
 from . import device
 from .engine import require_gpu
 from .kid import _to_device_f32
+
+
+def refuse_nonfinite_rows(sides):
+    """``sides``: (name, number of rows that hold a NaN or an infinity, index of the first of them) per side, host integers.
+    Raises ValueError for the first side that has such rows -- the ``prdc`` package refuses this input too.  Host only."""
+    for what, count, first in sides:
+        if count:
+            raise ValueError(f"the {what} side has {count} feature row{'s' if count > 1 else ''} with a NaN or an infinity "
+                             f"(the first is row {first}); precision, recall, density and coverage are not defined for them")
 
 
 def prdc_from_features(real, fake, nearest_k=5):
@@ -50,9 +63,16 @@ def prdc_from_features(real, fake, nearest_k=5):
     dev = real.device if isinstance(real, torch.Tensor) and real.is_cuda else torch.device("cuda", torch.cuda.current_device())
     R, F = _to_device_f32(real, dev), _to_device_f32(fake, dev)
     knn = device.KnnManifold(dev)
-    cnt, rec, prec = knn.counts(R, knn.radius2(R, k), F, knn.radius2(F, k))
+    r2R, r2F = knn.radius2(R, k), knn.radius2(F, k)
+    cnt, rec, prec = knn.counts(R, r2R, F, r2F)
     n, m = R.shape[0], F.shape[0]
-    # ONE device -> host copy of four integers
-    sums = torch.stack([prec.sum(), rec.sum(), cnt.sum(dtype=torch.int64), (cnt > 0).sum()]).cpu().tolist()
+    # r2 is NaN exactly for the rows that hold a non-finite value: their number and the first of them, per side
+    bad = []
+    for r2 in (r2R, r2F):
+        nan = torch.isnan(r2)
+        bad += [nan.sum(), torch.where(nan, torch.arange(r2.shape[0], device=dev), r2.shape[0]).min()]
+    # ONE device -> host copy of eight integers
+    sums = torch.stack([prec.sum(), rec.sum(), cnt.sum(dtype=torch.int64), (cnt > 0).sum()] + bad).cpu().tolist()
+    refuse_nonfinite_rows((("real", sums[4], sums[5]), ("fake", sums[6], sums[7])))
     return OrderedDict([("precision", sums[0] / m), ("recall", sums[1] / n), ("density", sums[2] / (k * m)),
                         ("coverage", sums[3] / n)])
