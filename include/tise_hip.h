@@ -265,7 +265,8 @@ int tise_mmd_rbf_grouped(const float* x_dev, int64_t rows_x, int64_t ld_x, const
  * TISE_ERR_UNSUPPORTED: more than 2^24 rows.
  * Non-finite feature rows (this block and tise_mmd_rbf_grouped / tise_mmd_poly3_grouped above).  A row that holds a NaN or an
  * infinity is a legal input with a defined result; nothing is rejected and nothing is clamped away.  Its |.|^2 is stored as NaN
- * and the clamp of d2 keeps a NaN (max(0, NaN) is NaN here, not 0), so d2 of every pair with such a row is NaN:
+ * and the clamp of d2 keeps a NaN (max(0, NaN) is NaN here, not 0), so d2 of every pair with such a row is NaN (one function
+ * each for every kernel of the block: rows_norm2_or_nan and rows_d2 in csrc/rows_tile.h):
  *   tise_knn_radius2 / tise_prdc_counts: every IEEE comparison with NaN is false, so the pair is never a neighbour candidate and
  *     never inside a ball.  The row itself gets r2 = NaN, cnt = 0, rec = 0, prec = 0; every other row gets exactly the results
  *     of the same call on the sets WITHOUT that row (the caller must leave k + 1 finite rows for them to be meaningful;

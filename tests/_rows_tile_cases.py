@@ -1,4 +1,4 @@
-"""Inputs of the width sweep and of the non-finite-row tests of the gathered-row fp64 tile (csrc/gemm_tile.h:
+"""Inputs of the width sweep and of the non-finite-row tests of the gathered-row fp64 tile (csrc/rows_tile.h:
 gemm_tile_64x64_rows_f32 / GtRowFetch), shared by tests/test_gpu_kid.py, tests/test_gpu_cmmd.py, tests/test_gpu_prdc.py and their
 host-side companions (seeded; nothing here touches a GPU).
 
@@ -121,6 +121,43 @@ def prdc_ties(ref):
 def prdc_bad_rows():
     """(side, row): the first row, and the last row of a side whose size is no multiple of 64 (replicated into the masked rows)."""
     return [("real", 0), ("real", PRDC_N - 1), ("fake", 0), ("fake", PRDC_M - 1)]
+
+
+# ---- the recorded bits (tests/golden/rows_tile_bits.npz) ----------------------------------------------------------------------
+BITS_WIDTHS = [3, 64, 67, 191]
+BITS_NONFINITE_WIDTH = 67
+BITS_SPLITS = [0, 3]
+BITS_GAMMA = 1 / 200                # tests/test_gpu_cmmd.py's GAMMA
+BITS_FILE = "rows_tile_bits.npz"
+
+
+def bits_mmd_cases():
+    """(key, fn, X, Y, index_x | None, index_y | None, gamma | None) of the recorded launches of tise_mmd_poly3_grouped ("pool3"
+    rows) and tise_mmd_rbf_grouped ("unit" rows), groups MMD_OX / MMD_OY: the contiguous and the gathered route at every width of
+    BITS_WIDTHS, and at d = 67 a NaN in the last row of either side -- the row GtRowFetch::bind replicates into the masked rows."""
+    out = []
+    for fn, family, gamma in (("tise_mmd_poly3", "pool3", None), ("tise_mmd_rbf", "unit", BITS_GAMMA)):
+        for d in BITS_WIDTHS:
+            X, Y = mmd_rows(d, family)
+            (Xs, ix), (Ys, iy) = shuffled(X, 11 + d), shuffled(Y, 12 + d)
+            out.append((f"{fn}/d{d}/contiguous", fn, X, Y, None, None, gamma))
+            out.append((f"{fn}/d{d}/gathered", fn, Xs, Ys, ix, iy, gamma))
+        X, Y = mmd_rows(BITS_NONFINITE_WIDTH, family)
+        nan = float("nan")
+        out.append((f"{fn}/d{BITS_NONFINITE_WIDTH}/nan-last-x", fn, with_bad_row(X, MMD_ROWS - 1, nan), Y, None, None, gamma))
+        out.append((f"{fn}/d{BITS_NONFINITE_WIDTH}/nan-last-y", fn, X, with_bad_row(Y, MMD_ROWS - 1, nan), None, None, gamma))
+    return out
+
+
+def bits_knn_cases():
+    """(key, R, F, k, col_splits) of the recorded launches of tise_knn_radius2 (both sides) and tise_prdc_counts: prdc_rows(d) at
+    every width of BITS_WIDTHS, k of PRDC_K, col_splits of BITS_SPLITS, and at d = 67 a NaN in the last row of either side."""
+    out = [(f"knn/d{d}/k{k}/s{s}", *prdc_rows(d), k, s) for d in BITS_WIDTHS for k in PRDC_K for s in BITS_SPLITS]
+    R, F = prdc_rows(BITS_NONFINITE_WIDTH)
+    nan = float("nan")
+    out.append((f"knn/d{BITS_NONFINITE_WIDTH}/nan-last-real", with_bad_row(R, PRDC_N - 1, nan), F, 5, 0))
+    out.append((f"knn/d{BITS_NONFINITE_WIDTH}/nan-last-fake", R, with_bad_row(F, PRDC_M - 1, nan), 5, 0))
+    return out
 
 
 def check_prdc_case_properties(d, k):

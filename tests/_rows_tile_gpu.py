@@ -54,6 +54,17 @@ def _i64(a):
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
 
 
+def sized_and_filled(dev, size_fn, size_args, outputs, fill):
+    """The workspace, sized through the library (``size_fn(*size_args, &bytes)``), and the outputs ``[(shape, dtype)]`` pre-filled
+    with ``fill`` -- an element nobody wrote shows.  -> (workspace, its size in bytes, [output tensors])"""
+    import torch
+    from tise_toolbox_amd import _lib
+    nb = ctypes.c_size_t()
+    _lib.call(size_fn, *size_args, ctypes.byref(nb))
+    ws = torch.empty(max(256, nb.value), dtype=torch.uint8, device=dev)
+    return ws, nb.value, [torch.full(shape, fill, dtype=dtype, device=dev) for shape, dtype in outputs]
+
+
 def mmd_cabi(fn, X, Y, ox, oy, dev, ix=None, iy=None, gamma=None):
     """tise_mmd_{poly3,rbf}_grouped on NaN-padded uploads of X and Y (``fn``: "tise_mmd_poly3" or "tise_mmd_rbf") -> (n_groups, 3)
     numpy array.  The output is pre-filled with -1: a sum nobody wrote shows."""
@@ -65,14 +76,11 @@ def mmd_cabi(fn, X, Y, ox, oy, dev, ix=None, iy=None, gamma=None):
     ng = len(ox) - 1
     ixd = torch.as_tensor(np.ascontiguousarray(ix, dtype=np.int64), device=dev) if ix is not None else None
     iyd = torch.as_tensor(np.ascontiguousarray(iy, dtype=np.int64), device=dev) if iy is not None else None
-    nb = ctypes.c_size_t()
-    _lib.call(fn + "_workspace_bytes", pox, poy, ng, ctypes.byref(nb))
-    ws = torch.empty(max(256, nb.value), dtype=torch.uint8, device=dev)
-    out = torch.full((ng, 3), -1.0, dtype=torch.float64, device=dev)
+    ws, nb, (out,) = sized_and_filled(dev, fn + "_workspace_bytes", (pox, poy, ng), [((ng, 3), torch.float64)], -1.0)
     extra = () if gamma is None else (ctypes.c_double(gamma),)
     _lib.call(fn + "_grouped", xb.data_ptr(), X.shape[0], ldx, ixd.data_ptr() if ixd is not None else None, len(ix) if ix is not None else 0,
               pox, yb.data_ptr(), Y.shape[0], ldy, iyd.data_ptr() if iyd is not None else None, len(iy) if iy is not None else 0, poy,
-              ng, d, *extra, out.data_ptr(), ws.data_ptr(), nb.value, None)
+              ng, d, *extra, out.data_ptr(), ws.data_ptr(), nb, None)
     torch.cuda.synchronize()
     return out.cpu().numpy()
 
@@ -158,16 +166,11 @@ def knn_cabi(R, F, k, splits, dev):
     d = R.shape[1]
     sides, r2 = [nan_padded(R, dev), nan_padded(F, dev)], []
     for (buf, ld), rows in zip(sides, (len(R), len(F))):
-        nb = ctypes.c_size_t()
-        _lib.call("tise_knn_workspace_bytes", rows, k, splits, ctypes.byref(nb))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-        out = torch.full((rows,), -1.0, dtype=torch.float64, device=dev)
-        _lib.call("tise_knn_radius2", buf.data_ptr(), rows, ld, d, k, splits, out.data_ptr(), ws.data_ptr(), nb.value, None)
+        ws, nb, (out,) = sized_and_filled(dev, "tise_knn_workspace_bytes", (rows, k, splits), [((rows,), torch.float64)], -1.0)
+        _lib.call("tise_knn_radius2", buf.data_ptr(), rows, ld, d, k, splits, out.data_ptr(), ws.data_ptr(), nb, None)
         r2.append(out)
     n, m = len(R), len(F)
-    cnt = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    rec = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    prec = torch.full((m,), -1, dtype=torch.int32, device=dev)
+    cnt, rec, prec = (torch.full((rows,), -1, dtype=torch.int32, device=dev) for rows in (n, n, m))
     ws = torch.empty(8 * (n + m), dtype=torch.uint8, device=dev)
     _lib.call("tise_prdc_counts", sides[0][0].data_ptr(), n, sides[0][1], r2[0].data_ptr(), sides[1][0].data_ptr(), m, sides[1][1],
               r2[1].data_ptr(), d, splits, cnt.data_ptr(), rec.data_ptr(), prec.data_ptr(), ws.data_ptr(), ws.numel(), None)

@@ -121,95 +121,3 @@ __device__ __forceinline__ void gemm_tile_store(double* __restrict__ C, int64_t 
                 }
             }
 }
-
-// ---- NT form on GATHERED fp32 rows (csrc/mmd.hip): acc += A B^T, tile row m of A = an arbitrary row of a feature matrix.
-// Both operands are contiguous along k, so a slab is 64 rows x GT_RK k-values per operand, fetched as float4 (8 in flight per
-// thread under 64 MFMAs per wave on the previous slab -- the depth the covariance kernel's fast path needs, stats.hip) and kept
-// fp32 in LDS as [row][k]; the widening to fp64 is exact and happens in registers.  Pitch 68 floats: the ds_read_b32 of a
-// fragment (row = lane & 15, k = lane >> 4) lands on bank (4 row + k) mod 64 -- all 64 lanes on different banks -- and a row
-// stays 16-byte aligned for the float4 stores.  The existing tile above is untouched.
-#define GT_RK 64
-#define GT_RP 68
-#define GT_ROWS_LDS_FLOATS (2 * 64 * GT_RP)
-
-struct GtRowFetch {
-    float4 v[4];
-    const float* row[4];          // tile rows (tid >> 4) + 16 q, already advanced to this thread's k offset (tid & 15) * 4
-    // rows x0 .. x0 + 63 of a group of n >= 1 rows that starts at r0: row r0 + m of `base` (index == nullptr) or row
-    // index[r0 + m].  Rows past the group are fetched from its last row: the caller masks them in its epilogue.
-    __device__ __forceinline__ void bind(const float* __restrict__ base, int64_t ld, const int64_t* __restrict__ index,
-                                         int64_t r0, int x0, int n, int tid) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int m = x0 + (tid >> 4) + 16 * q;
-            m = m < n ? m : n - 1;
-            const int64_t r = index ? index[r0 + m] : r0 + m;
-            row[q] = base + r * ld + (tid & 15) * 4;
-        }
-    }
-    // k0 % 4 == 0, rows 16-byte aligned (ld % 4 == 0): a float4 that lies inside [0, d) is one load, the tail of a row whose d
-    // is not a multiple of 4 is read element by element, nothing at or beyond column d is touched
-    __device__ __forceinline__ void load(int k0, int d, int tid) {
-        const int k = k0 + (tid & 15) * 4;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (k + 3 < d) {
-                v[q] = *reinterpret_cast<const float4*>(row[q] + k0);
-            } else {
-                v[q].x = k < d ? row[q][k0] : 0.f;
-                v[q].y = k + 1 < d ? row[q][k0 + 1] : 0.f;
-                v[q].z = k + 2 < d ? row[q][k0 + 2] : 0.f;
-                v[q].w = 0.f;
-            }
-        }
-    }
-    __device__ __forceinline__ void store(float* __restrict__ lds, int tid) const {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<float4*>(lds + ((tid >> 4) + 16 * q) * GT_RP + (tid & 15) * 4) = v[q];
-    }
-};
-
-// The squared distance the callers form from the tile, d2 = max(0, (|a|^2 + |b|^2) - 2 a.b), must not hide a row that holds a
-// NaN or an infinity: fmax returns the operand that is not NaN and would turn such a pair into d2 = 0, the nearest neighbour of
-// every row.  The rule (include/tise_hip.h, "Non-finite feature rows"): the norm pre-pass writes NaN for a row whose sum of
-// squares is not finite, and the clamp keeps a NaN, so d2 of every pair with such a row is NaN and every comparison with it is
-// false.  For finite operands both functions return the bits they were given (the difference is never -0: the norms are sums
-// of squares from +0 and the accumulators start at +0).
-__device__ __forceinline__ double rows_norm2_or_nan(double s) { return __builtin_isfinite(s) ? s : __builtin_nan(""); }
-__device__ __forceinline__ double rows_clamp_d2(double x) { return x < 0.0 ? 0.0 : x; }
-
-// acc[tm][tn] += sum_k A(m, k) B(n, k) over k in [0, d); same wave grid and accumulator layout as gemm_tile_64x64
-__device__ __forceinline__ void gemm_tile_64x64_rows_f32(GtRowFetch& fa, GtRowFetch& fb, int d, double4_t (&acc)[2][2],
-                                                         float* lds) {
-    float* As = lds;
-    float* Bs = lds + 64 * GT_RP;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int fi = lane & 15, fk = lane >> 4;
-    fa.load(0, d, tid);
-    fb.load(0, d, tid);
-    for (int k0 = 0; k0 < d; k0 += GT_RK) {
-        fa.store(As, tid);
-        fb.store(Bs, tid);
-        __syncthreads();
-        if (k0 + GT_RK < d) {
-            fa.load(k0 + GT_RK, d, tid);
-            fb.load(k0 + GT_RK, d, tid);
-        }
-#pragma unroll
-        for (int kk = 0; kk < GT_RK; kk += 4) {
-            const double a0 = (double)As[(wr * 32 + fi) * GT_RP + kk + fk];
-            const double a1 = (double)As[(wr * 32 + 16 + fi) * GT_RP + kk + fk];
-            const double b0 = (double)Bs[(wc * 32 + fi) * GT_RP + kk + fk];
-            const double b1 = (double)Bs[(wc * 32 + 16 + fi) * GT_RP + kk + fk];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-}

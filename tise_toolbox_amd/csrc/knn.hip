@@ -1,9 +1,9 @@
 // k-nearest-neighbour manifold passes of improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et
 // al. 2020) on fp32 feature rows that stay on the device.  Squared distances come from the expansion
 //     d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)
-// in fp64: a.b from the gathered-row fp64 MFMA tile of gemm_tile.h (every fp32 x fp32 product is exact in fp64), the norms from
-// knn_row_norm2_kernel (exact squares, fixed order; NaN for a row that holds a NaN or an infinity, and the clamp keeps a NaN --
-// gemm_tile.h: such a row is nobody's neighbour, lies in no ball, and its own r2 is NaN).  No N x N matrix is written: a
+// in fp64 (rows_tile.h's rows_d2): a.b from the gathered-row fp64 MFMA tile (every fp32 x fp32 product is exact in fp64), the norms
+// from rows_norm2_kernel (exact squares, fixed order; NaN for a row that holds a NaN or an infinity, and the clamp keeps a NaN --
+// rows_tile.h: such a row is nobody's neighbour, lies in no ball, and its own r2 is NaN).  No N x N matrix is written: a
 // workgroup turns the accumulators of one 64 x 64 tile into d2 and consumes them on the spot.
 //
 // One value per pair, whatever the pass.  a.b is accumulated over k in the tile's fixed order, and a step fma(a_k, b_k, acc) does
@@ -14,7 +14,7 @@
 // Grid of both tile kernels: (row tiles of 64) x (S column splits); workgroup (tm, s) walks column tiles [s T / S, (s + 1) T / S).
 //
 // Kernels
-//   knn_row_norm2_kernel   one wave per row; bound: HBM (reads the rows once)
+//   rows_norm2_kernel      (rows_tile.h) one wave per row; bound: HBM (reads the rows once)
 //   knn_radius2_kernel     within-set pass; after each tile's K loop the 64 x 64 d2 values are staged in the slab buffer (free after
 //                          the K loop's last barrier) and thread t < 64 folds row t's 64 values into its running k-smallest list;
 //                          k candidates per (row, split) at the end.  bound: fp64 MFMA for d in the thousands (64 * 64 * 2 * d flop
@@ -27,7 +27,7 @@
 // Reproducible by construction: the only cross-workgroup combination is integer add / or (order-independent) and a minimum
 // selection over candidates (order-independent); there are no floating-point atomics.
 #include "common.h"
-#include "gemm_tile.h"
+#include "rows_tile.h"
 
 #define KNN_MAX_K 16
 #define KNN_MAX_ROWS ((int64_t)1 << 24)
@@ -35,21 +35,6 @@
 #define KNN_TP 65        // pitch in doubles of the staged d2 tile: 64 * 65 * 8 = 33 280 bytes <= the 34 816 of the slab buffer
 
 static_assert(64 * KNN_TP * sizeof(double) <= GT_ROWS_LDS_FLOATS * sizeof(float), "the staged tile must fit the slab buffer");
-
-// fp64 |x|^2 per row: lane l adds the exact squares of columns l, l + 64, ... in order, then the fixed butterfly
-__global__ __launch_bounds__(256) void knn_row_norm2_kernel(const float* __restrict__ X, int64_t ld, int n, int d,
-                                                            double* __restrict__ out) {
-    const int row = blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n) return;                                     // wave-uniform
-    const float* p = X + (int64_t)row * ld;
-    double s = 0.0;
-    for (int c = lane; c < d; c += 64) {
-        const double v = (double)p[c];
-        s += v * v;
-    }
-    s = wave_sum(s);
-    if (lane == 0) out[row] = rows_norm2_or_nan(s);
-}
 
 // ascending list of the KL smallest values met
 template <int KL>
@@ -72,18 +57,12 @@ __global__ __launch_bounds__(256, 2) void knn_radius2_kernel(const float* __rest
     const int tm = blockIdx.x, s = blockIdx.y, S = gridDim.y;
     const int T = (n + 63) >> 6;
     const int t0 = (int)((int64_t)s * T / S), t1 = (int)((int64_t)(s + 1) * T / S);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
+    const int tid = threadIdx.x;
+    const GtAccLanes at;
     GtRowFetch fa, fb;
     fa.bind(X, ld, nullptr, 0, tm * 64, n, tid);
     double na[2][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
-            na[a][r] = norm[row < n ? row : n - 1];
-        }
+    gt_rows_load(na, norm, tm * 64, n, at);
     double best[KL];
 #pragma unroll
     for (int j = 0; j < KL; ++j) best[j] = __builtin_inf();
@@ -91,22 +70,19 @@ __global__ __launch_bounds__(256, 2) void knn_radius2_kernel(const float* __rest
     for (int tn = t0; tn < t1; ++tn) {
         fb.bind(X, ld, nullptr, 0, tn * 64, n, tid);
         double4_t acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
+        gt_acc_zero(acc);
         gemm_tile_64x64_rows_f32(fa, fb, d, acc, lds);
         // every wave is past the K loop's last barrier: the slab buffer is free.  i == j and columns past n become +inf
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const int cl = wc * 32 + b * 16 + (lane & 15), col = tn * 64 + cl;
+            const int cl = at.col(b), col = tn * 64 + cl;
             const double nb = norm[col < n ? col : n - 1];
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int rl = wr * 32 + a * 16 + (lane >> 4) + 4 * r, row = tm * 64 + rl;
-                    const double v = rows_clamp_d2((na[a][r] + nb) - 2.0 * acc[a][b][r]);
+                    const int rl = at.row(a, r), row = tm * 64 + rl;
+                    const double v = rows_d2(na[a][r], nb, acc[a][b][r]);
                     tile[rl * KNN_TP + cl] = (col < n && row != col) ? v : __builtin_inf();
                 }
         }
@@ -155,34 +131,24 @@ __global__ __launch_bounds__(256, 2) void prdc_counts_kernel(const float* __rest
     const int tm = blockIdx.x, s = blockIdx.y, S = gridDim.y;
     const int T = (m + 63) >> 6;
     const int t0 = (int)((int64_t)s * T / S), t1 = (int)((int64_t)(s + 1) * T / S);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const GtAccLanes at;
     if (tid < 64) row_cnt[tid] = row_rec[tid] = 0;
     __syncthreads();
     GtRowFetch fa, fb;
     fa.bind(R, ldr, nullptr, 0, tm * 64, n, tid);
     double na[2][4], ra[2][4];
-    int c_cnt[2][4], c_rec[2][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
-            na[a][r] = norm_r[row < n ? row : n - 1];
-            ra[a][r] = r2r[row < n ? row : n - 1];
-            c_cnt[a][r] = c_rec[a][r] = 0;
-        }
+    int c_cnt[2][4] = {}, c_rec[2][4] = {};
+    gt_rows_load(na, norm_r, tm * 64, n, at);
+    gt_rows_load(ra, r2r, tm * 64, n, at);
     for (int tn = t0; tn < t1; ++tn) {
         fb.bind(F, ldf, nullptr, 0, tn * 64, m, tid);
         double4_t acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
+        gt_acc_zero(acc);
         gemm_tile_64x64_rows_f32(fa, fb, d, acc, lds);
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const int col = tn * 64 + wc * 32 + b * 16 + (lane & 15);
+            const int col = tn * 64 + at.col(b);
             const bool col_on = col < m;
             const double nb = norm_f[col_on ? col : m - 1], rb = r2f[col_on ? col : m - 1];
             int hit = 0;                                      // some real row of this thread has the column inside its ball
@@ -190,8 +156,8 @@ __global__ __launch_bounds__(256, 2) void prdc_counts_kernel(const float* __rest
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
-                    const double v = rows_clamp_d2((na[a][r] + nb) - 2.0 * acc[a][b][r]);
+                    const int row = tm * 64 + at.row(a, r);
+                    const double v = rows_d2(na[a][r], nb, acc[a][b][r]);
                     const bool on = col_on && row < n;
                     const int in_r = (on && v < ra[a][r]) ? 1 : 0, in_f = (on && v < rb) ? 1 : 0;
                     c_cnt[a][r] += in_r;
@@ -209,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void prdc_counts_kernel(const float* __rest
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int rl = wr * 32 + a * 16 + (lane >> 4) + 4 * r;
+            const int rl = at.row(a, r);
             if (c_cnt[a][r]) atomicAdd(&row_cnt[rl], c_cnt[a][r]);
             if (c_rec[a][r]) atomicOr(&row_rec[rl], 1);
         }
@@ -234,15 +200,10 @@ static int knn_splits(int64_t rows, int64_t cols, int col_splits) {
 }
 
 static int knn_side_check(const float* p, int64_t rows, int64_t ld, int d, int64_t min_rows) {
-    if (!p || rows < min_rows || ld < d || (ld & 3) || (reinterpret_cast<uintptr_t>(p) & 15)) return TISE_ERR_INVALID_ARG;
-    if (rows > KNN_MAX_ROWS || rows > ((int64_t)1 << 40) / ld) return TISE_ERR_UNSUPPORTED;
-    return TISE_OK;
-}
-
-static int knn_norms(const float* x, int64_t rows, int64_t ld, int d, double* out, hipStream_t st) {
-    hipLaunchKernelGGL(knn_row_norm2_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, ld, (int)rows, d, out);
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    if (!p || rows < min_rows) return TISE_ERR_INVALID_ARG;
+    const int rc = rows_layout_check(p, rows, ld, d);
+    if (rc != TISE_OK) return rc;
+    return rows > KNN_MAX_ROWS ? TISE_ERR_UNSUPPORTED : TISE_OK;
 }
 
 extern "C" {
@@ -256,7 +217,7 @@ int tise_knn_workspace_bytes(int64_t rows, int k, int col_splits, size_t* bytes)
 
 int tise_knn_radius2(const float* x_dev, int64_t rows, int64_t ld, int d, int k, int col_splits, double* r2_dev, void* ws_dev,
                      size_t ws_bytes, void* stream) {
-    if (d <= 0 || d > (1 << 20) || k < 1 || k > KNN_MAX_K || col_splits < 0 || col_splits > KNN_MAX_SPLITS) return TISE_ERR_INVALID_ARG;
+    if (k < 1 || k > KNN_MAX_K || col_splits < 0 || col_splits > KNN_MAX_SPLITS) return TISE_ERR_INVALID_ARG;
     int rc = knn_side_check(x_dev, rows, ld, d, (int64_t)k + 1);
     if (rc != TISE_OK) return rc;
     if (!r2_dev || (reinterpret_cast<uintptr_t>(r2_dev) & 7)) return TISE_ERR_INVALID_ARG;
@@ -268,7 +229,7 @@ int tise_knn_radius2(const float* x_dev, int64_t rows, int64_t ld, int d, int k,
     const int S = knn_splits(rows, rows, col_splits), n = (int)rows;
     double* norm = reinterpret_cast<double*>(ws_dev);
     double* cand = norm + rows;
-    rc = knn_norms(x_dev, rows, ld, d, norm, st);
+    rc = rows_norm2(x_dev, ld, nullptr, 0, rows, nullptr, 0, nullptr, 0, 0, d, norm, st);
     if (rc != TISE_OK) return rc;
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)S);
     if (k <= 4) hipLaunchKernelGGL(knn_radius2_kernel<4>, grid, dim3(256), 0, st, x_dev, ld, n, d, k, norm, cand);
@@ -283,7 +244,7 @@ int tise_knn_radius2(const float* x_dev, int64_t rows, int64_t ld, int d, int k,
 int tise_prdc_counts(const float* r_dev, int64_t rows_r, int64_t ld_r, const double* r2_r_dev, const float* f_dev, int64_t rows_f,
                      int64_t ld_f, const double* r2_f_dev, int d, int col_splits, int32_t* cnt_dev, int32_t* rec_dev,
                      int32_t* prec_dev, void* ws_dev, size_t ws_bytes, void* stream) {
-    if (d <= 0 || d > (1 << 20) || col_splits < 0 || col_splits > KNN_MAX_SPLITS) return TISE_ERR_INVALID_ARG;
+    if (col_splits < 0 || col_splits > KNN_MAX_SPLITS) return TISE_ERR_INVALID_ARG;
     int rc = knn_side_check(r_dev, rows_r, ld_r, d, 1);
     if (rc != TISE_OK) return rc;
     rc = knn_side_check(f_dev, rows_f, ld_f, d, 1);
@@ -299,9 +260,7 @@ int tise_prdc_counts(const float* r_dev, int64_t rows_r, int64_t ld_r, const dou
     TISE_HIP_CHECK(hipMemsetAsync(cnt_dev, 0, sizeof(int32_t) * (size_t)n, st));
     TISE_HIP_CHECK(hipMemsetAsync(rec_dev, 0, sizeof(int32_t) * (size_t)n, st));
     TISE_HIP_CHECK(hipMemsetAsync(prec_dev, 0, sizeof(int32_t) * (size_t)m, st));
-    rc = knn_norms(r_dev, rows_r, ld_r, d, norm_r, st);
-    if (rc != TISE_OK) return rc;
-    rc = knn_norms(f_dev, rows_f, ld_f, d, norm_f, st);
+    rc = rows_norm2(r_dev, ld_r, nullptr, 0, rows_r, f_dev, ld_f, nullptr, 0, rows_f, d, norm_r, st);   // norm_f = norm_r + rows_r
     if (rc != TISE_OK) return rc;
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)knn_splits(rows_r, rows_f, col_splits));
     hipLaunchKernelGGL(prdc_counts_kernel, grid, dim3(256), 0, st, r_dev, ld_r, n, r2_r_dev, f_dev, ld_f, m, r2_f_dev, d, norm_r,

@@ -2,7 +2,7 @@
 //     k(a, b) = (a.b / d + 1)^3        Sxx = sum_{i != j} k(x_i, x_j)    Syy = sum_{i != j} k(y_i, y_j)    Sxy = sum_{i, j} k(x_i, y_j)
 // for MANY groups of rows in one launch pair -- the 100 random subsets of the KID estimate, or the 80 classes of a per-class
 // run -- from fp32 feature rows that never leave the device.  No Gram matrix is written: a workgroup forms one 64 x 64 block of
-// dot products in fp64 on v_mfma_f64_16x16x4_f64 (gemm_tile.h, gathered-row form; every fp32 x fp32 product is exact in fp64),
+// dot products in fp64 on v_mfma_f64_16x16x4_f64 (rows_tile.h; every fp32 x fp32 product is exact in fp64),
 // applies the kernel to its accumulator registers and keeps ONE number.
 //
 // Work list.  Group g contributes three segments (xx, yy, xy) in that order; a symmetric segment of T = ceil(n / 64) row tiles
@@ -19,9 +19,9 @@
 // Gaussian kernel (CMMD: Jayasumana et al. 2024, "Rethinking FID"; tise_mmd_rbf_grouped).  The same work list, tile and reductions
 // with another epilogue,
 //     k(a, b) = exp(-gamma d2(a, b)),      d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)
-// d2 by csrc/knn.hip's rule: a.b from the tile, |.|^2 from mmd_row_norm2_kernel (exact squares, that file's fixed order) into the
-// workspace, one double per group position of each side, parenthesised so that d2 of a pair is the same bits whichever side
-// each row is on.  A row that holds a NaN or an infinity has the norm NaN and the clamp keeps a NaN (gemm_tile.h): every kernel
+// d2 is rows_tile.h's rows_d2, the function csrc/knn.hip calls: a.b from the tile, |.|^2 from rows_norm2_kernel into the
+// workspace, one double per group position of each side, so that d2 of a pair is the same bits whichever side each row is
+// on.  A row that holds a NaN or an infinity has the norm NaN and the clamp keeps a NaN (rows_tile.h): every kernel
 // value of a pair with it is NaN, so the sums that involve the row are NaN and no other sum of the launch moves.  exp is the
 // fp64 library function.  Its cost against the tile's MFMA work has not been measured.
 //
@@ -29,11 +29,11 @@
 //   mmd_tiles_kernel<MMD_POLY3>   bound: fp64 MFMA for d in the thousands (64 * 64 * 2 * d flop per tile against 2 * 64 * d * 4
 //                                 bytes fetched, mostly from L2: the rows of a group are shared by all its tiles)
 //   mmd_tiles_kernel<MMD_RBF>     the same tile + 16 fp64 exp per thread; bound: not measured
-//   mmd_row_norm2_kernel          one wave per group position; bound: HBM (reads the rows once)
+//   rows_norm2_kernel             (rows_tile.h) one wave per group position; bound: HBM (reads the rows once)
 //   mmd_reduce_kernel             bound: latency (8 bytes per tile)
 #include <vector>
 #include "common.h"
-#include "gemm_tile.h"
+#include "rows_tile.h"
 
 struct MmdSeg {
     int64_t a0, b0;     // first row (contiguous form) or first index entry (indexed form) of the A / B side's group
@@ -53,29 +53,6 @@ struct MmdRbf {
     int64_t x0, y0;
     double gamma;
 };
-
-// fp64 |row|^2 of every group position of both sides: wave w takes position w of the x side, or w - cx of the y side; lane l adds
-// the exact squares of columns l, l + 64, ... in order, then the fixed butterfly (knn_row_norm2_kernel's order)
-__global__ __launch_bounds__(256) void mmd_row_norm2_kernel(const float* __restrict__ X, int64_t ldx, const int64_t* __restrict__ ix,
-                                                            int64_t x0, int64_t cx, const float* __restrict__ Y, int64_t ldy,
-                                                            const int64_t* __restrict__ iy, int64_t y0, int64_t cy, int d,
-                                                            double* __restrict__ out) {
-    const int64_t w = (int64_t)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (w >= cx + cy) return;                                 // wave-uniform
-    const bool y = w >= cx;
-    const int64_t p = y ? y0 + (w - cx) : x0 + w;
-    const int64_t* idx = y ? iy : ix;
-    const int64_t r = idx ? idx[p] : p;
-    const float* row = (y ? Y : X) + r * (y ? ldy : ldx);
-    double s = 0.0;
-    for (int c = lane; c < d; c += 64) {
-        const double v = (double)row[c];
-        s += v * v;
-    }
-    s = wave_sum(s);
-    if (lane == 0) out[w] = rows_norm2_or_nan(s);
-}
 
 template <int KF>
 __global__ __launch_bounds__(256, 2) void mmd_tiles_kernel(const float* __restrict__ X, int64_t ldx,
@@ -105,16 +82,13 @@ __global__ __launch_bounds__(256, 2) void mmd_tiles_kernel(const float* __restri
         tn = t - tm * sg.tcols;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
+    const GtAccLanes at;
     const bool a_is_y = sg.kind == 1, b_is_x = sg.kind == 0;
     GtRowFetch fa, fb;
     fa.bind(a_is_y ? Y : X, a_is_y ? ldy : ldx, a_is_y ? iy : ix, sg.a0, tm * 64, sg.na, tid);
     fb.bind(b_is_x ? X : Y, b_is_x ? ldx : ldy, b_is_x ? ix : iy, sg.b0, tn * 64, sg.nb, tid);
     double4_t acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    gt_acc_zero(acc);
     gemm_tile_64x64_rows_f32(fa, fb, d, acc, lds);
 
     const bool diag = sym && tm == tn;
@@ -129,35 +103,28 @@ __global__ __launch_bounds__(256, 2) void mmd_tiles_kernel(const float* __restri
             for (int b = 0; b < 2; ++b)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
-                    const int col = tn * 64 + wc * 32 + b * 16 + (lane & 15);
+                    const int row = tm * 64 + at.row(a, r), col = tn * 64 + at.col(b);
                     const double v = acc[a][b][r] / dd + 1.0;
                     const bool on = row < sg.na && col < sg.nb && !(diag && row == col);
                     s += on ? v * v * v : 0.0;
                 }
     } else {
-        // k = exp(-gamma d2) on the accumulator registers, d2 as csrc/knn.hip forms it; the same masks.  A row or column past
+        // k = exp(-gamma d2) on the accumulator registers, d2 = rows_d2 as in csrc/knn.hip; the same masks.  A row or column past
         // the group reads its last position's norm (the tile fetched that row too) and is masked.
         const double* norm_a = a_is_y ? rbf.ny + (sg.a0 - rbf.y0) : rbf.nx + (sg.a0 - rbf.x0);
         const double* norm_b = b_is_x ? rbf.nx + (sg.b0 - rbf.x0) : rbf.ny + (sg.b0 - rbf.y0);
         double na[2][4];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
-                na[a][r] = norm_a[row < sg.na ? row : sg.na - 1];
-            }
+        gt_rows_load(na, norm_a, tm * 64, sg.na, at);
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const int col = tn * 64 + wc * 32 + b * 16 + (lane & 15);
+            const int col = tn * 64 + at.col(b);
             const double nb = norm_b[col < sg.nb ? col : sg.nb - 1];
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int row = tm * 64 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
-                    const double d2 = rows_clamp_d2((na[a][r] + nb) - 2.0 * acc[a][b][r]);
+                    const int row = tm * 64 + at.row(a, r);
+                    const double d2 = rows_d2(na[a][r], nb, acc[a][b][r]);
                     const bool on = row < sg.na && col < sg.nb && !(diag && row == col);
                     s += on ? exp(-rbf.gamma * d2) : 0.0;
                 }
@@ -240,8 +207,9 @@ int tise_mmd_poly3_workspace_bytes(const int64_t* offsets_x_host, const int64_t*
 
 static int mmd_side_check(const float* p, int64_t rows, int64_t ld, const int64_t* index, int64_t n_index, const int64_t* off,
                           int n_groups, int d) {
-    if (rows < 0 || n_index < 0 || ld < d || (ld & 3) || (!p && rows > 0) || (reinterpret_cast<uintptr_t>(p) & 15)) return TISE_ERR_INVALID_ARG;
-    if (rows > ((int64_t)1 << 40) / ld) return TISE_ERR_UNSUPPORTED;
+    if (n_index < 0 || (!p && rows > 0)) return TISE_ERR_INVALID_ARG;
+    const int rc = rows_layout_check(p, rows, ld, d);
+    if (rc != TISE_OK) return rc;
     const int64_t last = n_groups > 0 ? off[n_groups] : 0;
     if (last > (index ? n_index : rows)) return TISE_ERR_INVALID_ARG;              // a group would reach past the rows / the index
     if (index && last > 0 && rows == 0) return TISE_ERR_INVALID_ARG;               // an index into no rows
@@ -251,13 +219,11 @@ static int mmd_side_check(const float* p, int64_t rows, int64_t ld, const int64_
 // rows of one side that enter some group: positions offsets[0] .. offsets[n_groups] - 1 (mmd_plan has checked the order)
 static int64_t mmd_used(const int64_t* off, int n_groups) { return n_groups > 0 ? off[n_groups] - off[0] : 0; }
 
-static size_t mmd_norm_offset(size_t table, int64_t total) { return table + (size_t)total * sizeof(double); }
-
 static int mmd_grouped(int kf, double gamma, const float* x_dev, int64_t rows_x, int64_t ld_x, const int64_t* index_x_dev,
                        int64_t n_index_x, const int64_t* offsets_x_host, const float* y_dev, int64_t rows_y, int64_t ld_y,
                        const int64_t* index_y_dev, int64_t n_index_y, const int64_t* offsets_y_host, int n_groups, int d,
                        double* out_dev, void* ws_dev, size_t ws_bytes, void* stream) {
-    if (d <= 0 || d > (1 << 20) || !out_dev) return TISE_ERR_INVALID_ARG;
+    if (!rows_width_ok(d) || !out_dev) return TISE_ERR_INVALID_ARG;
     if (kf == MMD_RBF && !(gamma >= 0.0 && gamma <= 1.7976931348623157e308)) return TISE_ERR_INVALID_ARG;   // NaN, inf, < 0
     std::vector<MmdSeg> segs;
     int64_t total = 0;
@@ -270,7 +236,7 @@ static int mmd_grouped(int kf, double gamma, const float* x_dev, int64_t rows_x,
     if (n_groups == 0) return TISE_OK;
     const size_t table = mmd_table_bytes(n_groups);
     const int64_t cx = kf == MMD_RBF ? mmd_used(offsets_x_host, n_groups) : 0, cy = kf == MMD_RBF ? mmd_used(offsets_y_host, n_groups) : 0;
-    const size_t need = mmd_norm_offset(table, total) + (size_t)(cx + cy) * sizeof(double);
+    const size_t need = table + (size_t)(total + cx + cy) * sizeof(double);
     if (!ws_dev || (reinterpret_cast<uintptr_t>(ws_dev) & 7) || ws_bytes < need) return TISE_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     MmdSeg* segs_dev = reinterpret_cast<MmdSeg*>(ws_dev);
@@ -284,9 +250,8 @@ static int mmd_grouped(int kf, double gamma, const float* x_dev, int64_t rows_x,
         double* norm = partial + total;
         rbf = {norm, norm + cx, offsets_x_host[0], offsets_y_host[0], gamma};
         if (cx + cy > 0) {
-            hipLaunchKernelGGL(mmd_row_norm2_kernel, dim3((unsigned)((cx + cy + 3) / 4)), dim3(256), 0, st, x_dev, ld_x, index_x_dev,
-                               rbf.x0, cx, y_dev, ld_y, index_y_dev, rbf.y0, cy, d, norm);
-            TISE_LAUNCH_CHECK();
+            rc = rows_norm2(x_dev, ld_x, index_x_dev, rbf.x0, cx, y_dev, ld_y, index_y_dev, rbf.y0, cy, d, norm, st);
+            if (rc != TISE_OK) return rc;
         }
     }
     if (total > 0) {

@@ -429,7 +429,7 @@ def mmd_index(index, rows, what):
 
 
 def _rows_side(t, what):
-    """A (rows, d) float32 CUDA tensor as the gathered-row fetch of csrc/gemm_tile.h needs it: unit column stride, row stride a
+    """A (rows, d) float32 CUDA tensor as the gathered-row fetch of csrc/rows_tile.h needs it: unit column stride, row stride a
     multiple of 4 and >= d, 16-byte aligned base -- the tensor itself when it already is, else a copy (padded when d % 4 != 0)."""
     _require_cuda(t)
     if t.dim() != 2 or t.dtype != torch.float32:
@@ -443,10 +443,9 @@ def _rows_side(t, what):
     return t
 
 
-class _GroupedMMD:
-    """What the grouped kernel-sum entry points of csrc/mmd.hip share on this side: the workspace, the host checks and ``sums``."""
-
-    _FN = None                                                    # C ABI prefix: <_FN>_workspace_bytes, <_FN>_grouped
+class _RowsTileUser:
+    """What the classes over the gathered-row tile (csrc/rows_tile.h) share on this side: the device check and one grow-only
+    byte workspace."""
 
     def __init__(self, device=None):
         self.device = torch.device(device if device is not None else "cuda")
@@ -454,19 +453,27 @@ class _GroupedMMD:
             raise _lib.TiseLibraryError(f"{type(self).__name__} needs a HIP device")
         self._ws = None
 
+    def _workspace(self, nbytes):
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(max(256, nbytes), dtype=torch.uint8, device=self.device)
+        return self._ws
+
+
+class _GroupedMMD(_RowsTileUser):
+    """What the grouped kernel-sum entry points of csrc/mmd.hip share on this side: the host checks and ``sums``."""
+
+    _FN = None                                                    # C ABI prefix: <_FN>_workspace_bytes, <_FN>_grouped
+
     def _kernel_args(self):
         """The kernel function's own arguments, between ``d`` and ``out_dev`` in the C signature."""
         return ()
-
-    def _side(self, t, what):
-        return _rows_side(t, what)
 
     def sums(self, X, Y, offsets_x, offsets_y, index_x=None, index_y=None):
         """X (rows_x, d), Y (rows_y, d): fp32 CUDA tensors (row stride may exceed d).  offsets_*: n_groups + 1 host integers
         per side.  index_* (host integer arrays, optional): with an index, group g of that side is the rows
         index[offsets[g]:offsets[g + 1]], else the contiguous rows offsets[g]:offsets[g + 1].  -> (n_groups, 3) fp64 CUDA tensor
         [Sxx, Syy, Sxy]; the groups' sizes come back as two int64 arrays in ``last_counts``."""
-        X, Y = self._side(X, "X"), self._side(Y, "Y")
+        X, Y = _rows_side(X, "X"), _rows_side(Y, "Y")
         if X.shape[1] != Y.shape[1] or X.shape[1] < 1:
             raise ValueError("X and Y must have the same, positive number of columns")
         ix = mmd_index(index_x, X.shape[0], "index_x") if index_x is not None else None
@@ -487,14 +494,13 @@ class _GroupedMMD:
             poy = oy.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
             nbytes = ctypes.c_size_t()
             _lib.call(self._FN + "_workspace_bytes", pox, poy, ng, ctypes.byref(nbytes))
-            if self._ws is None or self._ws.numel() < nbytes.value:
-                self._ws = torch.empty(max(256, nbytes.value), dtype=torch.uint8, device=self.device)
+            ws = self._workspace(nbytes.value)
             _lib.call(self._FN + "_grouped",
                       _ptr(X), X.shape[0], X.stride(0) if X.shape[0] else X.shape[1] + (-X.shape[1]) % 4, _ptr(ixd) if ixd is not None else None,
                       ix.size if ix is not None else 0, pox,
                       _ptr(Y), Y.shape[0], Y.stride(0) if Y.shape[0] else Y.shape[1] + (-Y.shape[1]) % 4, _ptr(iyd) if iyd is not None else None,
-                      iy.size if iy is not None else 0, poy, ng, int(X.shape[1]), *self._kernel_args(), _ptr(out), _ptr(self._ws),
-                      self._ws.numel(), _stream())
+                      iy.size if iy is not None else 0, poy, ng, int(X.shape[1]), *self._kernel_args(), _ptr(out), _ptr(ws),
+                      ws.numel(), _stream())
         return out
 
 
@@ -531,20 +537,9 @@ class GaussianMMD(_GroupedMMD):
         return (ctypes.c_double(self.gamma),)
 
 
-class KnnManifold:
+class KnnManifold(_RowsTileUser):
     """k-nearest-neighbour radii and the precision / recall / density / coverage counts on resident fp32 rows (tise_knn_radius2
     and tise_prdc_counts in include/tise_hip.h; csrc/knn.hip).  Owns the workspace; bitwise reproducible."""
-
-    def __init__(self, device=None):
-        self.device = torch.device(device if device is not None else "cuda")
-        if self.device.type != "cuda":
-            raise _lib.TiseLibraryError("KnnManifold needs a HIP device")
-        self._ws = None
-
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(max(256, nbytes), dtype=torch.uint8, device=self.device)
-        return self._ws
 
     def radius2(self, X, k, col_splits=0):
         """X (n, d) fp32 CUDA tensor (row stride may exceed d), n >= k + 1, 1 <= k <= 16 -> (n,) fp64 CUDA tensor: the squared
