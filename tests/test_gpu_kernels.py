@@ -1107,7 +1107,9 @@ def test_split_overflow_guard_fires_and_clears(dev):
     engine turns it into FloatingPointError instead of silently carrying +inf through the trunk.  (A NaN does NOT raise it
     at these sites -- their ReLU, fmaxf, turns it into 0 first; it reaches the guard's maximum only in split_mean.  The
     trunks refuse non-finite parameters instead, and elsewhere a NaN can only follow an overflow, which raises the flag
-    first: tests/test_gpu_nonfinite.py.)"""
+    first: tests/test_gpu_nonfinite.py.)
+    These launches plant the overflow in ALL outputs of three small instances; tests/test_gpu_range_guard.py moves a single
+    65536 over every row and cout of every kernel instance, and blows one bias entry of every launch the trunk itself makes."""
     from tise_toolbox_amd import device
     from tise_toolbox_amd.conv_split import SplitConv, merge, split
     device.read_split_overflow()

@@ -90,6 +90,11 @@ __host__ __device__ inline int tise_ilv_second(int c, int C) { return c < (C & ~
 // biases and input tables (trunk.py require_finite_params, conv_split.SplitConv, inception.require_finite_state_dict): the
 // network input is a table look-up of a byte, so with finite parameters the first non-finite value of a pass can only be
 // an fp32 result beyond the fp16 range, and that one raises the flag before the NaN (hi = +inf, lo = -inf) it turns into.
+// What the guard sees BEYOND the stored values: the GRID kernels (conv_pipe.hip configuration 34, plain and POOL) and the
+// pooled epilogues (POOL, the row-window kernel's POOLH) take the maximum before the store mask, so a result that is computed
+// but never stored -- a grid pixel whose window wraps into the next image row, a conv column no 3-wide stride-2 window
+// covers -- can raise the flag although every stored value is legal.  That is conservative (the job reruns on the exact
+// path; masking it would cost instructions in the hottest epilogues) and pinned as a record in tests/test_gpu_range_guard.py.
 // The library is built without relocatable device code, so each translation unit has its OWN word (unnamed
 // namespace) and exports a reader for it with TISE_DEFINE_SPLIT_FLAG_READER.
 #define TISE_F16_MAX 65504.0f

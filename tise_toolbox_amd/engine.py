@@ -259,6 +259,7 @@ class RealismEngine:
         """New image set.  ``rule`` also decides (unless ``fc_bias`` / the constructor's ``fc_bias`` force it) whether the
         classifier bias enters the logits of the following steps: inception.fc_bias_for_rule."""
         self.fc_bias = fc_bias_for_rule(rule, self._fc_bias_mode if fc_bias is None else fc_bias)
+        self._range_hit = False                                         # new accumulators: see _check_accumulated
         self.stats = device.StatsAccumulator(self.dims, self.device)
         self.is_acc = None
         if self.with_logits:
@@ -306,13 +307,25 @@ class RealismEngine:
                 flag = bool(tdist.all_reduce_sum_(t).item() > 0)
             device.check_split_overflow(flag=flag)
 
+    def _check_accumulated(self):
+        """check_numerics for the accumulators of this image set.  The device flag is read-and-clear, the accumulators are not:
+        once the guard fired they hold the wrong rows until the next begin(), so every later statistics() / inception_score()
+        of the same image set raises too (the first call used to clear the flag and the second returned a wrong number)."""
+        try:
+            self.check_numerics()
+        except FloatingPointError:
+            self._range_hit = True
+            raise
+        if getattr(self, "_range_hit", False):
+            device.check_split_overflow(flag=True)
+
     def statistics(self):
         """(mu, sigma) fp64 CUDA tensors of everything accumulated (after reduce())."""
-        self.check_numerics()
+        self._check_accumulated()
         return self.stats.finalize()
 
     def inception_score(self):
-        self.check_numerics()
+        self._check_accumulated()
         mean, std, _ = self.is_acc.finalize()
         return mean, std
 
