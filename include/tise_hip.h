@@ -491,6 +491,13 @@ int tise_cosine_top1(const void* img_emb_dev, const void* txt_emb_dev, const int
  *   tise_patchify_f16    image (batch, 3, res, res) NCHW -> [batch*(res/patch)^2][3*patch*patch], columns in the order of
  *                        conv1.weight.flatten(1): the patch embedding becomes one tise_gemm_f16 (patch % 8 == 0; image /
  *                        out 16-byte aligned)
+ *   tise_attention_long_f16  the same layout and result for ANY seq >= 1, non-causal: keys stream in tiles of
+ *                        tise_attention_long_key_tile() under an online softmax with the exact running maximum; a workgroup
+ *                        of 4 waves serves 128 consecutive queries of one (sequence, head) and stages each K / V tile once
+ *                        in LDS (the image tower of ViT-L/14@336: 577 tokens); head_dim == 64, qkv / out 16-byte aligned
+ *   tise_patchify_pad_f16  tise_patchify_f16's matrix for any patch >= 1 with res % patch == 0, rows padded to kpad columns
+ *                        (kpad >= 3*patch*patch, kpad % 64 == 0: tise_gemm_f16's K-step), the padding written as +0;
+ *                        image 2-byte, out 16-byte aligned
  *   tise_vit_tokens_f16  x[b][0] = class_emb + pos[0]; x[b][1+p] = patch_out[b*n_patches+p] + pos[1+p]
  *   tise_text_tokens_f16 x[r] = table[tokens[r]] + pos[r % seq]
  *   tise_gather_rows_f16 out[i] = x[index[i]]   (class token of every image / end-of-text token of every caption)
@@ -501,6 +508,9 @@ int tise_layernorm_f16(const void* x_dev, int64_t ldx, const void* gamma_dev, co
                        int64_t rows, int C, float eps, void* stream);
 int tise_attention_f16(const void* qkv_dev, int batch, int seq, int heads, int head_dim, int causal, void* out_dev, void* stream);
 int tise_patchify_f16(const void* img_dev, int batch, int res, int patch, void* out_dev, void* stream);
+int tise_attention_long_key_tile(void);
+int tise_attention_long_f16(const void* qkv_dev, int batch, int seq, int heads, int head_dim, void* out_dev, void* stream);
+int tise_patchify_pad_f16(const void* img_dev, int batch, int res, int patch, int kpad, void* out_dev, void* stream);
 int tise_vit_tokens_f16(const void* patch_out_dev, const void* class_emb_dev, const void* pos_emb_dev, int batch, int n_patches,
                         int width, void* x_dev, void* stream);
 int tise_text_tokens_f16(const int32_t* tokens_dev, const void* table_dev, const void* pos_emb_dev, int64_t rows, int seq, int width,

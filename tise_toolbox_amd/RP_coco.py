@@ -46,12 +46,13 @@ def parse_args(argv=None):
     return parser.parse_args(argv)
 
 
-def build_towers(weights_path, dev):
+def build_towers(weights_path, dev, arch=None, seed=0):
     """-> (towers, logit_scale).  ``towers.encode_image`` / ``.encode_text`` in fp16, as the model clip.load serves on a GPU.
     Default: the hand-written kernels of csrc/clip_ops.hip (clip_hip.HipTowers: 1.4x / 2.4x the library-kernel module
     on the image / text tower, profiles/r02x_clip_towers.txt); TISE_CLIP=torch runs the module itself on PyTorch-ROCm
-    library kernels (what north_star prescribes for the forward passes; same parameters, same results to fp16 rounding)."""
-    model = clip_model.build_clip(weights_path)
+    library kernels (what north_star prescribes for the forward passes; same parameters, same results to fp16 rounding).
+    ``arch``: a tower of clip_model.CONFIGS (None: ViT-B/32, what RP-COCO and PA use); ``seed``: of the stand-in parameters."""
+    model = clip_model.build_clip(weights_path, seed, arch)
     scale = float(model.logit_scale.detach().exp())            # clip's convert_weights leaves logit_scale in fp32
     model = model.to(dev).half()
     tdist.broadcast_module_(model)
@@ -178,24 +179,26 @@ def embed_paths(model, paths, dev, batch, workers=0, feed="ring", convert_first=
 @torch.no_grad()
 def encode_paths(model, paths, dev, batch, workers, feed, convert_first, finish, dtype):
     """The image loop embed_paths and cmmd.embed_image_dir share: ``finish(model.encode_image(batch))`` of the files ``paths``, in
-    order, every file used -> (len(paths), 512) tensor of ``dtype``."""
+    order, every file used -> (len(paths), model.out_dim) tensor of ``dtype``.  The images are preprocessed at the tower's
+    own input resolution (``model.resolution``; 224 for a model that does not say) on both roads."""
     out = []
+    size = getattr(model, "resolution", 224)
 
     def consume(loader):
         out.clear()                                           # the DataLoader pass after a ring that met an odd file starts afresh
         for x in loader:
             # the ring delivers uint8 (clip's preprocess on the device), the DataLoader's workers preprocessed fp32
-            f = model.encode_image((clip_model.preprocess_device(x) if x.dtype == torch.uint8 else x.to(dev)).half())
+            f = model.encode_image((clip_model.preprocess_device(x, size) if x.dtype == torch.uint8 else x.to(dev)).half())
             out.append(finish(f))
     feeds.run(feeds.CLIP, paths, feeds.Options(png_feed=feed, num_workers=workers), consume, dev, batch, tdist.world_size(),
               loader_args={"ring": {"batch_size": 1, "group": batch, "rgb_only": not convert_first},
-                           "dataloader": {"dataset": _Paths(paths, convert_first), "pin_memory": False, "collate": None}})
-    return torch.cat(out).contiguous() if out else torch.empty((0, 512), dtype=dtype, device=dev)
+                           "dataloader": {"dataset": _Paths(paths, convert_first, size), "pin_memory": False, "collate": None}})
+    return torch.cat(out).contiguous() if out else torch.empty((0, getattr(model, "out_dim", 512)), dtype=dtype, device=dev)
 
 
 class _Paths(torch.utils.data.Dataset):
-    def __init__(self, paths, convert_first=True):
-        self.paths, self.convert_first = paths, convert_first
+    def __init__(self, paths, convert_first=True, size=224):
+        self.paths, self.convert_first, self.size = paths, convert_first, size
 
     def __len__(self):
         return len(self.paths)
@@ -203,7 +206,7 @@ class _Paths(torch.utils.data.Dataset):
     def __getitem__(self, i):
         from PIL import Image
         img = Image.open(self.paths[i])
-        return clip_model.preprocess(img.convert("RGB") if self.convert_first else img)   # (clip's preprocess converts to RGB itself, after the resize)
+        return clip_model.preprocess(img.convert("RGB") if self.convert_first else img, self.size)   # (clip's preprocess converts to RGB itself, after the resize)
 
 
 def embed_images(model, image_dir, caption_ids, dev, batch, workers=0, feed="ring"):

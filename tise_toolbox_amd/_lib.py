@@ -59,6 +59,9 @@ SIGNATURES = {
     "tise_layernorm_f16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p]),
     "tise_attention_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tise_patchify_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tise_attention_long_key_tile": (c_int, []),
+    "tise_attention_long_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tise_patchify_pad_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tise_vit_tokens_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tise_text_tokens_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "tise_gather_rows_f16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),

@@ -1,10 +1,11 @@
-"""The CLIP ViT-B/32 towers on the hand-written kernels of csrc/clip_ops.hip.
+"""The CLIP towers (ViT-B/32; ViT-L/14@336 for CMMD) on the hand-written kernels of csrc/clip_ops.hip.
 
 ``HipTowers(model)`` takes a ``clip_model.CLIP`` (real OpenAI parameters or the seeded stand-ins), keeps fp16 copies
 of its parameters in the layouts the kernels read, and offers ``encode_image`` / ``encode_text`` with the signatures
 of the module's own methods.  Every matrix product -- the patch embedding (as a GEMM over ``tise_patchify_f16``'s
 patch matrix), the q/k/v, output, MLP and final projections -- is ``tise_gemm_f16`` with bias / QuickGELU / residual
-fused in its epilogue; LayerNorm, attention and the token assembly are the other kernels of that file.  PyTorch only
+fused in its epilogue; LayerNorm, attention (``tise_attention_f16`` up to 96 tokens, ``tise_attention_long_f16`` beyond: the
+577 tokens of L/14@336) and the token assembly are the other kernels of that file.  PyTorch only
 allocates the buffers.  Arithmetic: fp16 tensors, fp32 accumulation and statistics, i.e. what the fp16 model
 ``clip.load`` serves on a GPU computes (third-party `clip`, model.py: ``convert_weights`` + fp32 LayerNorm).
 Parity of the towers themselves stays UNPINNED (no `clip` package, weights or vocabulary here); the tests compare
@@ -47,11 +48,28 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     return out
 
 
+ATTN_LONG_KEY_TILE = 64          # keys per LDS tile of tise_attention_long_f16 (= tise_attention_long_key_tile(), csrc/clip_ops.hip)
+ATTN_SHORT_MAX_SEQ = 96          # tise_attention_f16 keeps a (sequence, head)'s scores in registers up to here
+
+
 def attention(qkv, batch, seq, heads, causal):
-    """qkv (batch*seq, 3*heads*64) fp16 contiguous -> (batch*seq, heads*64)."""
+    """qkv (batch*seq, 3*heads*64) fp16 contiguous -> (batch*seq, heads*64).  seq <= 96: tise_attention_f16 (one wave per
+    (sequence, head)); longer sequences: tise_attention_long_f16 (streamed keys, online softmax), non-causal only."""
+    if seq > ATTN_SHORT_MAX_SEQ:
+        if causal:
+            raise ValueError(f"causal attention runs up to {ATTN_SHORT_MAX_SEQ} tokens (got {seq}): the long-sequence kernel has no mask")
+        return attention_long(qkv, batch, seq, heads)
     assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.shape == (batch * seq, 3 * heads * 64)
     out = torch.empty((batch * seq, heads * 64), dtype=torch.float16, device=qkv.device)
     _lib.call("tise_attention_f16", _p(qkv), batch, seq, heads, 64, 1 if causal else 0, _p(out), _stream())
+    return out
+
+
+def attention_long(qkv, batch, seq, heads):
+    """attention(..., causal=False) on tise_attention_long_f16 whatever the length (any seq >= 1)."""
+    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.shape == (batch * seq, 3 * heads * 64)
+    out = torch.empty((batch * seq, heads * 64), dtype=torch.float16, device=qkv.device)
+    _lib.call("tise_attention_long_f16", _p(qkv), batch, seq, heads, 64, _p(out), _stream())
     return out
 
 
@@ -88,7 +106,16 @@ class HipTowers:
         v = model.visual
         self.patch = v.conv1.kernel_size[0]
         self.width_v = v.conv1.out_channels
+        self.resolution, self.out_dim = model.resolution, model.out_dim
         self.w_patch = h(v.conv1.weight.flatten(1))                 # (width, 3 * P * P): columns (c, ky, kx)
+        kcols = 3 * self.patch * self.patch
+        # tise_patchify_f16 moves 8 halves (patch % 8 == 0) and tise_gemm_f16 steps K by 64: any other patch size (L/14:
+        # 588 columns) takes tise_patchify_pad_f16 and a weight matrix with zero columns up to the next multiple of 64
+        self.kpad = 0 if (kcols % 64 == 0 and self.patch % 8 == 0) else (kcols + 63) // 64 * 64
+        if self.kpad:
+            w = torch.zeros((self.width_v, self.kpad), dtype=torch.float16, device=dev)
+            w[:, :kcols] = self.w_patch
+            self.w_patch = w
         self.cls, self.pos_v = h(v.class_embedding), h(v.positional_embedding)
         self.ln_pre = (h(v.ln_pre.weight), h(v.ln_pre.bias), v.ln_pre.eps)
         self.ln_post = (h(v.ln_post.weight), h(v.ln_post.bias), v.ln_post.eps)
@@ -104,13 +131,17 @@ class HipTowers:
 
     @torch.no_grad()
     def encode_image(self, image):
-        """(B, 3, 224, 224) preprocessed images -> (B, 512) fp16 (clip model.py VisionTransformer.forward)."""
+        """(B, 3, resolution, resolution) preprocessed images -> (B, out_dim) fp16 (clip model.py VisionTransformer.forward)."""
         x = image.to(self.device, torch.float16).contiguous()
         b, _, r, _ = x.shape
         g = r // self.patch
         npatch = g * g
-        pm = torch.empty((b * npatch, 3 * self.patch * self.patch), dtype=torch.float16, device=self.device)
-        _lib.call("tise_patchify_f16", _p(x), b, r, self.patch, _p(pm), _stream())
+        if self.kpad:
+            pm = torch.empty((b * npatch, self.kpad), dtype=torch.float16, device=self.device)
+            _lib.call("tise_patchify_pad_f16", _p(x), b, r, self.patch, self.kpad, _p(pm), _stream())
+        else:
+            pm = torch.empty((b * npatch, 3 * self.patch * self.patch), dtype=torch.float16, device=self.device)
+            _lib.call("tise_patchify_f16", _p(x), b, r, self.patch, _p(pm), _stream())
         pe = gemm(pm, self.w_patch)                                  # conv1 (no bias)
         seq = npatch + 1
         tok = torch.empty((b * seq, self.width_v), dtype=torch.float16, device=self.device)
@@ -125,7 +156,7 @@ class HipTowers:
 
     @torch.no_grad()
     def encode_text(self, text):
-        """(B, 77) int token ids -> (B, 512) fp16 (clip model.py CLIP.encode_text: features at the end-of-text token =
+        """(B, 77) int token ids -> (B, out_dim) fp16 (clip model.py CLIP.encode_text: features at the end-of-text token =
         the position of the largest id)."""
         text = text.to(self.device)
         b, seq = text.shape

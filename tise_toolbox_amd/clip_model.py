@@ -1,4 +1,4 @@
-"""CLIP ViT-B/32 for RP-COCO / PA: the module (parameters, tokenizers, preprocessing) and its
+"""CLIP ViT-B/32 for RP-COCO / PA and ViT-L/14@336 for CMMD (``CONFIGS``): the module (parameters, tokenizers, preprocessing) and its
 PyTorch-ROCm forward.  The default forward of the CLIs is clip_hip.HipTowers (csrc/clip_ops.hip) built FROM this module.
 
 The reference calls the third-party `clip` package (`clip.load("ViT-B/32")`, text_relevance/RP_coco.py:31,
@@ -27,6 +27,36 @@ CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 CONTEXT_LENGTH = 77
 VOCAB_SIZE = 49408
 SOT, EOT = 49406, 49407
+
+# The published towers (Radford et al. 2021, table 20; the OpenAI package's build_model reads the same numbers off a
+# checkpoint's shapes).  Heads are width // 64 in every published ViT tower.  ViT-B/32 serves RP-COCO, PA, CLIP-FID and the
+# default CMMD; ViT-L/14@336 is the tower of the published CMMD figures (Jayasumana et al. 2024).
+CONFIGS = {
+    "ViT-B/32": dict(resolution=224, patch=32, width=768, layers=12, heads=12, embed_dim=512,
+                     text_width=512, text_layers=12, text_heads=8),
+    "ViT-L/14@336": dict(resolution=336, patch=14, width=1024, layers=24, heads=16, embed_dim=768,
+                         text_width=768, text_layers=12, text_heads=12),
+}
+DEFAULT_ARCH = "ViT-B/32"
+
+
+def get_config(arch=None):
+    """A name of ``CONFIGS`` (None: ViT-B/32) or a configuration dict itself -> the dict."""
+    if arch is None:
+        arch = DEFAULT_ARCH
+    if isinstance(arch, dict):
+        return arch
+    if arch not in CONFIGS:
+        raise ValueError(f"unknown CLIP tower {arch!r}: one of {sorted(CONFIGS)}")
+    return CONFIGS[arch]
+
+
+def config_name(cfg):
+    """The ``CONFIGS`` name of a configuration, or its numbers when it has none (error messages)."""
+    for name, c in CONFIGS.items():
+        if c == cfg:
+            return name
+    return "unnamed(" + ", ".join(f"{k}={v}" for k, v in cfg.items()) + ")"
 
 
 class QuickGELU(nn.Module):
@@ -90,7 +120,7 @@ class VisionTransformer(nn.Module):
         self.proj = nn.Parameter(scale * torch.randn(width, out_dim))
 
     def forward(self, x):
-        x = self.conv1(x).flatten(2).transpose(1, 2)                       # (B, 49, width)
+        x = self.conv1(x).flatten(2).transpose(1, 2)                       # (B, patches, width)
         cls = self.class_embedding.to(x.dtype).expand(x.shape[0], 1, -1)
         x = torch.cat([cls, x], 1) + self.positional_embedding.to(x.dtype)
         x = self.transformer(self.ln_pre(x))
@@ -98,9 +128,19 @@ class VisionTransformer(nn.Module):
 
 
 class CLIP(nn.Module):
-    def __init__(self, embed_dim=512, text_width=512, text_layers=12, text_heads=8):
+    def __init__(self, embed_dim=512, text_width=512, text_layers=12, text_heads=8, config=None):
+        """``config``: a name of ``CONFIGS`` or a configuration dict (then the other arguments are not read); None: ViT-B/32
+        with the text tower of the arguments, as before the configurations existed."""
         super().__init__()
-        self.visual = VisionTransformer(out_dim=embed_dim)
+        if config is not None:
+            cfg = get_config(config)
+            embed_dim, text_width, text_layers, text_heads = cfg["embed_dim"], cfg["text_width"], cfg["text_layers"], cfg["text_heads"]
+            self.visual = VisionTransformer(cfg["resolution"], cfg["patch"], cfg["width"], cfg["layers"], cfg["heads"], embed_dim)
+        else:
+            self.visual = VisionTransformer(out_dim=embed_dim)
+        # what callers preprocess to and allocate for (clip_hip.HipTowers and RP_coco.encode_paths read both)
+        self.resolution = self.visual.conv1.kernel_size[0] * int(round((self.visual.positional_embedding.shape[0] - 1) ** 0.5))
+        self.out_dim = embed_dim
         self.transformer = Transformer(text_width, text_layers, text_heads)
         self.token_embedding = nn.Embedding(VOCAB_SIZE, text_width)
         self.positional_embedding = nn.Parameter(torch.empty(CONTEXT_LENGTH, text_width))
@@ -126,7 +166,9 @@ def seeded_init_(model, seed=0):
 
     normal_(model.token_embedding.weight, 0.02)
     normal_(model.positional_embedding, 0.01)
-    for tower, width, layers in ((model.transformer, 512, 12), (model.visual.transformer, 768, 12)):
+    tw, vw = model.token_embedding.weight.shape[1], model.visual.conv1.out_channels       # B/32: 512 and 768
+    for tower, width, layers in ((model.transformer, tw, len(model.transformer.resblocks)),
+                                 (model.visual.transformer, vw, len(model.visual.transformer.resblocks))):
         proj_std = (width ** -0.5) * ((2 * layers) ** -0.5)
         for blk in tower.resblocks:
             normal_(blk.attn.in_proj_weight, width ** -0.5)
@@ -135,35 +177,59 @@ def seeded_init_(model, seed=0):
             normal_(blk.mlp.c_proj.weight, proj_std)
             for b in (blk.attn.in_proj_bias, blk.attn.out_proj.bias, blk.mlp.c_fc.bias, blk.mlp.c_proj.bias):
                 b.data.zero_()
-    normal_(model.text_projection, 512 ** -0.5)
+    normal_(model.text_projection, tw ** -0.5)
     normal_(model.visual.conv1.weight, 0.02)
-    normal_(model.visual.class_embedding, 768 ** -0.5)
-    normal_(model.visual.positional_embedding, 768 ** -0.5)
-    normal_(model.visual.proj, 768 ** -0.5)
+    normal_(model.visual.class_embedding, vw ** -0.5)
+    normal_(model.visual.positional_embedding, vw ** -0.5)
+    normal_(model.visual.proj, vw ** -0.5)
     return model
 
 
-def build_clip(weights=None, seed=0):
-    model = CLIP()
+def config_from_state_dict(sd):
+    """The configuration an OpenAI-format ``state_dict`` was built with, read off its tensor SHAPES as the OpenAI package's
+    ``build_model`` does (meta-device tensors are enough).  Heads are not in the shapes: ``width // 64``."""
+    try:
+        conv = sd["visual.conv1.weight"]
+    except KeyError:
+        raise RuntimeError("not a CLIP ViT state_dict: no 'visual.conv1.weight' (the ResNet towers are not supported)") from None
+    width, patch = conv.shape[0], conv.shape[-1]
+    grid = int(round((sd["visual.positional_embedding"].shape[0] - 1) ** 0.5))
+    if grid * grid + 1 != sd["visual.positional_embedding"].shape[0]:
+        raise RuntimeError(f"visual.positional_embedding has {sd['visual.positional_embedding'].shape[0]} rows: not a square grid plus one")
+    blocks = lambda prefix: len({k[len(prefix):].split(".")[0] for k in sd if k.startswith(prefix)})
+    text_width = sd["ln_final.weight"].shape[0]
+    return dict(resolution=grid * patch, patch=patch, width=width, layers=blocks("visual.transformer.resblocks."),
+                heads=width // 64, embed_dim=sd["text_projection"].shape[1], text_width=text_width,
+                text_layers=blocks("transformer.resblocks."), text_heads=text_width // 64)
+
+
+def build_clip(weights=None, seed=0, arch=None):
+    """The module of tower ``arch`` (a name of ``CONFIGS`` or a configuration dict; None: ViT-B/32) with the parameters of the
+    file ``weights`` -- refused when its shapes say another tower -- or, without one, the seeded stand-ins."""
+    cfg = get_config(arch)
+    model = CLIP(config=cfg)
     if weights:
         sd = torch.load(weights, map_location="cpu")
         sd = sd.get("state_dict", sd)
         for k in ("input_resolution", "context_length", "vocab_size"):
             sd.pop(k, None)
+        found = config_from_state_dict(sd)
+        if found != cfg:
+            raise RuntimeError(f"{weights}: parameters of {config_name(found)}, but the tower asked for is {config_name(cfg)}")
         model.load_state_dict(sd, strict=True)
     else:
         seeded_init_(model, seed)
     return model.eval()
 
 
-def preprocess(img):
-    """clip._transform: Resize(224, bicubic) -> CenterCrop(224) -> RGB -> ToTensor -> Normalize.  PIL on the host
-    (as the reference), returns a (3, 224, 224) fp32 tensor."""
+def preprocess(img, size=224):
+    """clip._transform: Resize(size, bicubic) -> CenterCrop(size) -> RGB -> ToTensor -> Normalize (size = the tower's input
+    resolution: 224, or 336 for ViT-L/14@336).  PIL on the host (as the reference), returns a (3, size, size) fp32 tensor."""
     from PIL import Image
     w, h = img.size
-    nh, nw, top, left = preprocess_geometry(h, w)
+    nh, nw, top, left = preprocess_geometry(h, w, size)
     img = img.resize((nw, nh), Image.BICUBIC)
-    a = np.asarray(img.crop((left, top, left + 224, top + 224)).convert("RGB"), dtype=np.float32) / 255.0
+    a = np.asarray(img.crop((left, top, left + size, top + size)).convert("RGB"), dtype=np.float32) / 255.0
     a = (a - np.array(CLIP_MEAN, dtype=np.float32)) / np.array(CLIP_STD, dtype=np.float32)
     return torch.from_numpy(a).permute(2, 0, 1).contiguous()
 
@@ -175,29 +241,30 @@ def preprocess_lut():
     return np.ascontiguousarray(np.stack([(a - np.float32(CLIP_MEAN[c])) / np.float32(CLIP_STD[c]) for c in range(3)]).astype(np.float32))
 
 
-def preprocess_geometry(h, w):
+def preprocess_geometry(h, w, size=224):
     """(resized height, resized width, top, left) of clip._transform for an h x w image, with torchvision's own integer
-    rules (third-party; clip/clip.py _transform -> torchvision.transforms.Resize(224) + CenterCrop(224)): the shorter side
-    becomes 224 and the longer one ``int(224 * long / short)`` -- TRUNCATED, not rounded (640 x 480 -> 298, not 299) --
-    and the crop starts at ``int(round((n - 224) / 2.0))`` (Python's round: halves go to the even integer).  Square
-    images -- the toolbox's 256 x 256 -- are unaffected; ADVICE r5 caught the one-pixel difference on other shapes."""
+    rules (third-party; clip/clip.py _transform -> torchvision.transforms.Resize(size) + CenterCrop(size), size 224 unless
+    the tower says otherwise): the shorter side becomes ``size`` and the longer one ``int(size * long / short)`` -- TRUNCATED,
+    not rounded (640 x 480 -> 298, not 299, at 224) -- and the crop starts at ``int(round((n - size) / 2.0))`` (Python's
+    round: halves go to the even integer).  Square images -- the toolbox's 256 x 256 -- are unaffected; ADVICE r5 caught the
+    one-pixel difference on other shapes."""
     if w <= h:
-        nw, nh = 224, int(224 * h / w)
+        nw, nh = size, int(size * h / w)
     else:
-        nw, nh = int(224 * w / h), 224
-    return nh, nw, int(round((nh - 224) / 2.0)), int(round((nw - 224) / 2.0))
+        nw, nh = int(size * w / h), size
+    return nh, nw, int(round((nh - size) / 2.0)), int(round((nw - size) / 2.0))
 
 
-def preprocess_device(batch_u8):
+def preprocess_device(batch_u8, size=224):
     """preprocess() for a (N, H, W, 3) uint8 CUDA batch of equally sized RGB images, on the device: Pillow-exact BICUBIC
     8-bit resample (csrc/resize.hip, tise_resize_u8), the crop as a slice, ToTensor + Normalize through preprocess_lut().
-    Returns (N, 3, 224, 224) fp32 -- the values of torch.stack([preprocess(img) for img in batch]) bit for bit."""
+    Returns (N, 3, size, size) fp32 -- the values of torch.stack([preprocess(img, size) for img in batch]) bit for bit."""
     from . import device
     n, h, w, _ = batch_u8.shape
-    nh, nw, top, left = preprocess_geometry(h, w)
+    nh, nw, top, left = preprocess_geometry(h, w, size)
     x = device.resize_u8_lut(batch_u8, (nh, nw), preprocess_lut(), filter="bicubic")
-    if (nh, nw) != (224, 224):
-        x = x[:, :, top:top + 224, left:left + 224].contiguous()
+    if (nh, nw) != (size, size):
+        x = x[:, :, top:top + size, left:left + size].contiguous()
     return x
 
 

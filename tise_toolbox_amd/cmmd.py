@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CLIP-space realism metrics on MI355X: CMMD and CLIP-FID on the ViT-B/32 image tower.
+"""CLIP-space realism metrics on MI355X: CMMD and CLIP-FID on the ViT-B/32 or the ViT-L/14@336 image tower.
 
 The reference toolbox measures realism in Inception pool3 space only.  The two metrics current text-to-image work reports beside
 FID live on CLIP image embeddings:
@@ -21,17 +21,28 @@ term lies between 0.98 and 1 and the result is of order 1e-5 .. 1e-2: the publis
 are fp64 and two runs give the same bits.
 
 CLIP-FID (Kynkaanniemi et al. 2022, "The Role of ImageNet Classes in Frechet Inception Distance"; clean-fid's
-``clip_vit_b_32`` mode): the Frechet distance of the UN-normalised embeddings -- ``device.StatsAccumulator(512)`` and
-``engine.frechet_solver(512)``, the FID machinery at another width.
+``clip_vit_b_32`` mode): the Frechet distance of the UN-normalised embeddings -- ``device.StatsAccumulator(dims)`` and
+``engine.frechet_solver(dims)``, the FID machinery at another width (512 or 768).  ``--clip-fid`` works at either tower and its
+result line names the tower; ONLY the ViT-B/32 one is clean-fid's definition.
 
-THE TOWER.  Both run on CLIP ViT-B/32 (clip_hip.HipTowers.encode_image, csrc/clip_ops.hip) and the result lines say so.  For
-CLIP-FID that is clean-fid's definition.  Published CMMD figures use ViT-L/14 at 336 pixels, whose 577-token sequences and patch
-size 14 are beyond tise_attention_f16 (seq <= 96) and tise_patchify_f16 (patch % 8 == 0): a CMMD from here is NOT comparable
-with those figures, only with other ViT-B/32 ones.
+THE TOWER.  ``--tower`` chooses it and the result lines, the feature files' network tag and the default parameter file follow:
 
-PREPROCESSING is clip._transform as clip_model restates it: convert to RGB, bicubic resize of the short side to 224, centre
-crop.  CMMD's own loader crops the centre square BEFORE the resize; the two are identical for square images and differ by a
-rounding of the crop window otherwise.
+    ViT-B/32 (default)   224 px, 50 tokens, 512-d   tag clip-vit-b32       ~/.cache/clip/ViT-B-32.pt
+    ViT-L/14@336         336 px, 577 tokens, 768-d  tag clip-vit-l14-336   ~/.cache/clip/ViT-L-14-336px.pt
+
+Both run on clip_hip.HipTowers.encode_image (csrc/clip_ops.hip).  ViT-L/14@336 is the tower of the published CMMD figures
+(Jayasumana et al. 2024): its 577-token sequences run on tise_attention_long_f16 (streamed keys, online softmax) and its patch
+size 14 on tise_patchify_pad_f16 (588 columns padded to 640).  With the real ViT-L/14@336 parameters a CMMD from here is the
+metric the paper defines -- same tower, same kernel, same bandwidth, same V-statistic -- and so COMPARABLE with published
+figures up to what still differs: the preprocessing below (clip._transform at 336, not the CMMD loader's crop-then-resize),
+the fp16 tower (the published code runs its tower in fp32), and that PARITY of these towers with the real `clip` package is
+UNPINNED: there are no parameter files here, so the towers are tested against this project's own fp32 module on seeded
+parameters only.  A ViT-B/32 CMMD compares with other ViT-B/32 figures only.  A feature file of one tower is refused under
+the other.
+
+PREPROCESSING is clip._transform as clip_model restates it: convert to RGB, bicubic resize of the short side to the tower's
+resolution (224 or 336), centre crop.  CMMD's own loader crops the centre square BEFORE the resize; the two are identical for
+square images and differ by a rounding of the crop window otherwise.
 
 Every image of a directory is used (no drop-last).  Under torchrun the files are sharded as contiguous index ranges, the rows
 gathered in walk order on every rank (dist.all_gather_rows, as the --kid path), and rank 0 prints and writes.
@@ -49,7 +60,20 @@ GAMMA = 1 / (2 * SIGMA ** 2)
 SCALE = 1000.0
 DIMS = 512
 NETWORK = "clip-vit-b32"             # the tag of a feature file (fid_score.check_stats_network)
-TOWER = "ViT-B/32"
+TOWER = "ViT-B/32"                   # the default tower; DIMS and NETWORK above are its width and tag
+
+# per tower of clip_model.CONFIGS: (network tag of its feature files, weights._KINDS entry of its default parameter file)
+_TOWERS = {"ViT-B/32": (NETWORK, "clip"), "ViT-L/14@336": ("clip-vit-l14-336", "clip-l14-336")}
+
+
+def tower_info(tower=TOWER):
+    """-> (feature width, network tag, weights kind | None) of a tower of clip_model.CONFIGS.  A configuration registered at
+    run time gets a tag spelt from its name and no default parameter file."""
+    from . import clip_model
+    dims = clip_model.get_config(tower)["embed_dim"]
+    if tower in _TOWERS:
+        return (dims,) + _TOWERS[tower]
+    return dims, "clip-" + "".join(c if c.isalnum() else "-" for c in tower.lower()).strip("-"), None
 
 
 def cmmd_from_sums(sums, n, m, unbiased=False):
@@ -104,7 +128,7 @@ def cmmd_from_features(f1, f2, unbiased=False, sigma=SIGMA):
 
 @torch.no_grad()
 def embed_image_dir(towers, path, dev, batch, workers=0, feed="ring"):
-    """Un-normalised fp32 (n, 512) embeddings of EVERY image under ``path``, in img_data.get_filenames' walk order, on every
+    """Un-normalised fp32 (n, towers.out_dim) embeddings of EVERY image under ``path``, in img_data.get_filenames' walk order, on every
     rank.  The loop is RP_coco.embed_paths' (feeds.CLIP: the PNG ring + clip_model.preprocess_device, the DataLoader for a
     ragged directory); the fp16 rows of the tower are widened, not normalised."""
     from . import RP_coco
@@ -125,16 +149,18 @@ def clip_statistics(feats):
     return out
 
 
-def save_features_npz(path, feats, mu, sigma):
-    """The feature file of --save-features: ``features`` (fp32, un-normalised, walk order), ``mu``, ``sigma`` and the network tag."""
+def save_features_npz(path, feats, mu, sigma, tower=TOWER):
+    """The feature file of --save-features: ``features`` (fp32, un-normalised, walk order), ``mu``, ``sigma`` and the network tag
+    of ``tower``."""
     from . import fid_score
-    fid_score.save_stats_npz(path, mu, sigma, NETWORK, feats)
+    fid_score.save_stats_npz(path, mu, sigma, tower_info(tower)[1], feats)
 
 
-def load_features_npz(path):
-    """-> (features fp32 (n, 512), mu, sigma) of a file --save-features wrote.  A file of another network (or of none: an
-    Inception {mu, sigma} file) and a file without the rows are refused."""
+def load_features_npz(path, tower=TOWER):
+    """-> (features fp32 (n, dims), mu, sigma) of a file --save-features wrote under the SAME ``tower``.  A file of another
+    network or tower (or of none: an Inception {mu, sigma} file) and a file without the rows are refused."""
     from . import fid_score
+    DIMS, NETWORK, _ = tower_info(tower)
     with np.load(path, allow_pickle=True) as f:
         tag = str(f["network"]) if "network" in f.files else None
         if tag is None:
@@ -149,10 +175,10 @@ def load_features_npz(path):
         return feats, f["mu"][:], f["sigma"][:]
 
 
-def _side(path, towers, dev, batch_size, num_workers, feed, with_stats):
+def _side(path, towers, dev, batch_size, num_workers, feed, with_stats, tower=TOWER):
     """-> (fp32 device rows, mu | None, sigma | None) of a directory or a feature file."""
     if path.endswith(".npz"):
-        feats, mu, sigma = load_features_npz(path)
+        feats, mu, sigma = load_features_npz(path, tower)
         return torch.as_tensor(feats, device=dev), mu, sigma
     feats = embed_image_dir(towers(), path, dev, batch_size, num_workers, feed)
     if feats.shape[0] == 0:
@@ -161,7 +187,9 @@ def _side(path, towers, dev, batch_size, num_workers, feed, with_stats):
     return feats, mu, sigma
 
 
-def _given_paths(paths, batch_size, weights, seed, num_workers, feed, unbiased, clip_fid, save_features, want_cmmd=True):
+def _given_paths(paths, batch_size, weights, seed, num_workers, feed, unbiased, clip_fid, save_features, want_cmmd=True,
+                 tower=TOWER):
+    tower_info(tower)                                                      # an unknown tower: say so before anything is read
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError("Invalid path: %s" % p)
@@ -173,12 +201,12 @@ def _given_paths(paths, batch_size, weights, seed, num_workers, feed, unbiased, 
 
     def towers():                                                          # two feature files need no tower at all
         if not built:
-            built.append(_towers(weights, seed, dev))
+            built.append(_towers(weights, seed, dev, tower))
         return built[0]
-    f1, m1, s1 = _side(paths[0], towers, dev, batch_size, num_workers, feed, clip_fid or bool(save_features))
+    f1, m1, s1 = _side(paths[0], towers, dev, batch_size, num_workers, feed, clip_fid or bool(save_features), tower)
     if save_features and tdist.is_main():
-        save_features_npz(save_features, f1, m1, s1)
-    f2, m2, s2 = _side(paths[1], towers, dev, batch_size, num_workers, feed, clip_fid)
+        save_features_npz(save_features, f1, m1, s1, tower)
+    f2, m2, s2 = _side(paths[1], towers, dev, batch_size, num_workers, feed, clip_fid, tower)
     value = cmmd_from_features(f1, f2, unbiased) if want_cmmd else None
     fid = None
     if clip_fid:
@@ -187,36 +215,38 @@ def _given_paths(paths, batch_size, weights, seed, num_workers, feed, unbiased, 
     return value, fid
 
 
-def _towers(weights, seed, dev):
-    """RP_coco.build_towers; the seeded stand-in parameters (``weights`` None) of any ``seed`` (build_towers serves seed 0)."""
-    from . import RP_coco, clip_hip, clip_model
-    if weights is not None or seed == 0:
-        return RP_coco.build_towers(weights, dev)[0]
-    model = clip_model.build_clip(None, seed).to(dev).half()
-    tdist.broadcast_module_(model)
-    return model if os.environ.get("TISE_CLIP", "hip") == "torch" else clip_hip.HipTowers(model, dev)
+def _towers(weights, seed, dev, tower=TOWER):
+    """RP_coco.build_towers for ``tower``: the file's parameters, or the seeded stand-ins (``weights`` None) of ``seed``."""
+    from . import RP_coco
+    return RP_coco.build_towers(weights, dev, tower, seed)[0]
 
 
 def calculate_cmmd_given_paths(paths, batch_size=50, weights=None, seed=0, num_workers=0, feed="ring", unbiased=False,
-                               save_features=""):
-    """CMMD x 1000 (ViT-B/32) of two paths -- directories or feature files -> Python float.  ``weights=None``: seeded stand-in
+                               save_features="", tower=TOWER):
+    """CMMD x 1000 (on ``tower``: ViT-B/32 or ViT-L/14@336) of two paths -- directories or feature files -> Python float.  ``weights=None``: seeded stand-in
     parameters (the CLI only allows that behind --synthetic-weights).  ``save_features``: the FIRST path's rows (the reference
     set: embedded once, compared with many generated sets) are written there with their mu and sigma."""
-    return _given_paths(paths, batch_size, weights, seed, num_workers, feed, unbiased, False, save_features)[0]
+    return _given_paths(paths, batch_size, weights, seed, num_workers, feed, unbiased, False, save_features, tower=tower)[0]
 
 
-def calculate_clip_fid_given_paths(paths, batch_size=50, weights=None, seed=0, num_workers=0, feed="ring", save_features=""):
-    """CLIP-FID (ViT-B/32; clean-fid's clip_vit_b_32 definition) of two paths -> Python float: the Frechet distance of the
-    un-normalised embeddings' (mu, sigma) from device.StatsAccumulator(512) and engine.frechet_solver(512)."""
-    return _given_paths(paths, batch_size, weights, seed, num_workers, feed, False, True, save_features, want_cmmd=False)[1]
+def calculate_clip_fid_given_paths(paths, batch_size=50, weights=None, seed=0, num_workers=0, feed="ring", save_features="",
+                                   tower=TOWER):
+    """CLIP-FID (on ``tower``; only the ViT-B/32 one is clean-fid's clip_vit_b_32 definition) of two paths -> Python float: the
+    Frechet distance of the un-normalised embeddings' (mu, sigma) from device.StatsAccumulator(dims) and
+    engine.frechet_solver(dims)."""
+    return _given_paths(paths, batch_size, weights, seed, num_workers, feed, False, True, save_features, want_cmmd=False,
+                        tower=tower)[1]
 
 
 def parse_args(argv=None):
-    parser = argparse.ArgumentParser(description="CMMD and CLIP-FID on the CLIP ViT-B/32 image tower")
+    from . import clip_model
+    parser = argparse.ArgumentParser(description="CMMD and CLIP-FID on a CLIP image tower (ViT-B/32, or the paper's ViT-L/14@336)")
+    parser.add_argument("--tower", default=TOWER, choices=list(clip_model.CONFIGS),
+                        help="ViT-B/32 (default; clean-fid's CLIP-FID tower) or ViT-L/14@336 (the tower of the published CMMD figures)")
     parser.add_argument("--path1", type=str, required=True, help="reference images: a directory, or a feature file of --save-features")
     parser.add_argument("--path2", type=str, required=True, help="generated images: a directory, or a feature file of --save-features")
     parser.add_argument("--batch-size", type=int, default=50)
-    parser.add_argument("--weights", default=None, type=str, help="OpenAI CLIP ViT-B/32 state_dict (.pt); default: ~/.cache/clip/ViT-B-32.pt")
+    parser.add_argument("--weights", default=None, type=str, help="OpenAI CLIP state_dict (.pt) of the chosen tower; default: ~/.cache/clip/ViT-B-32.pt or ViT-L-14-336px.pt")
     parser.add_argument("--synthetic-weights", action="store_true",
                         help="seeded stand-in tower (plumbing / throughput only; results are tagged)")
     parser.add_argument("--seed", default=0, type=int, help="seed of the stand-in parameters")
@@ -239,12 +269,12 @@ def main(argv=None):
     rank, world, local_rank = tdist.init_from_env()
     dev = torch.device(f"cuda:{local_rank}" if world > 1 else f"cuda:{args.gpu}")
     torch.cuda.set_device(dev)
-    wpath, tag = tweights.resolve(args.weights, args.synthetic_weights, "clip")
+    wpath, tag = tweights.resolve(args.weights, args.synthetic_weights, tower_info(args.tower)[2], f"CLIP {args.tower}")
     value, fid = _given_paths([args.path1, args.path2], args.batch_size, wpath, args.seed, args.num_workers, args.png_feed,
-                              args.unbiased, args.clip_fid, args.save_features)
-    lines = [f"CMMD ({TOWER}): {value}{tag}"]
+                              args.unbiased, args.clip_fid, args.save_features, tower=args.tower)
+    lines = [f"CMMD ({args.tower}): {value}{tag}"]
     if args.clip_fid:
-        lines.append(f"CLIP-FID ({TOWER}): {fid}{tag}")
+        lines.append(f"CLIP-FID ({args.tower}): {fid}{tag}")
     if tdist.is_main():
         if args.saved_file:
             with open(args.saved_file, "w") as f:

@@ -1,4 +1,4 @@
-// Hand-written kernels of the CLIP ViT-B/32 towers (text_relevance/RP_coco.py:56-80 and
+// Hand-written kernels of the CLIP towers (ViT-B/32; the ViT-L/14@336 image tower of CMMD) (text_relevance/RP_coco.py:56-80 and
 // positional_alignment/PA.py:33-43 call the third-party `clip` model once per item; here the towers run batched).
 // fp16 tensors, fp32 accumulation / statistics, as the fp16 model `clip.load` serves on a GPU computes.
 //
@@ -11,7 +11,11 @@
 //   layernorm_f16_kernel one wave per row, fp32 mean / variance (CLIP's LayerNorm computes in fp32), eps inside sqrt.
 //   attention_f16_kernel one WAVE per (sequence, head): S <= 96 tokens, head dim 64: K Q^T and V^T P^T on the matrix
 //                        cores with operands loaded straight into the MFMA layout, fp32 softmax in registers.
-//   vit_tokens_f16_kernel / text_tokens_f16_kernel / patchify_f16_kernel / gather_rows_f16_kernel: token assembly.
+//   attention_long_f16_kernel  any S (ViT-L/14@336: 577 tokens), non-causal: 4 waves x 32 queries of one (sequence, head)
+//                        share each 64-key K / V tile in LDS; the same two products, online softmax with the exact running
+//                        maximum.
+//   vit_tokens_f16_kernel / text_tokens_f16_kernel / patchify_f16_kernel / patchify_pad_f16_kernel (any patch size, rows
+//   padded with zeros to the GEMM's K-step) / gather_rows_f16_kernel: token assembly.
 #include <hip/hip_fp16.h>
 #include <cstdlib>
 #include "common.h"
@@ -20,6 +24,7 @@ namespace {
 
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 typedef float float16_t __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
@@ -679,6 +684,164 @@ __global__ __launch_bounds__(256) void attention_f16_kernel(const _Float16* __re
     }
 }
 
+// Long sequences (the image tower of ViT-L/14@336: 577 tokens): the same two products as attention_f16_kernel -- S^T = K Q^T
+// with one query per lane, P fed from the accumulator registers as the B operand of O^T = V^T P^T with the K index permuted
+// alike on both operands -- but the keys STREAM in tiles of ATTN_LONG_KT under an online softmax, so no register holds more
+// than one tile of scores and the key loop has no length limit.
+//   workgroup = 4 waves = 4 x 32 consecutive queries of ONE (sequence, head); grid = ceil(S / 128) x batch * heads;
+//   a K / V tile is staged ONCE per workgroup in LDS and read by all four waves (a quarter of the global traffic of one
+//   wave per head): K as [key][64 d] rows of 128 bytes with the GEMM kernels' chunk swizzle, V transposed on the way in
+//   ([d][key], two keys packed per 4-byte write).  Two LDS stages: tile t + 1 is fetched into registers before tile t's
+//   MFMAs and written after them, ONE barrier per tile.
+//   online softmax with the exact running maximum: m' = max(m, tile max), alpha = exp(m - m'), O *= alpha, l = l alpha +
+//   sum p, p = exp(s - m') <= 1 BEFORE its fp16 rounding; the tile's P is exponentiated after m' is known, O and l are
+//   scaled once per tile.  l is kept as this lane's partial sum (alpha is common to lane and lane ^ 32) and the halves are
+//   added once at the end.  Tile 0 holds key 0, so m is finite from the first tile on (alpha = exp(-inf) = 0 there, on
+//   O = l = 0).
+//   padded keys j >= S: score -inf before the maximum, K and V rows written to LDS as ZEROS (p = 0 times stale bits that
+//   read as NaN would be NaN).  Padding queries i >= S compute on q = 0 and store nothing.  EVERY wave -- also one whose 32
+//   queries all lie beyond S -- runs every staging step and every barrier: there is no early return and no break.
+#define ATTN_LONG_KT 64
+__global__ __launch_bounds__(256) void attention_long_f16_kernel(const _Float16* __restrict__ qkv, int S, int H, int QB,
+                                                                 _Float16* __restrict__ out) {
+    constexpr int KT = ATTN_LONG_KT, NJ = KT / 32;
+    constexpr int VP = KT + 4;                                  // V^T pitch in halves: 8-byte aligned rows, 34 banks apart
+    constexpr int K_BYTES = KT * 128, V_BYTES = 64 * VP * 2, STAGE = K_BYTES + V_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int qb = (int)(blockIdx.x % (unsigned)QB), bh = (int)(blockIdx.x / (unsigned)QB);
+    const int b = bh / H, h = bh - b * H;
+    const int E = H * 64;
+    const long long ld = 3LL * E;
+    const _Float16* qbase = qkv + (long long)b * S * ld + h * 64;
+    const _Float16* kb = qbase + E;
+    const _Float16* vb = qbase + 2 * E;
+    const int r = lane & 31, hh = lane >> 5;
+    const int i = qb * 128 + wave * 32 + r;                    // this lane's query
+    const half8_t z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    half8_t qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = i < S ? *reinterpret_cast<const half8_t*>(qbase + (long long)i * ld + 16 * ks + 8 * hh) : z8;
+    // staging: thread -> 16-byte chunk sc of K rows sr, sr + 32 and of V rows 2 vp, 2 vp + 1
+    const int sc = tid & 7, sr = tid >> 3, vp = tid >> 3;
+    half8_t gk[2], gv[2];
+#define AL_FETCH(J0)                                                                                       \
+    {                                                                                                     \
+        _Pragma("unroll") for (int n = 0; n < 2; ++n) {                                                    \
+            const int jk = (J0) + sr + 32 * n, jv = (J0) + 2 * vp + n;                                     \
+            gk[n] = jk < S ? *reinterpret_cast<const half8_t*>(kb + (long long)jk * ld + 8 * sc) : z8;      \
+            gv[n] = jv < S ? *reinterpret_cast<const half8_t*>(vb + (long long)jv * ld + 8 * sc) : z8;      \
+        }                                                                                                  \
+    }
+#define AL_WRITE(SOFF)                                                                                     \
+    {                                                                                                     \
+        _Pragma("unroll") for (int n = 0; n < 2; ++n) {                                                    \
+            const int row = sr + 32 * n;                                                                   \
+            *reinterpret_cast<half8_t*>(lds + (SOFF) + row * 128 + ((sc ^ ((row >> 1) & 7)) << 4)) = gk[n]; \
+        }                                                                                                  \
+        _Float16* vt_ = reinterpret_cast<_Float16*>(lds + (SOFF) + K_BYTES);                               \
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                    \
+            half2_t pr = {gv[0][e], gv[1][e]};                                                             \
+            *reinterpret_cast<half2_t*>(vt_ + (8 * sc + e) * VP + 2 * vp) = pr;                             \
+        }                                                                                                  \
+    }
+    float16_t oc[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) oc[dt][e] = 0.f;
+    float m = -INFINITY, l = 0.f;
+    const int T = (S + KT - 1) / KT;                            // the same for every wave of the workgroup
+    AL_FETCH(0)
+    AL_WRITE(0)
+    __syncthreads();
+    const int ksw = (r >> 1) & 7;
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {
+        const int soff = (t & 1) * STAGE;
+        const int j0 = t * KT;
+        if (t + 1 < T) AL_FETCH(j0 + KT)                       // uniform over the workgroup
+        const unsigned char* kl = lds + soff;
+        const _Float16* vt = reinterpret_cast<const _Float16*>(lds + soff + K_BYTES);
+        float16_t s[NJ];
+#pragma unroll
+        for (int jt = 0; jt < NJ; ++jt) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) s[jt][e] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const half8_t kf = *reinterpret_cast<const half8_t*>(kl + (32 * jt + r) * 128 + (((2 * ks + hh) ^ ksw) << 4));
+                s[jt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[jt], 0, 0, 0);
+            }
+        }
+        // scale, mask the padded keys, tile maximum of query i (this lane's registers and lane ^ 32's)
+        float tm = -INFINITY;
+#pragma unroll
+        for (int jt = 0; jt < NJ; ++jt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int j = j0 + 32 * jt + 8 * (e >> 2) + 4 * hh + (e & 3);
+                const float v = j < S ? s[jt][e] * 0.125f : -INFINITY;
+                s[jt][e] = v;
+                tm = fmaxf(tm, v);
+            }
+        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+        const float mn = fmaxf(m, tm);                         // finite: tile 0 holds key 0
+        const float alpha = __expf(m - mn);                    // tile 0: exp(-inf) = 0 on O = l = 0
+        m = mn;
+        float psum = 0.f;
+#pragma unroll
+        for (int jt = 0; jt < NJ; ++jt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const float pe = __expf(s[jt][e] - mn);        // exp(-inf) = 0 for the padded keys
+                s[jt][e] = pe;
+                psum += pe;
+            }
+        l = l * alpha + psum;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) oc[dt][e] *= alpha;
+#pragma unroll
+        for (int jt = 0; jt < NJ; ++jt)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                half8_t pf;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) pf[e] = (_Float16)s[jt][8 * q + e];
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt) {
+                    const _Float16* vr = vt + (32 * dt + r) * VP + 32 * jt + 16 * q + 4 * hh;
+                    const half4_t lo4 = *reinterpret_cast<const half4_t*>(vr);
+                    const half4_t hi4 = *reinterpret_cast<const half4_t*>(vr + 8);
+                    half8_t vf;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { vf[e] = lo4[e]; vf[4 + e] = hi4[e]; }
+                    oc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oc[dt], 0, 0, 0);
+                }
+            }
+        if (t + 1 < T) AL_WRITE(STAGE - soff)                  // the stage tile t - 1 was read from: every wave passed the barrier since
+        __syncthreads();
+    }
+#undef AL_FETCH
+#undef AL_WRITE
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;                                 // l >= 1: the key of the maximum contributes exp(0)
+    if (i < S) {
+        _Float16* orow = out + ((long long)b * S + i) * E + h * 64;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                half4_t o4;
+#pragma unroll
+                for (int k2 = 0; k2 < 4; ++k2) o4[k2] = (_Float16)(oc[dt][4 * g + k2] * inv);
+                *reinterpret_cast<half4_t*>(orow + 32 * dt + 8 * g + 4 * hh) = o4;
+            }
+    }
+}
+
 // image (B, 3, R, R) fp16 NCHW -> patch matrix [B * (R/P)^2][3 * P * P], column = c * P*P + ky * P + kx (= the
 // flattening of conv1.weight (width, 3, P, P)), so that the patch embedding is one GEMM
 __global__ __launch_bounds__(256) void patchify_f16_kernel(const _Float16* __restrict__ img, int B, int R, int P,
@@ -693,6 +856,25 @@ __global__ __launch_bounds__(256) void patchify_f16_kernel(const _Float16* __res
         const int b = (int)(row / (G * G)), gy = (int)(row / G % G), gx = (int)(row % G);
         const _Float16* src = img + (((long long)b * 3 + c) * R + gy * P + ky) * R + gx * P + kx;
         *reinterpret_cast<half8_t*>(out + el) = *reinterpret_cast<const half8_t*>(src);
+    }
+}
+
+// the same patch matrix for ANY patch size, rows padded to KP >= 3 P^2 columns (KP % 64 == 0: tise_gemm_f16's K-step): one
+// output element per thread, 2-byte reads, stores consecutive along the output row; columns 3 P^2 .. KP - 1 are written as +0
+__global__ __launch_bounds__(256) void patchify_pad_f16_kernel(const _Float16* __restrict__ img, int B, int R, int P, int KP,
+                                                               _Float16* __restrict__ out) {
+    const int G = R / P, K = 3 * P * P;
+    const long long total = (long long)B * G * G * KP;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int col = (int)(e % KP);
+        const long long row = e / KP;
+        _Float16 v = (_Float16)0.f;
+        if (col < K) {
+            const int c = col / (P * P), ky = (col / P) % P, kx = col % P;
+            const int b = (int)(row / (G * G)), gy = (int)(row / G % G), gx = (int)(row % G);
+            v = img[(((long long)b * 3 + c) * R + gy * P + ky) * R + gx * P + kx];
+        }
+        out[e] = v;
     }
 }
 
@@ -837,6 +1019,22 @@ int tise_attention_f16(const void* qkv_dev, int batch, int seq, int heads, int h
     return TISE_OK;
 }
 
+int tise_attention_long_key_tile(void) { return ATTN_LONG_KT; }
+
+int tise_attention_long_f16(const void* qkv_dev, int batch, int seq, int heads, int head_dim, void* out_dev, void* stream) {
+    if (!qkv_dev || !out_dev || batch < 0 || seq <= 0 || heads <= 0 || head_dim != 64 ||
+        ((reinterpret_cast<uintptr_t>(qkv_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15) != 0)    // 16-byte q / k / v loads
+        return TISE_ERR_INVALID_ARG;
+    if (batch == 0) return TISE_OK;
+    const long long qblocks = ((long long)seq + 127) / 128;
+    const long long bh = (long long)batch * heads;
+    if (qblocks * bh > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(attention_long_f16_kernel, dim3((unsigned)(qblocks * bh)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const _Float16*>(qkv_dev), seq, heads, (int)qblocks, reinterpret_cast<_Float16*>(out_dev));
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
 int tise_patchify_f16(const void* img_dev, int batch, int res, int patch, void* out_dev, void* stream) {
     if (!img_dev || !out_dev || batch < 0 || res <= 0 || patch <= 0 || res % patch != 0 || patch % 8 != 0 ||
         ((reinterpret_cast<uintptr_t>(img_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15) != 0)    // 16-byte loads / stores
@@ -845,6 +1043,18 @@ int tise_patchify_f16(const void* img_dev, int batch, int res, int patch, void* 
     const long long total = (long long)batch * (res / patch) * (res / patch) * 3 * patch * patch / 8;
     hipLaunchKernelGGL(patchify_f16_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const _Float16*>(img_dev), batch, res, patch, reinterpret_cast<_Float16*>(out_dev));
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+int tise_patchify_pad_f16(const void* img_dev, int batch, int res, int patch, int kpad, void* out_dev, void* stream) {
+    if (!img_dev || !out_dev || batch < 0 || res <= 0 || patch <= 0 || res % patch != 0 || kpad <= 0 || kpad % 64 != 0 ||
+        3LL * patch * patch > kpad || (reinterpret_cast<uintptr_t>(img_dev) & 1) != 0 || (reinterpret_cast<uintptr_t>(out_dev) & 15) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (batch == 0) return TISE_OK;
+    const long long total = (long long)batch * (res / patch) * (res / patch) * kpad;
+    hipLaunchKernelGGL(patchify_pad_f16_kernel, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const _Float16*>(img_dev), batch, res, patch, kpad, reinterpret_cast<_Float16*>(out_dev));
     TISE_LAUNCH_CHECK();
     return TISE_OK;
 }

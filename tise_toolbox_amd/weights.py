@@ -33,6 +33,8 @@ _KINDS = {
     "slim": ("TF-slim InceptionV3 fine-tuned on CUB birds (TensorFlow checkpoint birds_valid299/model.ckpt)",
              lambda: [os.path.join("IS", "bird", "inception_finetuned_models", "birds_valid299", "model.ckpt")]),
     "clip": ("CLIP ViT-B/32", lambda: [os.path.expanduser(os.path.join("~", ".cache", "clip", "ViT-B-32.pt"))]),
+    # the tower of the published CMMD figures (cmmd --tower ViT-L/14@336), under the name the OpenAI package caches it
+    "clip-l14-336": ("CLIP ViT-L/14@336", lambda: [os.path.expanduser(os.path.join("~", ".cache", "clip", "ViT-L-14-336px.pt"))]),
 }
 
 
@@ -59,9 +61,13 @@ def _exists(path, kind):
     return os.path.exists(path) or (kind == "slim" and os.path.exists(path + ".index"))
 
 
-def resolve(weights, synthetic, kind):
-    """-> (path or None, tag).  ``None`` means seeded stand-in parameters (only with ``synthetic``)."""
-    what, defaults = _KINDS[kind]
+def resolve(weights, synthetic, kind, what=None):
+    """-> (path or None, tag).  ``None`` means seeded stand-in parameters (only with ``synthetic``).  ``kind`` None: a
+    network without a default file (``what`` names it), so ``--weights`` or ``--synthetic-weights`` it has to be."""
+    if kind is None:
+        defaults = lambda: []
+    else:
+        what, defaults = _KINDS[kind][0] if what is None else what, _KINDS[kind][1]
     if synthetic:
         # an explicit request always wins: a seeded plumbing / throughput run must not pick up a file that happens to
         # sit in ~/.cache or the working directory on one machine and not on another
@@ -77,6 +83,9 @@ def resolve(weights, synthetic, kind):
         if _exists(p, kind):
             print(f"[tise] {what}: parameters from {p}", file=sys.stderr, flush=True)
             return p, ""
+    if kind is None:
+        raise RuntimeError(f"no parameters for {what}, which has no default file: pass --weights PATH, or --synthetic-weights "
+                           f"for a plumbing/throughput run with seeded stand-ins")
     raise RuntimeError(
         f"no parameters for {what}: the reference downloads them, this machine cannot.  Pass --weights PATH, put the "
         f"file at {defaults()[0]!r}, or pass --synthetic-weights for a plumbing/throughput run with seeded stand-ins")
