@@ -157,6 +157,32 @@ int tise_resize_ragged_u8(const uint8_t* const* src_ptrs_host, const int32_t* h_
                           uint8_t* table_host_pinned, int64_t* bad_index, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (a3f) Pillow-exact FLOAT32 resize + clip + input affine, fused: clean-fid's resize (csrc/resize_f32.hip).
+ * Every channel of the uint8 image is resampled as Pillow resamples a mode "F" image -- double coefficients (Resample.c
+ * precompute_coeffs, no 22-bit rounding), per output `double ss = 0; ss += (double)pixel * k[x]` in ascending x with a
+ * separate multiply and add, the result of each pass rounded to float32, a pass whose size does not change skipped -- and is
+ * NOT quantised; then min(max(v, clip_lo), clip_hi) and (v - sub) / div, two fp32 operations in that order.
+ *
+ *   src_dev   n images, HWC uint8, contiguous (n, h, w, 3), any alignment
+ *   dst_dev   fp32, (n, 3, oh, ow) when nhwc == 0, (n, oh, ow, 3) when nhwc != 0
+ *   filter    0 = BILINEAR, 1 = BICUBIC
+ *   order     0: horizontal pass first (Pillow's ImagingResample); 1: vertical pass first (what Image.resize does for a
+ *             source more than 100 times taller than wide whose height shrinks: the caller applies that rule)
+ * clip_lo > clip_hi, a non-finite sub or div, div == 0: TISE_ERR_INVALID_ARG.  A size of which no row tile fits LDS, n > 65535:
+ * TISE_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+int tise_resize_f32(const uint8_t* src_dev, int n, int h, int w, float* dst_dev, int oh, int ow, int nhwc, int filter,
+                    float clip_lo, float clip_hi, float sub, float div, int order, void* stream);
+
+/* The same for n images of DIFFERENT sizes into one fp32 batch ((n, oh, ow, 3) when nhwc != 0, (n, 3, oh, ow) otherwise), one
+ * launch per 4096 images: image by image exactly the bits tise_resize_f32 writes.  Arguments, workspace size, pinned table and
+ * refusals as tise_resize_ragged_u8; order_host: per image, 0 or 1 as above. */
+int tise_resize_ragged_f32(const uint8_t* const* src_ptrs_host, const int32_t* h_host, const int32_t* w_host,
+                           const int32_t* order_host, int64_t n, float* dst_dev, int oh, int ow, int nhwc, int filter,
+                           float clip_lo, float clip_hi, float sub, float div, uint8_t* ws_dev, int64_t ws_bytes,
+                           uint8_t* table_host_pinned, int64_t* bad_index, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a7) Streaming activation statistics: n, s = sum_i x_i, S = sum_i x_i x_i^T in fp64 from
  * fp32 feature rows that never leave the device.
  * Replaces pred_arr[start:end] = pred.cpu()...  + np.mean(act, 0) + np.cov(act, rowvar=False)

@@ -294,6 +294,78 @@ def resize_ragged_u8(crops, out_hw=(299, 299), out=None, filter="bilinear"):
     return out
 
 
+def _f32_out(n, oh, ow, channels_last, dev):
+    if channels_last:
+        store = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=dev)
+        return store, store.permute(0, 3, 1, 2)
+    store = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=dev)
+    return store, store
+
+
+def resize_f32(src_u8, out_hw=(299, 299), filter="bicubic", clip=(0, 255), sub=128, div=128, channels_last=True):
+    """(N,H,W,3) uint8 CUDA tensor -> (N,3,oh,ow) fp32 network input of clean-fid's route (tise_resize_f32): every channel
+    resampled as Pillow resamples a float32 (mode "F") image, NOT quantised, clipped to ``clip`` and mapped ``(x - sub) / div``
+    in fp32.  Pillow's vertical-first rule (pillow_vertical_first) is applied here: the kernel takes the order as an argument.
+    With ``channels_last`` the result is an NCHW tensor in torch.channels_last memory format (what the trunk's stem reads)."""
+    _require_cuda(src_u8)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3:
+        raise ValueError("src_u8 must be (N,H,W,3) uint8")
+    oh, ow = out_hw
+    src_u8 = src_u8.contiguous()
+    n, h, w, _ = src_u8.shape
+    store, out = _f32_out(n, oh, ow, channels_last, src_u8.device)
+    _lib.call("tise_resize_f32", _ptr(src_u8), n, h, w, _ptr(store), oh, ow, 1 if channels_last else 0, _FILTERS[filter],
+              float(clip[0]), float(clip[1]), float(sub), float(div), 1 if pillow_vertical_first(h, w, oh) else 0, _stream())
+    return out
+
+
+def resize_ragged_f32(crops, out_hw=(299, 299), filter="bicubic", clip=(0, 255), sub=128, div=128, channels_last=True):
+    """List of (H_i,W_i,3) uint8 CUDA tensors of any sizes -> the (B,3,oh,ow) fp32 batch ``resize_f32`` gives image by image, bit
+    for bit, in ONE launch (tise_resize_ragged_f32); Pillow's vertical-first rule is applied per image.  A size the plan builder
+    refuses raises before anything of the batch is enqueued, naming the image."""
+    if len(crops) == 0:
+        raise ValueError("empty batch")
+    oh, ow = out_hw
+    dev = crops[0].device
+    srcs = []
+    for i, c in enumerate(crops):
+        _require_cuda(c)
+        if c.dim() == 4 and c.shape[0] == 1:
+            c = c[0]
+        if c.dtype != torch.uint8 or c.dim() != 3 or c.shape[2] != 3:
+            raise ValueError(f"crop {i} must be (H,W,3) uint8")
+        srcs.append(c.contiguous())
+    n = len(srcs)
+    store, out = _f32_out(n, oh, ow, channels_last, dev)
+    ptrs = np.fromiter((c.data_ptr() for c in srcs), dtype=np.uint64, count=n)
+    hs = np.fromiter((c.shape[0] for c in srcs), dtype=np.int32, count=n)
+    ws = np.fromiter((c.shape[1] for c in srcs), dtype=np.int32, count=n)
+    orders = np.fromiter((1 if pillow_vertical_first(c.shape[0], c.shape[1], oh) else 0 for c in srcs), dtype=np.int32, count=n)
+    need = n * (64 + 4 * oh) + 16 * (n // 4096 + 1)
+    ws_dev = torch.empty(need, dtype=torch.uint8, device=dev)
+    # the pinned table ring of resize_ragged_u8: built in page-locked memory, copied asynchronously, two buffers in turn
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    ring = _RAGGED_TABLES.setdefault(key, [[None, None], [None, None]])
+    slot = ring.pop(0)
+    ring.append(slot)
+    if slot[1] is not None:
+        slot[1].synchronize()
+    if slot[0] is None or slot[0].numel() < need:
+        slot[0] = torch.empty(max(need, 1 << 16), dtype=torch.uint8).pin_memory()
+    bad = ctypes.c_int64(-1)
+    st = _lib.load().tise_resize_ragged_f32(ptrs.ctypes.data, hs.ctypes.data, ws.ctypes.data, orders.ctypes.data, n, _ptr(store), oh, ow,
+                                            1 if channels_last else 0, _FILTERS[filter], float(clip[0]), float(clip[1]), float(sub),
+                                            float(div), _ptr(ws_dev), need, slot[0].data_ptr(), ctypes.byref(bad), _stream())
+    if st != _lib.TISE_OK:
+        if bad.value >= 0:
+            raise _lib.TiseStatusError(f"tise_resize_ragged_f32 (image {bad.value} of the batch, {int(hs[bad.value])} x {int(ws[bad.value])})",
+                                       st, _lib.load().tise_status_string(st).decode())
+        _lib.check("tise_resize_ragged_f32", st)
+    slot[1] = torch.cuda.Event()
+    slot[1].record(torch.cuda.current_stream(dev))
+    return out
+
+
 def read_split_overflow():
     """Read-and-clear the range guard of the split-fp16 activation format (csrc/common.h): True when any kernel
     since the last read converted a value above the fp16 range (65504) into a split tensor.  A NaN raises it only in

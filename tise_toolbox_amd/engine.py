@@ -62,13 +62,25 @@ def run_with_exact_fallback(fn, what="the evaluation"):
         return fn()
 
 
+RESIZES = ("reference", "clean")
+
+
 class RealismEngine:
     def __init__(self, dims=2048, device_index=None, weights=None, num_classes=None, seed=0,
                  channels_last=None, fold_bn=True, with_logits=False, model=None, normalize_input=True,
-                 lut=None, fused=None, fc_bias="auto", network="torchvision"):
+                 lut=None, fused=None, fc_bias="auto", network="torchvision", resize="reference"):
         """``network``: inception.NETWORKS -- "inception-2015" builds the TensorFlow Inception-2015 graph's variant of the
-        model (its pools, 1008-class head unless ``num_classes`` says otherwise) and its input table (device.make_lut)."""
+        model (its pools, 1008-class head unless ``num_classes`` says otherwise) and its input table (device.make_lut).
+        ``resize``: "reference" -- Pillow's 8-bit bilinear resize, the reference's (csrc/resize.hip); "clean" -- clean-fid's:
+        every channel resized as a float32 image with Pillow's bicubic filter, not quantised, clipped to [0, 255] and mapped
+        (x - 128) / 128 (csrc/resize_f32.hip), for the Inception-2015 network only (whose input map that is)."""
         require_gpu()
+        if resize not in RESIZES:
+            raise ValueError(f"unknown resize {resize!r} (choose from {', '.join(RESIZES)})")
+        net = getattr(model, "network", "torchvision") if model is not None else network
+        if resize == "clean" and net != "inception-2015":
+            raise ValueError(f"resize='clean' is clean-fid's route and runs on network 'inception-2015' only (got {net!r})")
+        self.resize = resize
         if device_index is None:
             device_index = torch.cuda.current_device()
         self.device = torch.device("cuda", device_index)
@@ -127,7 +139,15 @@ class RealismEngine:
         self._graphs = {}
 
     # ---- per-batch device work -----------------------------------------------------------------
+    def _clean_input(self, u8, ragged=False):
+        """The float route's network input: (N,3,299,299) fp32, channels_last as the engine's trunk reads it."""
+        from .inception import INCEPTION_2015_INPUT_DIV, INCEPTION_2015_INPUT_SUB
+        fn = device.resize_ragged_f32 if ragged else device.resize_f32
+        return fn(u8, (299, 299), "bicubic", (0, 255), INCEPTION_2015_INPUT_SUB, INCEPTION_2015_INPUT_DIV, channels_last=self.channels_last)
+
     def _features_from_u8_eager(self, batch_u8):
+        if self.resize == "clean":
+            return self._trunk(self._clean_input(batch_u8), prenormalized=True)
         if self._u8_stem:
             # all-HIP trunk: the resize kernel writes the Pillow-exact uint8 image only and the stem convolution
             # applies the input table (134 MB instead of 536 MB of network input per 500 images; same features)
@@ -157,7 +177,8 @@ class RealismEngine:
             return self._features_from_u8_eager(batch_u8)
         # the captured launches bake in the classifier-bias decision and whether logits are formed at all (begin(rule=...) flips
         # fc_bias: coco no bias, bird / ois bias): both are part of the key, or a coco graph would be replayed for an ois pass
-        key = tuple(batch_u8.shape) + (bool(self.fc_bias), bool(self.with_logits))
+        # ... and so is the resize kind (one engine has one, but the key says what the captured launches are)
+        key = tuple(batch_u8.shape) + (bool(self.fc_bias), bool(self.with_logits), self.resize)
         entry = self._graphs.get(key)
         if entry is None:
             # the first two batches of a shape run eagerly (library caches: resize plans, lookup table, hipBLASLt
@@ -193,7 +214,10 @@ class RealismEngine:
         a launch per crop) and the trunk runs ONCE on the batch."""
         if len(crops) == 0:
             raise ValueError("empty batch")
-        u8 = device.resize_ragged_u8([(c[0] if c.dim() == 4 else c).to(self.device, non_blocking=True) for c in crops], (299, 299))
+        crops = [(c[0] if c.dim() == 4 else c).to(self.device, non_blocking=True) for c in crops]
+        if self.resize == "clean":
+            return self._trunk(self._clean_input(crops, ragged=True), prenormalized=True)
+        u8 = device.resize_ragged_u8(crops, (299, 299))
         if self._u8_stem:
             return self._trunk_u8(u8)
         lut = self.lut_dev.view(3, 256)
@@ -228,6 +252,8 @@ class RealismEngine:
     # ---- memory -----------------------------------------------------------------------------------
     ACT_BYTES_PER_IMAGE = int(14.5 * 2**20)     # peak of a trunk pass per 256 x 256 image (tools/activation_memory_probe.py: 14.4 MiB at 250-1000, 13.5 at 3000)
 
+    CLEAN_INPUT_BYTES_PER_IMAGE = 299 * 299 * 3 * 4   # the float route's fp32 network input (1.07 MB; the uint8 stem reads 0.27 MB of bytes)
+
     def reserve_activations(self, images):
         """ONE allocation of the trunk's peak footprint for a pass of ``images`` images, released at once into torch's caching
         allocator -- the passes then split that block instead of asking the driver again and again.
@@ -243,7 +269,7 @@ class RealismEngine:
         images = int(images)
         if images <= getattr(self, "_reserved_images", 0) or not isinstance(self.fused, SplitTrunk) or os.environ.get("TISE_RESERVE", "1") == "0":
             return 0
-        nbytes = images * self.ACT_BYTES_PER_IMAGE
+        nbytes = images * (self.ACT_BYTES_PER_IMAGE + (self.CLEAN_INPUT_BYTES_PER_IMAGE if self.resize == "clean" else 0))
         free, _total = torch.cuda.mem_get_info(self.device)
         have = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)      # cached, free blocks
         if nbytes <= have or nbytes > 0.6 * free:

@@ -37,6 +37,7 @@ class Options:
 # under torchrun a rank that meets a ragged directory raises -- its consume holds collectives (False: RP / PA embed per rank).
 Site = namedtuple("Site", "kinds drop_last crop_on_request ring_when_empty png_line ragged_raises", defaults=(False, False, False, True))
 FID = Site(("jpeg", "crop", "ring", "dataloader"), True, crop_on_request=True, ring_when_empty=True, png_line=True)
+FID_ALL = FID._replace(drop_last=False)                           # fid_score --mode clean: the FID site, every image used
 CROPS = Site(("crop", "dataloader"), False)                       # fid_score --per-class, O-IS
 IS = Site(("jpeg", "ring", "dataloader"), False)
 CLIP = Site(("ring", "dataloader"), False, ragged_raises=False)   # RP_coco, PA

@@ -23,7 +23,8 @@ Deviations from the reference, all deliberate (SURVEY.md notes N3-N5):
     Frechet distance is solved), ``--label`` ("FID" | "O-FID", object_fidelity/O-FID/fid_score.py:216-222),
     ``--num-classes`` (80 for the O-FID fine-tune, O-FID/inception.py:58-64), ``--per-class`` (extension, BASELINE
     configs[4]: one FID per object class, crops grouped by the ``{class}`` token of ``{stem}_{class}_{k}.png``,
-    object_fidelity/crop_object.py:45).
+    object_fidelity/crop_object.py:45), ``--mode clean`` (extension: clean-fid's FID -- Inception-2015, every channel resized
+    as a float32 image with Pillow's bicubic filter and not quantised, every image used; MODES below).
 """
 import contextlib
 import os
@@ -31,7 +32,7 @@ import sys
 import time
 _T_IMPORT0 = time.time()
 import warnings
-from argparse import ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
+from argparse import Action, ArgumentDefaultsHelpFormatter, ArgumentParser, ArgumentTypeError
 from dataclasses import replace
 
 import numpy as np
@@ -67,6 +68,26 @@ def _timing(label, t0=None):
 FID_NETWORKS = tuple(n for n in NETWORKS if n != "slim")
 
 
+# --mode: what an image goes through before the network and which images count.  tise: the reference's -- Pillow's 8-bit bilinear
+# resize (csrc/resize.hip), whole loader batches only.  clean: clean-fid's (Parmar et al. 2022) -- network inception-2015, every
+# channel resized as a float32 image with Pillow's antialiased bicubic filter and NOT quantised, clipped to [0, 255], mapped
+# (x - 128) / 128 (csrc/resize_f32.hip), every image used.  The file set is this module's os.walk either way (clean-fid globs and
+# sorts: the same FID, other KID subsets).
+MODES = ("tise", "clean")
+CLEAN_TAG = " [mode clean]"
+
+
+def resolve_mode(mode, network):
+    """-> the network ``mode`` runs on; ``network`` None: the mode's own (tise: torchvision, clean: inception-2015)."""
+    if mode not in MODES:
+        raise ValueError(f"unknown mode {mode!r} (choose from {', '.join(MODES)})")
+    if mode == "clean":
+        if network not in (None, "inception-2015"):
+            raise ValueError(f"--mode clean is clean-fid's FID and runs on --network inception-2015 only (got --network {network})")
+        return "inception-2015"
+    return "torchvision" if network is None else network
+
+
 def _fid_network(value):
     if value == "slim":
         raise ArgumentTypeError("the slim network (TF-slim InceptionV3 of the reference's IS* for CUB birds) has no FID in the "
@@ -74,6 +95,13 @@ def _fid_network(value):
     if value not in FID_NETWORKS:
         raise ArgumentTypeError(f"invalid choice: {value!r} (choose from {', '.join(FID_NETWORKS)})")
     return value
+
+
+class _NetworkAction(Action):
+    """--network, remembering that it was given: --mode clean has a network of its own and refuses an explicit other one."""
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.network = values
+        namespace.network_given = True
 
 
 def _build_parser():
@@ -88,10 +116,16 @@ def _build_parser():
     parser.add_argument("--saved_file", type=str, default="")
     parser.add_argument("--weights", type=str, default=None, help="torchvision-format InceptionV3 state_dict (.pth)")
     parser.add_argument("--num-classes", type=int, default=None, help="classifier width (default: 1000, 1008 for --network inception-2015)")
-    parser.add_argument("--network", type=_fid_network, default="torchvision", metavar="{" + ",".join(FID_NETWORKS) + "}",
+    parser.add_argument("--network", type=_fid_network, default="torchvision", action=_NetworkAction, metavar="{" + ",".join(FID_NETWORKS) + "}",
                         help="torchvision: torchvision's InceptionV3 (the reference's FID wrapper); inception-2015: the "
                              "TensorFlow Inception-2015 graph pytorch-fid and TTUR take FID on (pt_inception-2015-12-05-6726825d.pth); "
-                             "--save-stats then tags the .npz with network=inception-2015")
+                             "--save-stats then tags the .npz with network=inception-2015 (under --mode clean the default is inception-2015 "
+                             "and any other choice is refused)")
+    parser.set_defaults(network_given=False)
+    parser.add_argument("--mode", type=str, default="tise", choices=list(MODES),
+                        help="tise: the reference's FID (Pillow's 8-bit bilinear resize, the last N mod batch-size files dropped); "
+                             "clean: clean-fid's FID -- --network inception-2015, every channel resized as a float32 image with "
+                             "Pillow's bicubic filter and not quantised, every image used; --save-stats tags the .npz with mode=clean")
     parser.add_argument("--synthetic-weights", action="store_true",
                         help="seeded stand-in parameters (plumbing / throughput only; results are tagged)")
     parser.add_argument("--seed", type=int, default=0, help="seed of the --synthetic-weights parameters")
@@ -147,7 +181,8 @@ def _engine_for(model, dims):
         return model
     eng = getattr(model, "_tise_engine", None)
     if eng is None:
-        eng = RealismEngine(dims=dims, model=model, fold_bn=isinstance(model, InceptionV3))
+        eng = RealismEngine(dims=dims, model=model, fold_bn=isinstance(model, InceptionV3),
+                            resize="clean" if getattr(model, "fid_mode", "tise") == "clean" else "reference")
         try:
             model._tise_engine = eng
         except Exception:
@@ -253,7 +288,7 @@ def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
 
 
 def calculate_activation_statistics(images, model, batch_size=64, dims=2048, cuda=True, verbose=True,
-                                    return_device=False, keep_features=False):
+                                    return_device=False, keep_features=False, n_images=None):
     """mu = mean(act), sigma = cov(act) of the pool_3 activations (fid_score.py:174-196).
 
     Unlike the reference no (N, dims) float64 array is ever materialised: every batch is folded
@@ -262,10 +297,14 @@ def calculate_activation_statistics(images, model, batch_size=64, dims=2048, cud
     Returns numpy float64 arrays (or CUDA tensors with ``return_device``).
     ``keep_features`` (KID, opt-in): the fp32 pool3 rows of the images used are also kept on the device (8 KB per image) and
     returned as a third value, in global index order on every rank (dist.all_gather_rows).  Without it nothing is retained.
+    ``n_images`` (--mode clean): ``images`` delivers exactly this many images and EVERY one is used -- a short last batch
+    included; the reference's whole-batch bookkeeping is not applied.
     """
     _check_cuda(cuda)
     model.eval()
-    if tdist.world_size() > 1:
+    if n_images is not None:
+        n_batches = images.__len__()
+    elif tdist.world_size() > 1:
         # data-parallel: `images` is THIS rank's shard and may be empty (fewer batches than ranks).  The reference's
         # single-process bookkeeping below would divide by zero there while the other ranks wait in the all-reduce,
         # so an empty rank contributes zeros and the emptiness check is made once, on the global count.
@@ -278,12 +317,13 @@ def calculate_activation_statistics(images, model, batch_size=64, dims=2048, cud
         n_batches = d0 // batch_size                      # ZeroDivisionError for an empty loader, as upstream
     engine = _engine_for(model, dims)
     stats = device.StatsAccumulator(dims, engine.device)
-    engine.reserve_activations(min(n_batches * batch_size, device_batch_images(batch_size)))      # one allocation of the passes' peak
+    n_rows = n_batches * batch_size if n_images is None else int(n_images)
+    engine.reserve_activations(min(n_rows, device_batch_images(batch_size)))      # one allocation of the passes' peak
     if getattr(images, "pregrouped", False):              # img_data.U8CacheLoader(group=K): items are device batches already
         batches = iter(images)
     else:
         limit = device_batch_images(batch_size)
-        batches = coalesce_u8(_first(images, n_batches), engine.device, limit, (n_batches * batch_size, batch_size))
+        batches = coalesce_u8(_first(images, n_batches), engine.device, limit, (n_rows, batch_size))
     err = None
     kept = []
     try:
@@ -307,6 +347,8 @@ def calculate_activation_statistics(images, model, batch_size=64, dims=2048, cud
     tdist.all_reduce_sum_(stats.buffer())
     if tdist.world_size() > 1 and stats.count() == 0:     # identical on every rank (read after the all-reduce)
         raise ZeroDivisionError("no complete batch in the image set (global N < batch size)")
+    if n_images is not None and stats.count() == 0:
+        raise ZeroDivisionError("no image in the image set")
     mu, sigma = stats.finalize()
     if verbose:
         print(" done")
@@ -351,14 +393,29 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         f = np.load(path, allow_pickle=True)              # :201-203
         m, s = f["mu"][:], f["sigma"][:]
         tag = str(f["network"]) if "network" in f.files else None
+        mode_tag = str(f["mode"]) if "mode" in f.files else "tise"
         f.close()
         check_stats_network(path, tag, getattr(model, "network", "torchvision"))
+        check_stats_mode(path, mode_tag, getattr(model, "fid_mode", "tise"))
         if keep_features:
             return m, s, kid_features_of_npz(path)
         return m, s
     files = img_data.get_filenames(path)                  # os.walk order (img_data.py:27-35)
     rank, world, _ = tdist.env_world()
     engine = _engine_for(model, dims)
+
+    if getattr(model, "fid_mode", "tise") == "clean":
+        # every image is used: contiguous index ranges of the walk per rank (as cmmd.py), a short last loader batch; the PNG
+        # ring forms whole batches of ITS batch size, so it runs on batches of one image (as the IS* feed, inception_score.py)
+        if u8_cache:
+            raise RuntimeError("--u8-cache holds whole loader batches only (the reference's drop-last rule); --mode clean uses every image")
+        lo, hi = tdist.shard_range(len(files), rank, world)
+        shard = files[lo:hi]
+
+        def consume_all(loader):
+            return calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features, n_images=len(shard))
+        return feeds.run(feeds.FID_ALL, shard, replace(_FEED, num_workers=num_workers), consume_all, engine.device, batch_size, world,
+                         loader_args={"ring": {"batch_size": 1}})
 
     def consume(loader):
         return calculate_activation_statistics(loader, model, batch_size, dims, cuda, keep_features=keep_features)
@@ -421,12 +478,24 @@ def check_stats_network(path, tag, network):
         raise RuntimeError(f"{path}: statistics of network {tag!r}, this run uses --network {network}")
 
 
-def save_stats_npz(path, mu, sigma, network="torchvision", features=None):
+def stats_mode_tag(mode):
+    """``mode`` for --mode clean only: the default mode's files stay exactly what they were."""
+    return {} if mode == "tise" else {"mode": np.asarray(mode)}
+
+
+def check_stats_mode(path, tag, mode):
+    """Statistics of one mode (another resize, another set of images) do not compare with features of the other.  ``tag``: the
+    file's ``mode`` array, "tise" for a file without one."""
+    if tag != mode:
+        raise RuntimeError(f"{path}: statistics of mode {tag!r}, this run uses --mode {mode}")
+
+
+def save_stats_npz(path, mu, sigma, network="torchvision", features=None, mode="tise"):
     """``features`` (only under --kid or --prdc): the float32 rows those metrics need, beside mu and sigma; without it the file
-    is exactly {mu, sigma[, network]}."""
+    is exactly {mu, sigma[, network][, mode]}."""
     extra = {} if features is None else {"features": np.ascontiguousarray(
         features.cpu().numpy() if isinstance(features, torch.Tensor) else features, dtype=np.float32)}
-    np.savez(path, mu=np.asarray(mu), sigma=np.asarray(sigma), **stats_network_tag(network), **extra)
+    np.savez(path, mu=np.asarray(mu), sigma=np.asarray(sigma), **stats_network_tag(network), **stats_mode_tag(mode), **extra)
 
 
 def _build_model(dims, weights, num_classes, seed, network="torchvision"):
@@ -438,7 +507,7 @@ def _build_model(dims, weights, num_classes, seed, network="torchvision"):
 
 
 @contextlib.contextmanager
-def _own_model(dims, weights, num_classes, seed, network="torchvision"):
+def _own_model(dims, weights, num_classes, seed, network="torchvision", mode="tise"):
     """The model of ONE call of this module's path-level functions.
 
     _engine_for hangs the engine on the model and the engine holds the model: a reference cycle, so a finished call's ~1.4 GiB of
@@ -449,7 +518,9 @@ def _own_model(dims, weights, num_classes, seed, network="torchvision"):
     prompt release in place two of thirteen runs of tests/test_gpu_pipeline.py failed in tests that had never failed before
      and the cause was not found in what was left of round 6 -- the collector-driven release is the
     behaviour of rounds 1-5."""
+    network = resolve_mode(mode, network)
     model = _build_model(dims, weights, num_classes, seed, network)
+    model.fid_mode = mode                                   # _engine_for picks the resize by it, _compute_statistics_of_path the images
     try:
         yield model
     finally:
@@ -461,44 +532,47 @@ def _own_model(dims, weights, num_classes, seed, network="torchvision"):
 
 
 def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0,
-                              save_stats="", num_workers=8, u8_cache=False, network="torchvision"):
+                              save_stats="", num_workers=8, u8_cache=False, network=None, mode="tise"):
     """Calculates the FID of two paths (fid_score.py:223-238).  ``weights=None`` = seeded stand-in parameters (the
-    CLI only allows that behind --synthetic-weights)."""
+    CLI only allows that behind --synthetic-weights).  ``mode``: MODES ("clean": clean-fid's FID; ``network`` None = the
+    mode's own network, resolve_mode)."""
     return _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache,
-                                network, None)[0]
+                                network, None, mode=mode)[0]
 
 
 def calculate_fid_and_kid_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0, save_stats="",
-                                      num_workers=8, u8_cache=False, network="torchvision", subsets=100, subset_size=1000,
-                                      kid_seed=0):
+                                      num_workers=8, u8_cache=False, network=None, subsets=100, subset_size=1000,
+                                      kid_seed=0, mode="tise"):
     """FID and KID of two paths from ONE pass over each directory -> (fid, (kid_mean, kid_std)).  The pool3 rows of the images
     FID uses are kept on the device (8 KB per image) and handed to kid.kid_from_features; ``save_stats`` then also stores them
     (``features``), and an .npz path must hold them.  ``kid_seed`` seeds the subsets (``seed`` is the stand-in weights')."""
     return _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache,
-                                network, {"subsets": subsets, "subset_size": subset_size, "seed": kid_seed})[:2]
+                                network, {"subsets": subsets, "subset_size": subset_size, "seed": kid_seed}, mode=mode)[:2]
 
 
 def calculate_kid_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0, save_stats="",
-                              num_workers=8, u8_cache=False, network="torchvision", subsets=100, subset_size=1000, kid_seed=0):
-    """Kernel Inception Distance of two paths -> (mean, std) over the subsets (kid.py; std is NaN for subset_size = 0)."""
+                              num_workers=8, u8_cache=False, network=None, subsets=100, subset_size=1000, kid_seed=0, mode="tise"):
+    """Kernel Inception Distance of two paths -> (mean, std) over the subsets (kid.py; std is NaN for subset_size = 0).
+    ``mode="clean"``: clean-fid's KID (its defaults are these: 100 subsets of at most 1000)."""
     return calculate_fid_and_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers,
-                                             u8_cache, network, subsets, subset_size, kid_seed)[1]
+                                             u8_cache, network, subsets, subset_size, kid_seed, mode)[1]
 
 
 def calculate_prdc_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0, save_stats="",
-                               num_workers=8, u8_cache=False, network="torchvision", nearest_k=5):
+                               num_workers=8, u8_cache=False, network=None, nearest_k=5, mode="tise"):
     """Precision, recall, density and coverage of two paths (paths[0] the real side, paths[1] the generated side) -> OrderedDict
     (prdc.py).  One pass over each directory, as for KID: the pool3 rows are kept on the device; ``save_stats`` then also stores
     them (``features``), and an .npz path must hold them."""
     return _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache,
-                                network, None, nearest_k)[2]
+                                network, None, nearest_k, mode)[2]
 
 
 def _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache, network,
-                         kid_args, prdc_k=None):
+                         kid_args, prdc_k=None, mode="tise"):
     """calculate_fid_given_paths; with ``kid_args`` (subsets, subset_size, seed) and / or ``prdc_k`` the feature rows of both
     sides are retained and the KID / the k-NN metrics are evaluated after the Frechet distance
     -> (fid, None | (mean, std), None | OrderedDict).  Without either: the launches of the FID alone."""
+    network = resolve_mode(mode, network)
     for p in paths:
         if not os.path.exists(p):
             raise RuntimeError("Invalid path: %s" % p)    # :225-227
@@ -510,7 +584,7 @@ def _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, se
             if p.endswith(".npz"):
                 kid_features_of_npz(p, "--kid" if kid_args is not None else "--prdc")
     _check_cuda(cuda)
-    if not u8_cache:
+    if not u8_cache and mode == "tise":                    # (clean: the ring runs on batches of one image, started by feeds.run)
         # the decode workers of the first directory start now: PNG decode overlaps building the model (weights, BatchNorm
         # folding, split packing); the second directory's start when the first one's last chunk is decoded
         first = next((p for p in paths if os.path.isdir(p)), None)
@@ -525,7 +599,7 @@ def _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, se
         torch.cuda.synchronize()
         print(f"[tise timing] prealloc {os.environ['TISE_PREALLOC_GB']} GB: {time.perf_counter() - tp:.3f} s", file=sys.stderr, flush=True)
         del _x
-    with _own_model(dims, weights, num_classes, seed, network) as model:
+    with _own_model(dims, weights, num_classes, seed, network, mode) as model:
         _engine_for(model, dims)                               # fold BatchNorm, pack the split weights, load the code objects
         t = _timing("model + engine ready", t)
         m1, s1, *f1 = _compute_statistics_of_path(paths[0], model, batch_size, dims, cuda, num_workers, u8_cache, keep)
@@ -540,7 +614,7 @@ def _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, se
         m2, s2, *f2 = _compute_statistics_of_path(paths[1], model, batch_size, dims, cuda, num_workers, u8_cache, keep)
         t = _timing("second side done", t)
         if save_stats and tdist.is_main():
-            save_stats_npz(save_stats, m2, s2, network, f2[0] if keep else None)
+            save_stats_npz(save_stats, m2, s2, network, f2[0] if keep else None, mode)
 
         def solve():
             if not use_pf or np.shape(m1) != np.shape(m2) or np.shape(s1) != np.shape(s2):
@@ -571,19 +645,20 @@ def _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, se
 
 
 def save_statistics_of_path(path, out_npz, batch_size, cuda, dims, weights=None, num_classes=None, seed=0,
-                            num_workers=8, u8_cache=False, network="torchvision", keep_features=False):
+                            num_workers=8, u8_cache=False, network=None, keep_features=False, mode="tise"):
     """STATS-ONLY mode: the step BEFORE the reference path -- write the ``.npz {mu, sigma}`` that
     ``_compute_statistics_of_path`` (fid_score.py:200-203) reads (the reference ships such files,
     download_evaluation_data.py:11-12, but no script that makes them).  No Frechet distance is solved."""
     if not os.path.exists(path):
         raise RuntimeError("Invalid path: %s" % path)
+    network = resolve_mode(mode, network)
     _check_cuda(cuda)
-    if not u8_cache:
+    if not u8_cache and mode == "tise":
         prefetch_png_ring(path, batch_size, num_workers)   # decode overlaps building the model
-    with _own_model(dims, weights, num_classes, seed, network) as model:
+    with _own_model(dims, weights, num_classes, seed, network, mode) as model:
         mu, sigma, *feats = _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers, u8_cache, keep_features)
         if tdist.is_main():
-            save_stats_npz(out_npz, mu, sigma, network, feats[0] if keep_features else None)   # --kid / --prdc: the rows they need, too
+            save_stats_npz(out_npz, mu, sigma, network, feats[0] if keep_features else None, mode)   # --kid / --prdc: the rows they need, too
         return mu, sigma
 
 
@@ -676,18 +751,18 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None, ke
 
 
 def calculate_per_class_fid(paths, batch_size, cuda, dims, weights=None, num_classes=80, seed=0, num_workers=8,
-                            min_count=2, network="torchvision"):
+                            min_count=2, network=None, mode="tise"):
     """EXTENSION (BASELINE configs[4]; the reference computes ONE O-FID over all crops): a Frechet
     distance per object class.  Returns (OrderedDict class -> fid, skipped) where ``skipped`` lists classes with
     fewer than ``min_count`` crops on either side (covariance undefined)."""
-    return _per_class(paths, batch_size, cuda, dims, weights, num_classes, seed, num_workers, min_count, network, False)[:2]
+    return _per_class(paths, batch_size, cuda, dims, weights, num_classes, seed, num_workers, min_count, network, False, mode)[:2]
 
 
 def calculate_per_class_kid(paths, batch_size, cuda, dims, weights=None, num_classes=80, seed=0, num_workers=8,
-                            min_count=2, network="torchvision"):
+                            min_count=2, network=None, mode="tise"):
     """One full-set KID per object class (kid.per_class_kid: unbiased, so classes with different crop counts compare).
     Returns (OrderedDict class -> kid, skipped) like calculate_per_class_fid."""
-    return _per_class(paths, batch_size, cuda, dims, weights, num_classes, seed, num_workers, min_count, network, True)[2:]
+    return _per_class(paths, batch_size, cuda, dims, weights, num_classes, seed, num_workers, min_count, network, True, mode)[2:]
 
 
 def _class_sorted(feats_walk, path, names):
@@ -699,15 +774,16 @@ def _class_sorted(feats_walk, path, names):
     return feats_walk.index_select(0, torch.from_numpy(order).to(feats_walk.device)), offsets
 
 
-def _per_class(paths, batch_size, cuda, dims, weights, num_classes, seed, num_workers, min_count, network, with_kid):
+def _per_class(paths, batch_size, cuda, dims, weights, num_classes, seed, num_workers, min_count, network, with_kid, mode="tise"):
     """The per-class pass: -> (fids, skipped, kids | None, kid_skipped | None).  ``with_kid`` retains the crops' rows during
     the same pass (all-gathered in walk order under torchrun: every rank evaluates the 80 small groups itself)."""
     from collections import OrderedDict
     for p in paths:
         if not os.path.isdir(p):
             raise RuntimeError("Invalid path: %s" % p)
+    network = resolve_mode(mode, network)
     _check_cuda(cuda)
-    with _own_model(dims, weights, num_classes, seed, network) as model:
+    with _own_model(dims, weights, num_classes, seed, network, mode) as model:
         # the class list comes from the file names alone: the sorted union over both directories, identical on every rank,
         # dealt round-robin to the ranks
         present = [set(class_of_crop(f) for f in img_data.get_filenames(p)) for p in paths]
@@ -811,6 +887,12 @@ def main(argv=None):
     global _FEED
     parser = _build_parser()
     args = parser.parse_args(argv)
+    try:
+        args.network = resolve_mode(args.mode, args.network if args.network_given else None)
+    except ValueError as e:
+        parser.error(str(e))
+    if args.mode == "clean" and args.u8_cache:
+        parser.error("--mode clean --u8-cache is not available: the cache holds whole loader batches only, --mode clean uses every image")
     if args.num_classes is None:
         args.num_classes = NETWORK_CLASSES[args.network]
     _timing(f"imports done (this module's imports {_T_IMPORT1 - _T_IMPORT0:.2f} s)")
@@ -830,12 +912,14 @@ def main(argv=None):
         os.environ["TISE_CONV"] = "miopen" if args.conv == "exact" else "split"
     kind = tweights.inception_kind(args.network, args.label == "O-FID" and args.num_classes == 80)
     wpath, tag = tweights.resolve(args.weights, args.synthetic_weights, kind)
+    if args.mode == "clean":
+        tag = CLEAN_TAG + tag                                          # result lines name the mode
     if args.path1 is None:                                             # statistics-only
         if tdist.is_main():
             print([args.path2])
         mu, sigma = run_with_exact_fallback(lambda: save_statistics_of_path(
             args.path2, args.save_stats, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.num_workers,
-            args.u8_cache, args.network, args.kid or args.prdc), "the statistics pass")
+            args.u8_cache, args.network, args.kid or args.prdc, args.mode), "the statistics pass")
         if tdist.is_main():
             print(f"statistics of {args.path2} -> {args.save_stats}{tag}")
         return None
@@ -846,7 +930,7 @@ def main(argv=None):
     if args.per_class:
         per, skipped, kids, kid_skipped = run_with_exact_fallback(lambda: _per_class(
             paths, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.num_workers, 2,
-            args.network, args.kid), "the per-class FID")
+            args.network, args.kid, args.mode), "the per-class FID")
         mean = float(np.mean(list(per.values()))) if per else float("nan")
         if tdist.is_main():
             lines = [f"{args.label}[{c}]: {v}{tag}" for c, v in per.items()]
@@ -871,7 +955,7 @@ def main(argv=None):
     kid_args = {"subsets": args.kid_subsets, "subset_size": args.kid_subset_size, "seed": args.kid_seed} if args.kid else None
     fid_value, kid_value, prdc_value = run_with_exact_fallback(lambda: _fid_kid_given_paths(
         paths, args.batch_size, args.gpu, args.dims, wpath, args.num_classes, args.seed, args.save_stats, args.num_workers,
-        args.u8_cache, args.network, kid_args, args.prdc_k if args.prdc else None), "the FID")
+        args.u8_cache, args.network, kid_args, args.prdc_k if args.prdc else None, args.mode), "the FID")
     fid_value = fid_value.item()
     if tdist.is_main():
         if args.saved_file:
