@@ -183,6 +183,21 @@ int tise_resize_ragged_f32(const uint8_t* const* src_ptrs_host, const int32_t* h
                            uint8_t* table_host_pinned, int64_t* bad_index, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (a3t) TensorFlow 1's legacy ResizeBilinear (align_corners=False, no half-pixel centres, no antialiasing) + input affine,
+ * fused: the input route of the guided-diffusion ("ADM") evaluator's Inception graph (csrc/resize_tf1.hip).  Per axis, all in
+ * float32: scale = (float)in / (float)out, x = (float)o * scale, lo = floorf(x), hi = min(ceilf(x), in - 1), t = x - floorf(x)
+ * (lo is clamped to in - 1 as well: TensorFlow does not, and the clamp is never active at any size tested in
+ * tests/test_tf1_resize_host.py).  Per value: top = tl + (tr - tl) * tx, bot = bl + (br - bl) * tx, v = top + (bot - top) * ty,
+ * out = (v - sub) * mul -- every multiply and every add a separate fp32 operation, never a fused multiply-add.
+ *
+ *   src_dev   n images, HWC uint8, contiguous (n, h, w, 3), any alignment
+ *   dst_dev   fp32 (n, oh, ow, 3), what tise_stem_conv3x3s2_split reads
+ * A non-positive size, n < 0, a null pointer, a non-finite sub or mul: TISE_ERR_INVALID_ARG.  One launch for any n (grid-stride).
+ * ------------------------------------------------------------------------------------------ */
+int tise_resize_tf1_f32(const uint8_t* src_dev, int n, int h, int w, float* dst_dev, int oh, int ow, float sub, float mul,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a7) Streaming activation statistics: n, s = sum_i x_i, S = sum_i x_i x_i^T in fp64 from
  * fp32 feature rows that never leave the device.
  * Replaces pred_arr[start:end] = pred.cpu()...  + np.mean(act, 0) + np.cov(act, rowvar=False)
@@ -485,6 +500,12 @@ int tise_split_mean_nhwc(const void* x_dev, int n, int hw, int C, float* out_dev
 /* the same mean, also written as a split row (n, 2C) fp16 (layout above): the operand of the classifier layer, which runs
  * as a 1x1 split-precision convolution on it (the IS* logits: pool3 x W, inception_score_star_coco.py:104-105) */
 int tise_split_mean_both_nhwc(const void* x_dev, int n, int hw, int C, float* out_dev, void* out_split_dev, void* stream);
+/* A channel slice of a split tensor (n, hw, C) (layout above; C % 16 == 0) as fp32 rows: the only way a feature MAP leaves
+ * the split trunk (sFID's 17 x 17 x 7 tap of Mixed_6d).  out[i, p * nc + j] = float(hi) + float(lo) * 2^-11 of channel
+ * c0 + j of pixel p -- exact in fp32, the value conv_split.merge gives -- in h, w, c order; columns [hw * nc, ld) of every
+ * row are written as 0.  The slice may cross a 32-channel block boundary and reach into the 16-wide tail.
+ * ld < hw * nc, c0 < 0, nc <= 0, c0 + nc > C: TISE_ERR_INVALID_ARG. */
+int tise_split_tap_rows(const void* x_dev, int n, int hw, int C, int c0, int nc, float* out_dev, int64_t ld, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a11, section 8 f3) Top-1 text retrieval for R-precision and the 2-way softmax test of PA.

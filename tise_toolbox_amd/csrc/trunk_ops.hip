@@ -570,6 +570,27 @@ __global__ __launch_bounds__(256) void split_mean_kernel(const _Float16* __restr
     }
 }
 
+// channel slice [c0, c0 + nc) of a split tensor (N, HW, C) -> fp32 rows (N, ld): element (p, j) of image i at column
+// p * nc + j (h, w, c order), columns [HW * nc, ld) zero.  One thread per output column (coalesced stores; the reads are
+// 2-byte gathers of a slice that is small by construction: sFID's tap is 7 of 768 channels).  lo * 2^-11 is exact in fp32
+// (a power of two), so a contracted fma and a multiply followed by an add round the same sum once: the bits of
+// conv_split.merge either way (and for the trunk's own tensors, lo below half an ulp of hi, the sum itself is exact).
+__global__ __launch_bounds__(256) void split_tap_rows_kernel(const _Float16* __restrict__ x, int64_t total, int HW, int C,
+                                                             int c0, int nc, float* __restrict__ out, int64_t ld) {
+    const int64_t stride = (int64_t)gridDim.x * 256, used = (int64_t)HW * nc;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
+        const int64_t i = e / ld, col = e - i * ld;
+        float v = 0.f;
+        if (col < used) {
+            const int64_t p = col / nc;
+            const int c = c0 + (int)(col - p * nc);
+            const _Float16* q = x + (i * HW + p) * (int64_t)C * 2 + tise_ilv_off(c, C);
+            v = (float)q[0] + (float)q[tise_ilv_second(c, C)] * (1.f / 2048.f);
+        }
+        out[e] = v;
+    }
+}
+
 inline int grid_for(int64_t total) {
     int64_t b = (total + 255) / 256;
     if (b > 16384) b = 16384;
@@ -750,6 +771,18 @@ int tise_split_mean_both_nhwc(const void* x_dev, int n, int hw, int C, float* ou
     if (n > 65535) return TISE_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(split_mean_kernel<true>, dim3((unsigned)((C / 8 + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const _Float16*>(x_dev), n, hw, C / 8, out_dev, reinterpret_cast<_Float16*>(out_split_dev));
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+int tise_split_tap_rows(const void* x_dev, int n, int hw, int C, int c0, int nc, float* out_dev, int64_t ld, void* stream) {
+    if (!x_dev || !out_dev || n < 0 || hw <= 0 || C <= 0 || C % 16 || c0 < 0 || nc <= 0 || c0 > C - nc ||
+        ld < (int64_t)hw * nc)
+        return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    const int64_t total = (int64_t)n * ld;
+    hipLaunchKernelGGL(split_tap_rows_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const _Float16*>(x_dev), total, hw, C, c0, nc, out_dev, ld);
     TISE_LAUNCH_CHECK();
     return TISE_OK;
 }

@@ -366,6 +366,45 @@ def resize_ragged_f32(crops, out_hw=(299, 299), filter="bicubic", clip=(0, 255),
     return out
 
 
+def resize_tf1_f32(src_u8, out_hw=(299, 299), sub=128, mul=2.0 ** -7, channels_last=True):
+    """(N,H,W,3) uint8 CUDA tensor -> (N,3,oh,ow) fp32 network input of the ADM evaluator's route (tise_resize_tf1_f32):
+    TensorFlow 1's legacy ResizeBilinear (float32, align_corners=False, no half-pixel centres, no antialiasing), then
+    ``(v - sub) * mul``, every multiply and add a separate fp32 operation (tests/_tf1_resize_ref.py is the definition).  The
+    kernel writes NHWC: with ``channels_last`` the result is its NCHW view (torch.channels_last memory format, what the trunk's
+    stem reads); otherwise a contiguous NCHW copy."""
+    _require_cuda(src_u8)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3:
+        raise ValueError("src_u8 must be (N,H,W,3) uint8")
+    oh, ow = (int(v) for v in out_hw)
+    src_u8 = src_u8.contiguous()
+    n, h, w, _ = src_u8.shape
+    if h <= 0 or w <= 0 or oh <= 0 or ow <= 0:
+        raise ValueError(f"resize_tf1_f32: sizes must be positive (got {h} x {w} -> {oh} x {ow})")
+    store = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=src_u8.device)
+    if n:
+        _lib.call("tise_resize_tf1_f32", _ptr(src_u8), n, h, w, _ptr(store), oh, ow, float(sub), float(mul), _stream())
+    out = store.permute(0, 3, 1, 2)
+    return out if channels_last else out.contiguous()
+
+
+def split_tap_rows(t, c0, nc, ld):
+    """Channels [c0, c0 + nc) of a split tensor (N,H,W,2C) (conv_split.py) as fp32 rows (N, ld) (tise_split_tap_rows): row i
+    holds ``conv_split.merge(t)[i, :, :, c0:c0+nc]`` flattened in h, w, c order -- the same bits -- and zeros from column
+    H*W*nc on."""
+    _require_cuda(t)
+    if t.dtype != torch.float16 or t.dim() != 4 or t.shape[3] % 32 or not t.is_contiguous():
+        raise ValueError("t must be a contiguous split tensor (N,H,W,2C) fp16 with C % 16 == 0")
+    n, h, w, c2 = t.shape
+    c0, nc, ld = int(c0), int(nc), int(ld)
+    if h * w <= 0 or c0 < 0 or nc <= 0 or c0 + nc > c2 // 2 or ld < h * w * nc:
+        raise ValueError(f"split_tap_rows: channels [{c0}, {c0 + nc}) of {c2 // 2} into rows of {ld} < {h * w * nc} columns"
+                         if ld < h * w * nc else f"split_tap_rows: channels [{c0}, {c0 + nc}) outside 0..{c2 // 2}")
+    out = torch.empty((n, ld), dtype=torch.float32, device=t.device)
+    if n:
+        _lib.call("tise_split_tap_rows", _ptr(t), n, h * w, c2 // 2, c0, nc, _ptr(out), ld, _stream())
+    return out
+
+
 def read_split_overflow():
     """Read-and-clear the range guard of the split-fp16 activation format (csrc/common.h): True when any kernel
     since the last read converted a value above the fp16 range (65504) into a split tensor.  A NaN raises it only in

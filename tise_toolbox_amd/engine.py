@@ -62,24 +62,33 @@ def run_with_exact_fallback(fn, what="the evaluation"):
         return fn()
 
 
-RESIZES = ("reference", "clean")
+RESIZES = ("reference", "clean")          # the resizes behind fid_score's modes (--mode tise / clean)
+SUITE_RESIZES = ("tf1",)                   # ... and the one only the ADM suite (adm_eval.py) uses
 
 
 class RealismEngine:
     def __init__(self, dims=2048, device_index=None, weights=None, num_classes=None, seed=0,
                  channels_last=None, fold_bn=True, with_logits=False, model=None, normalize_input=True,
-                 lut=None, fused=None, fc_bias="auto", network="torchvision", resize="reference"):
+                 lut=None, fused=None, fc_bias="auto", network="torchvision", resize="reference", spatial=False):
         """``network``: inception.NETWORKS -- "inception-2015" builds the TensorFlow Inception-2015 graph's variant of the
         model (its pools, 1008-class head unless ``num_classes`` says otherwise) and its input table (device.make_lut).
         ``resize``: "reference" -- Pillow's 8-bit bilinear resize, the reference's (csrc/resize.hip); "clean" -- clean-fid's:
         every channel resized as a float32 image with Pillow's bicubic filter, not quantised, clipped to [0, 255] and mapped
-        (x - 128) / 128 (csrc/resize_f32.hip), for the Inception-2015 network only (whose input map that is)."""
+        (x - 128) / 128 (csrc/resize_f32.hip), for the Inception-2015 network only (whose input map that is); "tf1" -- the
+        ADM evaluator's: TensorFlow 1's legacy float32 ResizeBilinear, then (x - 128) * 2^-7 (csrc/resize_tf1.hip), for the
+        same network only.
+        ``spatial``: the split-precision trunk also hands out the first 7 channels of Mixed_6d's 1x1 branch (17 x 17 x 7, the
+        ADM evaluator's sFID features) as rows of 2048 fp32 (25 zero columns): begin() creates ``stats_spatial``, the steps
+        feed it, ``statistics_spatial()`` finalises it.  Needs dims 2048 and the split trunk; runs eagerly (no hipGraph)."""
         require_gpu()
-        if resize not in RESIZES:
-            raise ValueError(f"unknown resize {resize!r} (choose from {', '.join(RESIZES)})")
+        if resize not in RESIZES + SUITE_RESIZES:
+            raise ValueError(f"unknown resize {resize!r} (choose from {', '.join(RESIZES + SUITE_RESIZES)})")
         net = getattr(model, "network", "torchvision") if model is not None else network
         if resize == "clean" and net != "inception-2015":
             raise ValueError(f"resize='clean' is clean-fid's route and runs on network 'inception-2015' only (got {net!r})")
+        if resize == "tf1" and net != "inception-2015":
+            raise ValueError(f"resize='tf1' is the ADM evaluator's route and runs on network 'inception-2015' only (got {net!r})")
+        self.spatial = bool(spatial)
         self.resize = resize
         if device_index is None:
             device_index = torch.cuda.current_device()
@@ -125,15 +134,19 @@ class RealismEngine:
             # TISE_CONV=split (default, every --dims): hand-written split-precision fp16-MFMA convolutions;
             # TISE_CONV=miopen: MIOpen fp32 convolutions + HIP epilogues
             use_split = os.environ.get("TISE_CONV", "split") == "split"
-            self.fused = (SplitTrunk if use_split else FusedTrunk)(self.model, self.device)
+            self.fused = (SplitTrunk if use_split else FusedTrunk)(self.model, self.device, spatial=self.spatial)
+        if self.spatial and not getattr(self.fused, "spatial", False):
+            raise ValueError("spatial=True needs the split-precision trunk (TISE_CONV=split, channels_last, the fused trunk)")
         self.stats = None
+        self.stats_spatial = None
         self.is_acc = None
         # Optional hipGraph replay of resize + trunk (~85 launches per batch, all on one stream), TISE_GRAPH=1.
         # Measured no faster than eager launching here (25.7 vs 25.6 ms per 500-image step: the host keeps the queue
         # full and the GPU's launch-to-launch gap is the same either way), so it is off by default; it pays when the
         # host is the slower side (small batches).  Only for the all-HIP trunk (MIOpen picks solvers at run time).
         from .trunk import SplitTrunk as _ST
-        self._graph_ok = isinstance(self.fused, _ST) and os.environ.get("TISE_GRAPH", "0") == "1"
+        # (a spatial engine is not captured: the rows of the pass are a second output that the replay does not hand out)
+        self._graph_ok = isinstance(self.fused, _ST) and os.environ.get("TISE_GRAPH", "0") == "1" and not self.spatial
         self._u8_stem = isinstance(self.fused, _ST) and os.environ.get("TISE_U8_STEM", "1") != "0"
         self.lut_dev = torch.from_numpy(np.ascontiguousarray(self.lut, dtype=np.float32).reshape(-1)).to(self.device)
         self._graphs = {}
@@ -145,9 +158,16 @@ class RealismEngine:
         fn = device.resize_ragged_f32 if ragged else device.resize_f32
         return fn(u8, (299, 299), "bicubic", (0, 255), INCEPTION_2015_INPUT_SUB, INCEPTION_2015_INPUT_DIV, channels_last=self.channels_last)
 
+    def _tf1_input(self, u8):
+        """The ADM route's network input: (N,3,299,299) fp32, channels_last as the engine's trunk reads it."""
+        from .inception import INCEPTION_2015_INPUT_SUB
+        return device.resize_tf1_f32(u8, (299, 299), INCEPTION_2015_INPUT_SUB, 2.0 ** -7, channels_last=self.channels_last)
+
     def _features_from_u8_eager(self, batch_u8):
         if self.resize == "clean":
             return self._trunk(self._clean_input(batch_u8), prenormalized=True)
+        if self.resize == "tf1":
+            return self._trunk(self._tf1_input(batch_u8), prenormalized=True)
         if self._u8_stem:
             # all-HIP trunk: the resize kernel writes the Pillow-exact uint8 image only and the stem convolution
             # applies the input table (134 MB instead of 536 MB of network input per 500 images; same features)
@@ -217,6 +237,8 @@ class RealismEngine:
         crops = [(c[0] if c.dim() == 4 else c).to(self.device, non_blocking=True) for c in crops]
         if self.resize == "clean":
             return self._trunk(self._clean_input(crops, ragged=True), prenormalized=True)
+        if self.resize == "tf1":
+            raise ValueError("resize='tf1' takes batches of equal-sized images (features_from_u8), not ragged crop lists")
         u8 = device.resize_ragged_u8(crops, (299, 299))
         if self._u8_stem:
             return self._trunk_u8(u8)
@@ -269,7 +291,7 @@ class RealismEngine:
         images = int(images)
         if images <= getattr(self, "_reserved_images", 0) or not isinstance(self.fused, SplitTrunk) or os.environ.get("TISE_RESERVE", "1") == "0":
             return 0
-        nbytes = images * (self.ACT_BYTES_PER_IMAGE + (self.CLEAN_INPUT_BYTES_PER_IMAGE if self.resize == "clean" else 0))
+        nbytes = images * (self.ACT_BYTES_PER_IMAGE + (self.CLEAN_INPUT_BYTES_PER_IMAGE if self.resize in ("clean", "tf1") else 0))
         free, _total = torch.cuda.mem_get_info(self.device)
         have = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)      # cached, free blocks
         if nbytes <= have or nbytes > 0.6 * free:
@@ -287,6 +309,8 @@ class RealismEngine:
         self.fc_bias = fc_bias_for_rule(rule, self._fc_bias_mode if fc_bias is None else fc_bias)
         self._range_hit = False                                         # new accumulators: see _check_accumulated
         self.stats = device.StatsAccumulator(self.dims, self.device)
+        # the spatial rows are 2048 wide (2023 values + 25 zero columns): the accumulator's d % 64 == 0 path; zeros add nothing
+        self.stats_spatial = device.StatsAccumulator(self.fused.SPATIAL_LD, self.device) if self.spatial else None
         self.is_acc = None
         if self.with_logits:
             if n_total is None:
@@ -298,6 +322,7 @@ class RealismEngine:
     def step_u8(self, batch_u8, idx_base=0):
         feats, logits = self.features_from_u8(batch_u8)
         self.stats.update(feats)
+        self._update_spatial(feats)
         if self.is_acc is not None:
             self.is_acc.update(logits, idx_base)
         return feats
@@ -305,6 +330,7 @@ class RealismEngine:
     def step_u8_list(self, crops, idx_base=0):
         feats, logits = self.features_from_u8_list(crops)
         self.stats.update(feats)
+        self._update_spatial(feats)
         if self.is_acc is not None:
             self.is_acc.update(logits, idx_base)
         return feats
@@ -312,13 +338,31 @@ class RealismEngine:
     def step_float(self, batch, idx_base=0):
         feats, logits = self.features_from_float(batch)
         self.stats.update(feats)
+        self._update_spatial(feats)
         if self.is_acc is not None:
             self.is_acc.update(logits, idx_base)
         return feats
 
+    def spatial_rows(self):
+        """(B, 2048) fp32 rows of the last features_from_* pass of a spatial engine: 2023 values (17 x 17 x 7 in h, w, c
+        order), 25 zeros.  A step_* consumes them (None afterwards)."""
+        if not self.spatial:
+            raise ValueError("spatial_rows() needs RealismEngine(spatial=True)")
+        return self.fused._spatial_rows
+
+    def _update_spatial(self, feats):
+        if self.stats_spatial is not None:
+            rows = self.fused._spatial_rows
+            if rows is None or rows.shape[0] != feats.shape[0]:
+                raise RuntimeError("spatial=True: this pass did not go through the split trunk (no Mixed_6d rows to accumulate)")
+            self.stats_spatial.update(rows)
+            self.fused._spatial_rows = None                             # one pass, one update
+
     def reduce(self):
         """One all-reduce(SUM) per accumulator over RCCL (no-op for a single process)."""
         tdist.all_reduce_sum_(self.stats.buffer())
+        if self.stats_spatial is not None:
+            tdist.all_reduce_sum_(self.stats_spatial.buffer())
         if self.is_acc is not None:
             tdist.all_reduce_sum_(self.is_acc.acc)
 
@@ -349,6 +393,18 @@ class RealismEngine:
         """(mu, sigma) fp64 CUDA tensors of everything accumulated (after reduce())."""
         self._check_accumulated()
         return self.stats.finalize()
+
+    SPATIAL_DIMS = 17 * 17 * 7
+
+    def statistics_spatial(self):
+        """(mu (2023,), sigma (2023, 2023)) fp64 CUDA tensors of the spatial rows accumulated (after reduce()): the ADM
+        evaluator's ``mu_s`` / ``sigma_s``."""
+        if self.stats_spatial is None:
+            raise ValueError("statistics_spatial() needs RealismEngine(spatial=True) and begin()")
+        self._check_accumulated()
+        mu, sigma = self.stats_spatial.finalize()
+        d = self.SPATIAL_DIMS
+        return mu[:d].contiguous(), sigma[:d, :d].contiguous()
 
     def inception_score(self):
         self._check_accumulated()

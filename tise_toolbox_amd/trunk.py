@@ -96,8 +96,11 @@ class _Conv:
 class FusedTrunk:
     """Callable: (N,299,299,3)-storage channels-last input -> pool3 features (N, 2048) fp32."""
 
-    def __init__(self, model, device):
+    def __init__(self, model, device, spatial=False):
         assert isinstance(model, InceptionV3)
+        if spatial and not isinstance(self, SplitTrunk):
+            raise ValueError("spatial=True (the 17 x 17 x 7 tap of Mixed_6d, sFID) is served by the split-precision trunk only "
+                             "(TISE_CONV=split); the MIOpen trunk keeps no feature map")
         self.device = torch.device(device)
         with torch.no_grad():
             mods = dict(model.named_modules())
@@ -345,8 +348,17 @@ class SplitTrunk(FusedTrunk):
     768 / 2048, inception.py:14-19): the output is always the GLOBAL MEAN of that block's feature map, (N, C, 1, 1) --
     what fid_score.py:110-111's adaptive_avg_pool2d makes of the map the reference wrapper returns."""
 
-    def __init__(self, model, device):
-        super().__init__(model, device)
+    SPATIAL_BLOCK, SPATIAL_C0, SPATIAL_NC, SPATIAL_LD = 6, 0, 7, 2048
+
+    def __init__(self, model, device, spatial=False):
+        """``spatial``: after Mixed_6d (``sblocks[6]``) also keep channels 0..6 of that block's output -- its ``branch1x1``
+        after ReLU, TensorFlow's ``mixed_6/conv:0`` -- as fp32 rows (n, 2048) in ``_spatial_rows``: 17 x 17 x 7 = 2023 values
+        in h, w, c order and 25 zero columns (sFID's features; for --dims 2048 only)."""
+        super().__init__(model, device, spatial=spatial)
+        if spatial and self.last_block != 3:
+            raise ValueError("spatial=True needs the whole trunk (dims 2048): the tap sits behind Mixed_6d")
+        self.spatial = bool(spatial)
+        self._spatial_rows = None
         from .conv_split import SplitConv
 
         def sc(c):                                              # c's parameters were checked by FusedTrunk.__init__
@@ -607,7 +619,6 @@ class SplitTrunk(FusedTrunk):
     def _after_pool1(self, a, pooled):
         """Everything behind stem max-pool 1.  ``pooled``: ``a`` is the pooled tensor (Conv2d_2b's epilogue or the stand-alone
         kernel pooled it); otherwise ``a`` is Conv2d_2b's full result and Conv2d_3b takes the pool inside its operand load."""
-        fn = {"A": self._sblock_a, "B": self._sblock_b, "C": self._sblock_c, "D": self._sblock_d, "E": self._sblock_e}
         if self.last_block == 0:                                        # --dims 64: block 0 ends with max-pool 1
             return self._global_mean(a)
         if pooled:
@@ -624,22 +635,26 @@ class SplitTrunk(FusedTrunk):
             hp = self._new(n, oh, (ow - 3) // 2 + 1, self.s4a.cout, t.device)
             self.s4a(t, [(0, self.s4a.cout, hp, 0, 0)], pool_h=True)               # Conv2d_4a + horizontal half of max-pool 2
             a = self._sblock_a(hp, self.sblocks[0][1], pooled_input="v")           # vertical half + Mixed_5b
-            rest = self.sblocks[1:]
-            for kind, P in rest:
-                a = fn[kind](a, P)
-            return self._global_mean(a)
+            return self._global_mean(self._run_blocks(a, 1))
         a = self._sconv(self.s4a, t)
         if self.last_block == 1:                                        # --dims 192: block 1 ends with max-pool 2
             return self._global_mean(self._maxpool_split(a))
         if self.fuse_pool:
             a = self._sblock_a(a, self.sblocks[0][1], pooled_input=True)           # max-pool 2 + Mixed_5b
-            rest = self.sblocks[1:]
-        else:
-            a = self._maxpool_split(a)
-            rest = self.sblocks
-        for kind, P in rest:                                            # --dims 768 stops after Mixed_6e, 2048 after Mixed_7c
+            return self._global_mean(self._run_blocks(a, 1))
+        return self._global_mean(self._run_blocks(self._maxpool_split(a), 0))
+
+    def _run_blocks(self, a, first):
+        """``sblocks[first:]`` in order (--dims 768 stops after Mixed_6e, 2048 after Mixed_7c); with ``spatial`` the tap is
+        read from Mixed_6d's output before the next block runs."""
+        fn = {"A": self._sblock_a, "B": self._sblock_b, "C": self._sblock_c, "D": self._sblock_d, "E": self._sblock_e}
+        for i in range(first, len(self.sblocks)):
+            kind, P = self.sblocks[i]
             a = fn[kind](a, P)
-        return self._global_mean(a)
+            if self.spatial and i == self.SPATIAL_BLOCK:
+                from .device import split_tap_rows
+                self._spatial_rows = split_tap_rows(a, self.SPATIAL_C0, self.SPATIAL_NC, self.SPATIAL_LD)
+        return a
 
     def _global_mean(self, a):
         n, h, w, c2 = a.shape                                           # merge + global average, one pass
