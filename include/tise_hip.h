@@ -565,6 +565,40 @@ int tise_text_tokens_f16(const int32_t* tokens_dev, const void* table_dev, const
 int tise_gather_rows_f16(const void* x_dev, const int64_t* index_dev, int64_t n, int width, void* out_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The DINOv2 ViT tower (FD-DINOv2, tise_toolbox_amd/dinov2_hip.py): what torch.autocast(fp16) computes -- fp16 operands on the
+ * matrix cores, fp32 accumulation, an FP32 RESIDUAL STREAM, LayerNorm from fp32, fp32 features.  Attention, the patch matrix
+ * and the fp16 GEMMs are the entries above.
+ *   tise_gemm_f16_act    tise_gemm_f16 -- the same kernels, arguments and refusals -- with one more activation: act 2 = exact
+ *                        GELU 0.5 v (1 + erff(v / sqrt 2)), applied in fp32 before the one fp16 rounding as QuickGELU is
+ *                        (-inf gives -0, +inf +inf, NaN NaN); act 0 and 1 give tise_gemm_f16's bits.  tise_gemm_f16 itself
+ *                        keeps refusing every act but 0 and 1.  Under the default instance rule an act 2 launch stays on a
+ *                        128 x 128 kernel (the erff epilogue needs the second workgroup of a CU to hide under).
+ *   tise_gemm_f16_res32  out32[m][n] = res32[m][n] + scale[n] * (sum_k a[m][k] w[n][k] + bias[n]): the kernels, main loops and
+ *                        instance rule of tise_gemm_f16 (TISE_GEMM_BIG / TISE_GEMM_SHAPE included) with another epilogue;
+ *                        everything after the fp32 accumulator stays fp32 (one add for the bias, one multiply, one add, each
+ *                        rounded once, no fma).  a / w / bias as tise_gemm_f16 (fp16; bias nullable); scale fp32 [n],
+ *                        nullable (= 1); res32 / out32 fp32, never null, leading dimensions in elements, % 4 == 0 and >= n.
+ *                        out32 == res32 with ldo == ldr is allowed (the tower updates its stream in place); any other
+ *                        overlap is undefined.  k % 64 == 0, n % 8 == 0; a / w / scale / res32 / out32 16-byte aligned,
+ *                        bias 8-byte aligned.
+ *   tise_layernorm_f32   tise_layernorm_f16 on an fp32 row with fp32 gamma / beta, eps inside the square root;
+ *                        out_f32 0: fp16 rows (ldo % 8 == 0) for the next GEMM, 1: fp32 rows (ldo % 4 == 0), the features.
+ *                        C <= 1024, C % 8 == 0, ldx % 4 == 0, ldx / ldo >= C, 16-byte aligned pointers.
+ *   tise_vit_tokens_f32  x[b][0] = class_tok + pos[0]; x[b][1+p] = float(patch_out[b*n_patches+p]) + pos[1+p]: fp16 rows of
+ *                        the patch GEMM, fp32 class row and position table, fp32 tokens (one fp32 add per element)
+ *   tise_gather_rows_f32 out[i] = x[index[i]], fp32 rows (the class token of every image)
+ * ------------------------------------------------------------------------------------------ */
+int tise_gemm_f16_act(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* res_dev,
+                      int64_t ldr, void* out_dev, int64_t ldo, int m, int n, int k, int act, void* stream);
+int tise_gemm_f16_res32(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* scale_dev,
+                        const void* res32_dev, int64_t ldr, void* out32_dev, int64_t ldo, int m, int n, int k, void* stream);
+int tise_layernorm_f32(const void* x_dev, int64_t ldx, const void* gamma_dev, const void* beta_dev, void* out_dev, int64_t ldo,
+                       int64_t rows, int C, float eps, int out_f32, void* stream);
+int tise_vit_tokens_f32(const void* patch_out_dev, const void* class_tok_dev, const void* pos_emb_dev, int batch, int n_patches,
+                        int width, void* x_dev, void* stream);
+int tise_gather_rows_f32(const void* x_dev, const int64_t* index_dev, int64_t n, int width, void* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a5, convolution) Implicit-GEMM convolution on fp16 MFMA with 3-term split-precision operands.
  * Replaces the Conv2d + BatchNorm(eval) + ReLU of torchvision's BasicConv2d for split tensors (layout above;
  * v ~= hi + lo * 2^-11): D = max(scale * conv(x, w) + bias, 0), re-split and written

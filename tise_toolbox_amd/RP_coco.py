@@ -183,22 +183,26 @@ def encode_paths(model, paths, dev, batch, workers, feed, convert_first, finish,
     own input resolution (``model.resolution``; 224 for a model that does not say) on both roads."""
     out = []
     size = getattr(model, "resolution", 224)
+    # a tower with a preprocessing of its own (dinov2_hip.HipDino) brings it along; the CLIP towers have none: clip's
+    on_device = getattr(model, "preprocess_device", clip_model.preprocess_device)
+    on_host = getattr(model, "preprocess", clip_model.preprocess)
 
     def consume(loader):
         out.clear()                                           # the DataLoader pass after a ring that met an odd file starts afresh
         for x in loader:
-            # the ring delivers uint8 (clip's preprocess on the device), the DataLoader's workers preprocessed fp32
-            f = model.encode_image((clip_model.preprocess_device(x, size) if x.dtype == torch.uint8 else x.to(dev)).half())
+            # the ring delivers uint8 (the tower's preprocess on the device), the DataLoader's workers preprocessed fp32
+            f = model.encode_image((on_device(x, size) if x.dtype == torch.uint8 else x.to(dev)).half())
             out.append(finish(f))
     feeds.run(feeds.CLIP, paths, feeds.Options(png_feed=feed, num_workers=workers), consume, dev, batch, tdist.world_size(),
               loader_args={"ring": {"batch_size": 1, "group": batch, "rgb_only": not convert_first},
-                           "dataloader": {"dataset": _Paths(paths, convert_first, size), "pin_memory": False, "collate": None}})
+                           "dataloader": {"dataset": _Paths(paths, convert_first, size, on_host), "pin_memory": False, "collate": None}})
     return torch.cat(out).contiguous() if out else torch.empty((0, getattr(model, "out_dim", 512)), dtype=dtype, device=dev)
 
 
 class _Paths(torch.utils.data.Dataset):
-    def __init__(self, paths, convert_first=True, size=224):
+    def __init__(self, paths, convert_first=True, size=224, preprocess=None):
         self.paths, self.convert_first, self.size = paths, convert_first, size
+        self.preprocess = clip_model.preprocess if preprocess is None else preprocess
 
     def __len__(self):
         return len(self.paths)
@@ -206,7 +210,7 @@ class _Paths(torch.utils.data.Dataset):
     def __getitem__(self, i):
         from PIL import Image
         img = Image.open(self.paths[i])
-        return clip_model.preprocess(img.convert("RGB") if self.convert_first else img, self.size)   # (clip's preprocess converts to RGB itself, after the resize)
+        return self.preprocess(img.convert("RGB") if self.convert_first else img, self.size)   # (clip's preprocess converts to RGB itself, after the resize)
 
 
 def embed_images(model, image_dir, caption_ids, dev, batch, workers=0, feed="ring"):

@@ -27,14 +27,15 @@ def _stream():
 
 
 def gemm(a, w, bias=None, residual=None, act=0, out=None):
-    """out = act(a @ w.T + bias) + residual;  a (M, K), w (N, K) fp16 CUDA, row strides arbitrary multiples of 8."""
+    """out = act(a @ w.T + bias) + residual;  a (M, K), w (N, K) fp16 CUDA, row strides arbitrary multiples of 8.
+    act: 0 none, 1 QuickGELU (tise_gemm_f16, the CLIP towers' entry), 2 exact (erf) GELU (tise_gemm_f16_act: the DINOv2 tower)."""
     assert a.dtype == w.dtype == torch.float16 and a.is_cuda and a.dim() == 2 and w.dim() == 2 and a.shape[1] == w.shape[1]
     assert a.stride(1) == 1 and w.stride(1) == 1
     m, k = a.shape
     n = w.shape[0]
     if out is None:
         out = torch.empty((m, n), dtype=torch.float16, device=a.device)
-    _lib.call("tise_gemm_f16", _p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(residual),
+    _lib.call("tise_gemm_f16_act" if int(act) == 2 else "tise_gemm_f16", _p(a), a.stride(0), _p(w), w.stride(0), _p(bias), _p(residual),
               residual.stride(0) if residual is not None else 0, _p(out), out.stride(0), m, n, k, int(act), _stream())
     return out
 

@@ -16,6 +16,10 @@
 //                        maximum.
 //   vit_tokens_f16_kernel / text_tokens_f16_kernel / patchify_f16_kernel / patchify_pad_f16_kernel (any patch size, rows
 //   padded with zeros to the GEMM's K-step) / gather_rows_f16_kernel: token assembly.
+// The DINOv2 tower of FD-DINOv2 (dinov2_hip.HipDino) keeps its residual stream in fp32 -- what torch.autocast(fp16) computes:
+//   the GEMM kernels' epilogue is a template parameter (EPI_F16 above, EPI_RES32: out32 = res32 + scale * (A W^T + bias), fp32
+//   after the accumulator), act 2 (tise_gemm_f16_act only) is the exact (erf) GELU, and layernorm_f32_kernel / vit_tokens_f32_kernel /
+//   gather_rows_f32_kernel are the fp32-stream siblings of the kernels above.
 #include <hip/hip_fp16.h>
 #include <cstdlib>
 #include "common.h"
@@ -32,14 +36,57 @@ __device__ __attribute__((aligned(128))) unsigned char g_clip_zero_page[128];
 
 #define GM_BK 64
 
+typedef float float4_t __attribute__((ext_vector_type(4)));
+
 struct GemmArgs {
     const _Float16* a; long long lda;
     const _Float16* w; long long ldw;
     const _Float16* bias;                            // [N] or null
     const _Float16* res; long long ldr;              // [M][ldr] or null
     _Float16* out; long long ldo;
-    int M, N, K, act;                                // act: 0 none, 1 QuickGELU (x * sigmoid(1.702 x))
+    int M, N, K, act;                                // act: 0 none, 1 QuickGELU (x * sigmoid(1.702 x)), 2 exact GELU (erf)
+    // EPI_RES32 only (tise_gemm_f16_res32): out32 = res32 + scale * (acc + bias), all in fp32
+    const float* scale;                              // [N] or null (= 1)
+    const float* res32; long long ldr32;             // [M][ldr32]
+    float* out32; long long ldo32;                   // may be res32 itself: a lane reads the 16 bytes it then writes
 };
+
+// The epilogue of a GEMM kernel is a template parameter: the main loops are the same code.
+//   EPI_F16    out = fp16(act(acc + bias)) [+ fp16 residual, a second rounding]: the fp16 stream of the CLIP towers
+//   EPI_RES32  out32 = res32 + scale * (acc + bias): nothing after the accumulator is rounded to fp16 -- the fp32 residual
+//              stream of the DINOv2 tower (dinov2_hip.HipDino), LayerScale fused
+enum { EPI_F16 = 0, EPI_RES32 = 1 };
+
+// nn.GELU() / F.gelu: 0.5 v (1 + erf(v / sqrt 2)) in fp32.  Far below zero erff returns -1 exactly and the sum is 0: the
+// result is -0 there, for v = -inf too (0.5 v * 0 would be NaN); +inf stays +inf and NaN stays NaN.
+__device__ __forceinline__ float gelu_erf(float v) {
+    const float t = 1.0f + erff(v * 0.70710678118654752440f);
+    return t == 0.0f ? -0.0f : (0.5f * v) * t;
+}
+
+// EPI_RES32, second half: the wave's 32 x 64 fp32 staging rows (pitch 272 bytes: 256 + 16, so that the rows of a 16-byte
+// column of writes start 4 banks apart, as the fp16 pitch of 144 does) leave as whole 256-byte rows = two full lines: 16
+// lanes per row, four rows per pass.  One fp32 multiply and one fp32 add per element, never contracted into an fma.
+constexpr int GM_PITCH32 = 272;
+__device__ __forceinline__ void gemm_store_res32(const GemmArgs& p, const unsigned char* st, int lane, int mrow0, int ncol0) {
+#pragma unroll
+    for (int pass = 0; pass < 8; ++pass) {
+        const int r = pass * 4 + (lane >> 4), ch = lane & 15;
+        const int m = mrow0 + r, n = ncol0 + ch * 4;
+        float4_t v = *reinterpret_cast<const float4_t*>(st + r * GM_PITCH32 + ch * 16);
+        if (m < p.M && n < p.N) {
+            const float4_t rr = *reinterpret_cast<const float4_t*>(p.res32 + (long long)m * p.ldr32 + n);
+            if (p.scale) {
+                const float4_t s = *reinterpret_cast<const float4_t*>(p.scale + n);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = __fmul_rn(s[k], v[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = __fadd_rn(rr[k], v[k]);
+            *reinterpret_cast<float4_t*>(p.out32 + (long long)m * p.ldo32 + n) = v;
+        }
+    }
+}
 
 // 128 x 128 x 64 tiles: four waves (2 x 2 of 64 x 64), TWO LDS stages of 32 KB, two workgroups per CU -- the structure of
 // the convolution kernel (conv_split.hip).  The first version used 256 x 128 tiles with eight waves and three stages
@@ -47,6 +94,7 @@ struct GemmArgs {
 // fully exposed, and the towers' GEMMs are short: K = 512 / 768 is 8 / 12 K-steps.  With two workgroups per CU the
 // second one computes meanwhile: 5-15 % faster on every tower shape (tools/clip_gemm_probe.py) although a CU now
 // moves 64 KB instead of 48 KB of operands per 128 MFMAs.
+template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmArgs p) {
     constexpr int BM = 128, BN = 128;
     constexpr int A_BYTES = BM * 128, STAGE = A_BYTES + BN * 128;         // 32 KB
@@ -160,10 +208,27 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmArgs p) {
     }
     __syncthreads();
     constexpr int PITCH = 144;
-    unsigned char* st = lds + wave * (32 * PITCH);
+    unsigned char* st = lds + wave * (32 * (EPI == EPI_RES32 ? GM_PITCH32 : PITCH));
     const int ncol0 = n0 + wn * 64;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
+        if constexpr (EPI == EPI_RES32) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int cl = j * 32 + 8 * g + 4 * (lane >> 5);
+                    const int n = ncol0 + cl;
+                    half4_t bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+                    if (p.bias && n < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + n);
+                    float4_t f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) f[k] = acc[i][j][4 * g + k] + (float)bq[k];
+                    *reinterpret_cast<float4_t*>(st + (lane & 31) * GM_PITCH32 + cl * 4) = f;
+                }
+            gemm_store_res32(p, st, lane, m0 + wm * 64 + i * 32, ncol0);
+            continue;
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -176,6 +241,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmArgs p) {
                 for (int k = 0; k < 4; ++k) {
                     float v = acc[i][j][4 * g + k] + (float)bq[k];
                     if (p.act == 1) v = v / (1.0f + __expf(-1.702f * v));
+                    else if (p.act == 2) v = gelu_erf(v);
                     h[k] = (_Float16)v;
                 }
                 *reinterpret_cast<half4_t*>(st + (lane & 31) * PITCH + cl * 2) = h;
@@ -202,6 +268,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmArgs p) {
 // 64 B/clk of the 128 x 128 kernel and the ~38 B/clk the LDS-DMA path delivers -- and a wave reads 6 fragments per 8
 // MFMAs instead of 4 per 4.  The price is one workgroup per CU: the DMA latency in front of a tile's first K-step and
 // its epilogue are exposed, so the launcher uses it only where a tile has enough K-steps and the launch enough tiles.
+template <int EPI>
 __global__ __launch_bounds__(512, 1) void gemm_f16_big_kernel(const GemmArgs p) {
     constexpr int BM = 256, BN = 256;
     constexpr int A_BYTES = BM * 128, STAGE = A_BYTES + BN * 128;         // 64 KB
@@ -304,10 +371,27 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_big_kernel(const GemmArgs p) 
     }
     __syncthreads();
     constexpr int PITCH = 144;
-    unsigned char* st = lds + wave * (32 * PITCH);
+    unsigned char* st = lds + wave * (32 * (EPI == EPI_RES32 ? GM_PITCH32 : PITCH));
     const int ncol0 = n0 + wn * 64;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+        if constexpr (EPI == EPI_RES32) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int cl = j * 32 + 8 * g + 4 * (lane >> 5);
+                    const int n = ncol0 + cl;
+                    half4_t bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+                    if (p.bias && n < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + n);
+                    float4_t f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) f[k] = acc[i][j][4 * g + k] + (float)bq[k];
+                    *reinterpret_cast<float4_t*>(st + (lane & 31) * GM_PITCH32 + cl * 4) = f;
+                }
+            gemm_store_res32(p, st, lane, m0 + wm * 128 + i * 32, ncol0);
+            continue;
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -320,6 +404,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_big_kernel(const GemmArgs p) 
                 for (int k = 0; k < 4; ++k) {
                     float v = acc[i][j][4 * g + k] + (float)bq[k];
                     if (p.act == 1) v = v / (1.0f + __expf(-1.702f * v));
+                    else if (p.act == 2) v = gelu_erf(v);
                     h[k] = (_Float16)v;
                 }
                 *reinterpret_cast<half4_t*>(st + (lane & 31) * PITCH + cl * 2) = h;
@@ -350,9 +435,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_big_kernel(const GemmArgs p) 
 // The chunk swizzle is the convolution kernels' tise_lds_swz (conflict-free for 16-row fragments).
 // BIG = false: 128 x 128 x 64 tiles, 4 waves of 64 x 64, two workgroups per CU;  BIG = true: 256 x 256 x 64, 8 waves of
 // 128 x 64, one per CU.  TISE_GEMM_SHAPE=32 selects the 32x32x16 kernels above (A/B of tools/clip_gemm_probe.py).
-typedef float float4_t __attribute__((ext_vector_type(4)));
-
-template <bool BIG>
+template <bool BIG, int EPI>
 __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : 2) void gemm16_f16_kernel(const GemmArgs p) {
     constexpr int BM = BIG ? 256 : 128, BN = BM;
     constexpr int NW = BIG ? 8 : 4;
@@ -467,10 +550,28 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : 2) void gemm16_f16_kerne
     // epilogue: 32 rows x 64 columns at a time through the wave's staging rows (as the kernels above); the accumulator
     // block (i, j) holds row m = 16 i + (lane & 15) and the four columns n = 16 j + 4 (lane >> 4) + k of this lane
     constexpr int PITCH = 144;
-    unsigned char* st = lds + wave * (32 * PITCH);
+    unsigned char* st = lds + wave * (32 * (EPI == EPI_RES32 ? GM_PITCH32 : PITCH));
     const int ncol0 = n0 + wn * 64;
 #pragma unroll
     for (int i2 = 0; i2 < MI / 2; ++i2) {
+        if constexpr (EPI == EPI_RES32) {
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+                const int cl = 16 * j + 4 * (lane >> 4);
+                const int n = ncol0 + cl;
+                half4_t bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+                if (p.bias && n < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + n);
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2) {
+                    float4_t f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) f[k] = acc[2 * i2 + h2][j][k] + (float)bq[k];
+                    *reinterpret_cast<float4_t*>(st + (16 * h2 + (lane & 15)) * GM_PITCH32 + cl * 4) = f;
+                }
+            }
+            gemm_store_res32(p, st, lane, m0 + wm * WM + i2 * 32, ncol0);
+            continue;
+        }
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int cl = 16 * j + 4 * (lane >> 4);
@@ -484,6 +585,7 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : 2) void gemm16_f16_kerne
                 for (int k = 0; k < 4; ++k) {
                     float v = acc[2 * i2 + h2][j][k] + (float)bq[k];
                     if (p.act == 1) v = v / (1.0f + __expf(-1.702f * v));
+                    else if (p.act == 2) v = gelu_erf(v);
                     h[k] = (_Float16)v;
                 }
                 *reinterpret_cast<half4_t*>(st + (16 * h2 + (lane & 15)) * PITCH + cl * 2) = h;
@@ -917,34 +1019,109 @@ __global__ __launch_bounds__(256) void gather_rows_f16_kernel(const _Float16* __
     }
 }
 
+// ---- the fp32 residual stream of the DINOv2 tower (dinov2_hip.HipDino) ---------------------------------------------------
+// layernorm_f16_kernel's sibling on an fp32 row with fp32 gamma / beta: one wave per row, lane l holds columns 8l .. 8l+7
+// and 512 + 8l .. (two 16-byte loads each), two passes over registers.  OutT = _Float16 feeds the next GEMM, float is the
+// tower's feature row.
+template <typename OutT>
+__global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restrict__ x, long long ldx, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, OutT* __restrict__ out, long long ldo,
+                                                            int rows, int C, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xr = x + (long long)row * ldx;
+    float v[2][8];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = 512 * k + 8 * lane;
+        float4_t lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
+        if (c < C) {
+            lo = *reinterpret_cast<const float4_t*>(xr + c);
+            hi = *reinterpret_cast<const float4_t*>(xr + c + 4);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[k][e] = lo[e]; v[k][4 + e] = hi[e]; }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s += v[k][e];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    const float mean = s / (float)C;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (512 * k + 8 * lane < C) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float d = v[k][e] - mean; q += d * d; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
+    const float rstd = 1.0f / sqrtf(q / (float)C + eps);
+    OutT* o = out + (long long)row * ldo;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int c = 512 * k + 8 * lane;
+        if (c < C) {
+            float y[8];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float4_t g = *reinterpret_cast<const float4_t*>(gamma + c + 4 * h);
+                const float4_t bb = *reinterpret_cast<const float4_t*>(beta + c + 4 * h);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[4 * h + e] = (v[k][4 * h + e] - mean) * rstd * g[e] + bb[e];
+            }
+            if constexpr (sizeof(OutT) == 2) {
+                half8_t r;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) r[e] = (_Float16)y[e];
+                *reinterpret_cast<half8_t*>(o + c) = r;
+            } else {
+                *reinterpret_cast<float4_t*>(o + c) = float4_t{y[0], y[1], y[2], y[3]};
+                *reinterpret_cast<float4_t*>(o + c + 4) = float4_t{y[4], y[5], y[6], y[7]};
+            }
+        }
+    }
+}
+
+// x[b][0] = cls + pos[0];  x[b][1 + p] = float(patch_out[b * NP + p]) + pos[1 + p]: fp16 rows of the patch GEMM, fp32 class
+// row and position table, fp32 tokens; one fp32 add per element
+__global__ __launch_bounds__(256) void vit_tokens_f32_kernel(const _Float16* __restrict__ patch_out, const float* __restrict__ cls,
+                                                             const float* __restrict__ pos, int B, int NP, int W,
+                                                             float* __restrict__ x) {
+    const long long total = (long long)B * (NP + 1) * W;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int c = (int)(e % W);
+        const long long t = e / W;
+        const int s = (int)(t % (NP + 1));
+        const long long b = t / (NP + 1);
+        const float base = s == 0 ? cls[c] : (float)patch_out[(b * NP + s - 1) * W + c];
+        x[e] = base + pos[(long long)s * W + c];
+    }
+}
+
+// out[i] = x[index[i]]  (fp32 rows of width W: the class token of every image)
+__global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float* __restrict__ x, const long long* __restrict__ index,
+                                                              long long n, int W, float* __restrict__ out) {
+    const long long total = n * W;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int c = (int)(e % W);
+        const long long i = e / W;
+        out[e] = x[index[i] * W + c];
+    }
+}
+
 inline int grid1d(long long total) {
     long long b = (total + 255) / 256;
     return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
 }
 
-}  // namespace
-
-extern "C" {
-
-int tise_gemm_f16(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* res_dev,
-                  int64_t ldr, void* out_dev, int64_t ldo, int m, int n, int k, int act, void* stream) {
-    // the kernels move a / w rows by 16-byte LDS-DMA, res / out in 16-byte pieces and bias in 8-byte pieces: strides
-    // below the row length and misaligned pointers are refused here, before anything reaches the device
-    if (!a_dev || !w_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || k % GM_BK != 0 || n % 8 != 0 || lda % 8 != 0 || ldw % 8 != 0 ||
-        ldo % 8 != 0 || (res_dev && ldr % 8 != 0) || (act != 0 && act != 1) || lda < k || ldw < k || ldo < n ||
-        (res_dev && ldr < n) ||
-        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev) | reinterpret_cast<uintptr_t>(out_dev) |
-          reinterpret_cast<uintptr_t>(res_dev)) & 15) != 0 ||
-        (reinterpret_cast<uintptr_t>(bias_dev) & 7) != 0)
-        return TISE_ERR_INVALID_ARG;
-    if (m == 0) return TISE_OK;
-    GemmArgs p;
-    p.a = reinterpret_cast<const _Float16*>(a_dev); p.lda = lda;
-    p.w = reinterpret_cast<const _Float16*>(w_dev); p.ldw = ldw;
-    p.bias = reinterpret_cast<const _Float16*>(bias_dev);
-    p.res = reinterpret_cast<const _Float16*>(res_dev); p.ldr = ldr;
-    p.out = reinterpret_cast<_Float16*>(out_dev); p.ldo = ldo;
-    p.M = m; p.N = n; p.K = k; p.act = act;
+// the instance rule and the launch, the same for every epilogue (p.M > 0)
+template <int EPI>
+int gemm_launch(const GemmArgs& p, void* stream) {
+    const int m = p.M, n = p.N;
     const long long tiles = (long long)((m + 127) / 128) * ((n + 127) / 128);
     if (tiles > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
     // TISE_GEMM_BIG: 0 never, 1 (default) by the rule below, 2 always -- the A/B switch of tools/clip_gemm_probe.py
@@ -956,18 +1133,21 @@ int tise_gemm_f16(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw
     // SLOWER (its 128 x 64 wave tile needs the slice-1 fragments re-loaded row block by row block to stay inside 256
     // registers, which serialises its issue stream), so it stays on 32x32x16
     static const int shape = [] { const char* e = getenv("TISE_GEMM_SHAPE"); return e ? atoi(e) : 0; }();
-    const bool big = big_mode == 2 || (big_mode == 1 && tiles_big >= 768);
+    // act 2 stays on the 128 x 128 kernel under the default rule: erff is some 40 VALU instructions per element, which a
+    // second workgroup on the CU hides under its MFMAs and the one-per-CU kernel cannot (DINOv2 ViT-L/14 fc1, 12 850 x 4096 x
+    // 1024: 209 us on the 256 x 256 kernel; the whole tower 14.88 -> 14.12 ms, profiles/r15a_dinov2_probe.txt)
+    const bool big = big_mode == 2 || (big_mode == 1 && tiles_big >= 768 && p.act != 2);
     if (shape == 16 || (shape == 0 && !big)) {
         constexpr int lds_big = 2 * (256 * 128 + 256 * 128), lds_small = 2 * (128 * 128 + 128 * 128);
         static std::atomic<unsigned long long> attr16{0};
         if (tise_first_use_on_this_device(attr16)) {
-            TISE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm16_f16_kernel<true>),
+            TISE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm16_f16_kernel<true, EPI>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_big));
-            TISE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm16_f16_kernel<false>),
+            TISE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm16_f16_kernel<false, EPI>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_small));
         }
-        if (big) hipLaunchKernelGGL(gemm16_f16_kernel<true>, dim3((unsigned)tiles_big), dim3(512), lds_big, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(gemm16_f16_kernel<false>, dim3((unsigned)tiles), dim3(256), lds_small, (hipStream_t)stream, p);
+        if (big) hipLaunchKernelGGL((gemm16_f16_kernel<true, EPI>), dim3((unsigned)tiles_big), dim3(512), lds_big, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL((gemm16_f16_kernel<false, EPI>), dim3((unsigned)tiles), dim3(256), lds_small, (hipStream_t)stream, p);
         TISE_LAUNCH_CHECK();
         return TISE_OK;
     }
@@ -975,13 +1155,122 @@ int tise_gemm_f16(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw
         constexpr int lds_big = 2 * (256 * 128 + 256 * 128);
         static std::atomic<unsigned long long> attr_set{0};
         if (tise_first_use_on_this_device(attr_set))
-            TISE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_big_kernel),
+            TISE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_big_kernel<EPI>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds_big));
-        hipLaunchKernelGGL(gemm_f16_big_kernel, dim3((unsigned)tiles_big), dim3(512), lds_big, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(gemm_f16_big_kernel<EPI>, dim3((unsigned)tiles_big), dim3(512), lds_big, (hipStream_t)stream, p);
         TISE_LAUNCH_CHECK();
         return TISE_OK;
     }
-    hipLaunchKernelGGL(gemm_f16_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(gemm_f16_kernel<EPI>, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, p);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+// tise_gemm_f16 (act 0 .. 1, as it always was) and tise_gemm_f16_act (act 0 .. 2): one check, one launch
+int gemm_f16_entry(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* res_dev,
+                   int64_t ldr, void* out_dev, int64_t ldo, int m, int n, int k, int act, int max_act, void* stream) {
+    // the kernels move a / w rows by 16-byte LDS-DMA, res / out in 16-byte pieces and bias in 8-byte pieces: strides
+    // below the row length and misaligned pointers are refused here, before anything reaches the device
+    if (!a_dev || !w_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || k % GM_BK != 0 || n % 8 != 0 || lda % 8 != 0 || ldw % 8 != 0 ||
+        ldo % 8 != 0 || (res_dev && ldr % 8 != 0) || act < 0 || act > max_act || lda < k || ldw < k || ldo < n ||
+        (res_dev && ldr < n) ||
+        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev) | reinterpret_cast<uintptr_t>(out_dev) |
+          reinterpret_cast<uintptr_t>(res_dev)) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(bias_dev) & 7) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (m == 0) return TISE_OK;
+    GemmArgs p = {};
+    p.a = reinterpret_cast<const _Float16*>(a_dev); p.lda = lda;
+    p.w = reinterpret_cast<const _Float16*>(w_dev); p.ldw = ldw;
+    p.bias = reinterpret_cast<const _Float16*>(bias_dev);
+    p.res = reinterpret_cast<const _Float16*>(res_dev); p.ldr = ldr;
+    p.out = reinterpret_cast<_Float16*>(out_dev); p.ldo = ldo;
+    p.M = m; p.N = n; p.K = k; p.act = act;
+    return gemm_launch<EPI_F16>(p, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tise_gemm_f16(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* res_dev,
+                  int64_t ldr, void* out_dev, int64_t ldo, int m, int n, int k, int act, void* stream) {
+    return gemm_f16_entry(a_dev, lda, w_dev, ldw, bias_dev, res_dev, ldr, out_dev, ldo, m, n, k, act, 1, stream);
+}
+
+int tise_gemm_f16_act(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* res_dev,
+                      int64_t ldr, void* out_dev, int64_t ldo, int m, int n, int k, int act, void* stream) {
+    return gemm_f16_entry(a_dev, lda, w_dev, ldw, bias_dev, res_dev, ldr, out_dev, ldo, m, n, k, act, 2, stream);
+}
+
+int tise_gemm_f16_res32(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* scale_dev,
+                        const void* res32_dev, int64_t ldr, void* out32_dev, int64_t ldo, int m, int n, int k, void* stream) {
+    // a / w / bias as tise_gemm_f16; res32 / out32 move in 16-byte pieces of four floats (rows 16-byte aligned: strides % 4),
+    // scale in 16-byte pieces.  out32 == res32 (same stride) is the tower's in-place update; any other overlap is the caller's.
+    if (!a_dev || !w_dev || !res32_dev || !out32_dev || m < 0 || n <= 0 || k <= 0 || k % GM_BK != 0 || n % 8 != 0 || lda % 8 != 0 ||
+        ldw % 8 != 0 || ldr % 4 != 0 || ldo % 4 != 0 || lda < k || ldw < k || ldr < n || ldo < n ||
+        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev) | reinterpret_cast<uintptr_t>(res32_dev) |
+          reinterpret_cast<uintptr_t>(out32_dev) | reinterpret_cast<uintptr_t>(scale_dev)) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(bias_dev) & 7) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (m == 0) return TISE_OK;
+    GemmArgs p = {};
+    p.a = reinterpret_cast<const _Float16*>(a_dev); p.lda = lda;
+    p.w = reinterpret_cast<const _Float16*>(w_dev); p.ldw = ldw;
+    p.bias = reinterpret_cast<const _Float16*>(bias_dev);
+    p.scale = reinterpret_cast<const float*>(scale_dev);
+    p.res32 = reinterpret_cast<const float*>(res32_dev); p.ldr32 = ldr;
+    p.out32 = reinterpret_cast<float*>(out32_dev); p.ldo32 = ldo;
+    p.M = m; p.N = n; p.K = k; p.act = 0;
+    return gemm_launch<EPI_RES32>(p, stream);
+}
+
+int tise_layernorm_f32(const void* x_dev, int64_t ldx, const void* gamma_dev, const void* beta_dev, void* out_dev, int64_t ldo,
+                       int64_t rows, int C, float eps, int out_f32, void* stream) {
+    // x, gamma, beta (and an fp32 out) move as 16-byte pieces of four floats, an fp16 out as 16-byte pieces of eight halves
+    const int64_t omul = out_f32 ? 4 : 8;
+    if (!x_dev || !gamma_dev || !beta_dev || !out_dev || rows < 0 || C <= 0 || C > 1024 || C % 8 != 0 || ldx % 4 != 0 || ldo % omul != 0 ||
+        ldx < C || ldo < C || (out_f32 != 0 && out_f32 != 1) ||
+        ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(gamma_dev) |
+          reinterpret_cast<uintptr_t>(beta_dev)) & 15) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (rows == 0) return TISE_OK;
+    if ((rows + 3) / 4 > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    const float* x = reinterpret_cast<const float*>(x_dev);
+    const float* g = reinterpret_cast<const float*>(gamma_dev);
+    const float* b = reinterpret_cast<const float*>(beta_dev);
+    if (out_f32) hipLaunchKernelGGL(layernorm_f32_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, g, b,
+                                    reinterpret_cast<float*>(out_dev), ldo, (int)rows, C, eps);
+    else hipLaunchKernelGGL(layernorm_f32_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, g, b,
+                            reinterpret_cast<_Float16*>(out_dev), ldo, (int)rows, C, eps);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+int tise_vit_tokens_f32(const void* patch_out_dev, const void* class_tok_dev, const void* pos_emb_dev, int batch, int n_patches,
+                        int width, void* x_dev, void* stream) {
+    if (!patch_out_dev || !class_tok_dev || !pos_emb_dev || !x_dev || batch < 0 || n_patches <= 0 || width <= 0 ||
+        (reinterpret_cast<uintptr_t>(patch_out_dev) & 1) != 0 ||
+        ((reinterpret_cast<uintptr_t>(class_tok_dev) | reinterpret_cast<uintptr_t>(pos_emb_dev) | reinterpret_cast<uintptr_t>(x_dev)) & 3) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (batch == 0) return TISE_OK;
+    hipLaunchKernelGGL(vit_tokens_f32_kernel, dim3(grid1d((long long)batch * (n_patches + 1) * width)), dim3(256), 0,
+                       (hipStream_t)stream, reinterpret_cast<const _Float16*>(patch_out_dev), reinterpret_cast<const float*>(class_tok_dev),
+                       reinterpret_cast<const float*>(pos_emb_dev), batch, n_patches, width, reinterpret_cast<float*>(x_dev));
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+int tise_gather_rows_f32(const void* x_dev, const int64_t* index_dev, int64_t n, int width, void* out_dev, void* stream) {
+    if (!x_dev || !index_dev || !out_dev || n < 0 || width <= 0 ||
+        ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 3) != 0 ||
+        (reinterpret_cast<uintptr_t>(index_dev) & 7) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    hipLaunchKernelGGL(gather_rows_f32_kernel, dim3(grid1d(n * width)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float*>(x_dev), reinterpret_cast<const long long*>(index_dev), (long long)n, width,
+                       reinterpret_cast<float*>(out_dev));
     TISE_LAUNCH_CHECK();
     return TISE_OK;
 }

@@ -35,6 +35,10 @@ _KINDS = {
     "clip": ("CLIP ViT-B/32", lambda: [os.path.expanduser(os.path.join("~", ".cache", "clip", "ViT-B-32.pt"))]),
     # the tower of the published CMMD figures (cmmd --tower ViT-L/14@336), under the name the OpenAI package caches it
     "clip-l14-336": ("CLIP ViT-L/14@336", lambda: [os.path.expanduser(os.path.join("~", ".cache", "clip", "ViT-L-14-336px.pt"))]),
+    # the towers of FD-DINOv2 (fd_dinov2 --arch), under the names torch.hub caches the released files
+    "dinov2-vits14": ("DINOv2 ViT-S/14", lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "dinov2_vits14_pretrain.pth")]),
+    "dinov2-vitb14": ("DINOv2 ViT-B/14", lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "dinov2_vitb14_pretrain.pth")]),
+    "dinov2-vitl14": ("DINOv2 ViT-L/14", lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "dinov2_vitl14_pretrain.pth")]),
 }
 
 
