@@ -74,10 +74,26 @@ def instance_for(m, n, env=None, act=0):
 L_GELU_ERF = 1.13                    # the largest |GELU'| (1.1289 at x = sqrt 2)
 
 
+def check_act2(a, w, b, out):
+    """(ratio, largest |x|) of an act = 2 launch on random operands against fp64: |h - ref| <= (1 + 2^-8)[u16 |ref| + eta16 + L E
+    + 0.5 |x| K_ACT 2^-24 + u32 |ref|] with L = 1.13 the largest |GELU'| and E the accumulator bound (``b`` may be None).  A
+    function of the operands: run_gelu_dispatch_edge and the tower audit (tests/_tower_audit.py) share it."""
+    import torch
+    k = a.shape[1]
+    x = a.double() @ w.double().t()
+    mag = a.double().abs() @ w.double().abs().t()
+    if b is not None:
+        x = x + b.double()
+        mag = mag + b.double().abs()
+    E = C_ACC * (k + 1) * 2.0 ** -24 * mag
+    ref = 0.5 * x * (1 + torch.special.erf(x * 0.5 ** 0.5))
+    bound = (1 + 2.0 ** -8) * (U16 * ref.abs() + ETA16 + L_GELU_ERF * E + 0.5 * x.abs() * K_ACT * 2.0 ** -24 + U32 * ref.abs())
+    return float(((out.double() - ref).abs() / bound).max().item()), float(x.abs().max().item())
+
+
 def run_gelu_dispatch_edge(dev):
     """act = 2 with bias at 6141 x 8184 x 64 = 768 tiles of 256 x 256, where the default rule sends every other launch to a
-    256 x 256 kernel and this one not: random operands against fp64, |h - ref| <= (1 + 2^-8)[u16 |ref| + eta16 + L E + 0.5 |x|
-    K_ACT 2^-24 + u32 |ref|] with L = 1.13 the largest |GELU'| and E the accumulator bound."""
+    256 x 256 kernel and this one not: random operands against fp64 within check_act2's bound."""
     import torch
     from tise_toolbox_amd import clip_hip
     m, n, k = 6141, 8184, 64
@@ -87,13 +103,10 @@ def run_gelu_dispatch_edge(dev):
     b = (torch.randn(n, generator=g, device=dev) * 0.3).half()
     out = clip_hip.gemm(a, w, b, act=2)
     again = clip_hip.gemm(a, w, b, act=2)
-    x = a.double() @ w.double().t() + b.double()
-    E = C_ACC * (k + 1) * 2.0 ** -24 * (a.double().abs() @ w.double().abs().t() + b.double().abs())
-    ref = 0.5 * x * (1 + torch.special.erf(x * 0.5 ** 0.5))
-    bound = (1 + 2.0 ** -8) * (U16 * ref.abs() + ETA16 + L_GELU_ERF * E + 0.5 * x.abs() * K_ACT * 2.0 ** -24 + U32 * ref.abs())
-    return dict(instance=instance_for(m, n, act=2), ratio=float(((out.double() - ref).abs() / bound).max().item()),
+    ratio, spread = check_act2(a, w, b, out)
+    return dict(instance=instance_for(m, n, act=2), ratio=ratio,
                 finite=bool(torch.isfinite(out).all().item()), repeat_equal=bool(torch.equal(out, again)),
-                spread=float(x.abs().max().item()))
+                spread=spread)
 
 
 def make_res32_inputs(case, dev):

@@ -160,3 +160,64 @@ def test_cli_refusals_that_need_no_gpu(tmp_path):
         assert fd_dinov2.arch_info(arch) == (dims, "dinov2-" + arch, "dinov2-" + arch)
         assert weights._KINDS["dinov2-" + arch][1]()[0].endswith(f"hub/checkpoints/dinov2_{arch}_pretrain.pth")
     assert dm.RESOLUTION == 224
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def _evaluate(model, x, mode):
+    """The module's forward on the CPU: "a" as it is (fp32); "b" with every Linear's (and the patch convolution's) operands and
+    output rounded to fp16, and the attention's and the GELU's outputs, which is what torch.autocast(fp16) rounds -- LayerNorm,
+    LayerScale and the residual stream stay fp32; "c" = "b" with the stream also rounded to fp16 after each residual add, which
+    is clip_hip.HipTowers' arithmetic.  -> (features, the stream after the last block)."""
+    r = (lambda t: t.half().float()) if mode != "a" else (lambda t: t)
+    s = (lambda t: t.half().float()) if mode == "c" else (lambda t: t)
+    lin = lambda t, l: r(F.linear(r(t), r(l.weight), r(l.bias)))
+    pe = model.patch_embed.proj
+    t = r(F.conv2d(r(x), r(pe.weight), r(pe.bias), stride=model.patch)).flatten(2).transpose(1, 2)
+    t = torch.cat([model.cls_token.expand(t.shape[0], -1, -1), t], 1) + model.pos
+    for blk in model.blocks:
+        y = F.layer_norm(t, t.shape[-1:], blk.norm1.weight, blk.norm1.bias, blk.norm1.eps)
+        b, n, w = y.shape
+        q, k, v = lin(y, blk.attn.qkv).view(b, n, 3, blk.attn.heads, w // blk.attn.heads).permute(2, 0, 3, 1, 4)
+        o = r(F.scaled_dot_product_attention(q, k, v)).transpose(1, 2).reshape(b, n, w)
+        t = s(t + blk.ls1.gamma * lin(o, blk.attn.proj))
+        y = F.layer_norm(t, t.shape[-1:], blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
+        t = s(t + blk.ls2.gamma * lin(r(F.gelu(lin(y, blk.mlp.fc1))), blk.mlp.fc2))
+    return F.layer_norm(t, t.shape[-1:], model.norm.weight, model.norm.bias, model.norm.eps)[:, 0], t
+
+
+def _one_minus_cos(a, b):
+    a, b = a.double(), b.double()
+    return (1 - (a * b).sum(-1) / (a.norm(dim=-1) * b.norm(dim=-1))).max().item()
+
+
+def test_an_fp16_stream_misses_the_end_to_end_condition_on_outliers():
+    """The condition of tests/test_gpu_dinov2.py has teeth on the inputs the fp32 stream exists for.  The tiny 154-pixel tower with
+    tests/_tower_audit.make_outliers_ (+-3000 on channels 5 and 77 of two patch tokens' position rows, +-50 on the class row's,
+    block 0's fc2 rows of those channels x 40) on the 3 seeded images of tests/test_gpu_tower_launches.py, three CPU evaluations
+    (_evaluate): (a) the fp32 module, (b) fp16-rounded Linear operands and outputs = what autocast rounds, (c) = (b) with the
+    stream rounded to fp16 after each residual add.  Asserted: 1 - cos(c, a) >= 10 x (1 - cos(b, a)), worst image.
+
+    Measured (worst of 3 images): 1 - cos(b, a) = 3.033e-10, 1 - cos(c, a) = 6.949e-08, ratio 229; evaluation "a" equals the
+    module's own forward to 2e-16.  The same tower WITHOUT outliers: 1.405e-07 and 2.500e-07, ratio 1.8 -- two layers of O(1)
+    activations do not tell the two streams apart, which is why the suite never did.
+
+    How the magnitudes were chosen (on the CPU, from the references alone): everything that passes a LayerNorm is rounded to
+    fp16 as a Linear operand in (b) as well, so in a 2-layer tower an fp16 stream can only lose what reaches the features
+    directly: the class row.  With 3000 on the class row too the two channels are all the final LayerNorm sees of it (every
+    other feature is ~1e-3 of them) and (b) drops to 1e-14, the rounding noise of fp32 features, where no condition can be
+    tested (ratio 2e6); with no outlier on the class row the ratio is 3.4 (3.1e-07 / 1.05e-06).  At +-50 the class row's outlier
+    channels are 8 sigma of its LayerNorm and an fp16 ulp of them (2^-5) is 1e2 x the fp16 rounding of an O(0.1) update.
+    The construction itself is asserted: the fp32 stream reaches 1e3 with its median below 10."""
+    from tests import _tower_audit as A
+    from tise_toolbox_amd import dinov2_model as dm
+    model = A.make_outliers_(dm.build_dinov2(None, 0, A.TINY154))
+    x = A.seeded_images(3, 154, 5, "cpu").half().float()
+    with torch.no_grad():
+        fa, stream = _evaluate(model, x, "a")
+        fb, fc = _evaluate(model, x, "b")[0], _evaluate(model, x, "c")[0]
+        assert _one_minus_cos(model(x), fa) < 1e-12                        # _evaluate restates the module
+    assert stream.abs().max() >= 1e3 and stream.abs().median() < 10
+    eb, ec = _one_minus_cos(fb, fa), _one_minus_cos(fc, fa)
+    print(f"1 - cos against the fp32 module: autocast restatement {eb:.3e}, fp16 stream {ec:.3e}, ratio {ec / eb:.1f}")
+    assert torch.isfinite(fc).all() and eb > 1e-11                         # well above the noise of fp32 features (1e-14)
+    assert ec >= 10 * eb, (ec, eb)

@@ -121,9 +121,10 @@ def _ln32_check(x, gamma, beta, eps, got):
     return ((got.double() - ref).abs() / bound).max().item()
 
 
-@pytest.mark.parametrize("C", [8, 384, 1024])
+@pytest.mark.parametrize("C", [8, 64, 384, 768, 1024])
 def test_layernorm_f32_matches_fp64_per_element(cuda_device, C):
-    """C = 8 (idle lanes), 384 (ViT-S: the first half partly used), 1024 (both halves full); rows = 1, 4, 5 (one workgroup
+    """C = 8 (idle lanes), 64 (one lane group exactly), 384 (ViT-S: the first half partly used), 768 (ViT-B: the second half
+    partly used), 1024 (both halves full); rows = 1, 4, 5 (one workgroup
     exactly, and a second one with three idle waves); fp16 and fp32 output; strided input and output with the columns beside the
     output untouched; a row with a common offset of 1000, a small-variance row (eps = 1e-6 matters), a constant row (output =
     beta exactly: the constant has 11 significant bits, so its fp32 sum over C <= 1024 columns is exact), and a row of O(1)
