@@ -35,7 +35,9 @@ KNOWN = {
     "tise_avgpool3_excl_bias_relu_split_nhwc": ((0, 7), (8,)),
     "tise_split_mean_nhwc": ((0,), (4,)),
     "tise_split_mean_both_nhwc": ((0,), (4, 5)),
+    "tise_split_tap_rows": ((0,), (6,)),
 }
+TAP = "tise_split_tap_rows"      # the one launch that comes from device.py (device._ptr), not from trunk.py (trunk._p)
 STEMS = ("tise_stem_conv3x3s2_split", "tise_stem_conv3x3s2_split_u8", "tise_stem_conv3x3s2_split_u8_mfma")
 
 
@@ -79,7 +81,8 @@ def bits(t):
 class Launch:
     """One kernel launch: ``name``, the cloned ``inputs``, ``dsts`` = [(before, after)] per distinct destination tensor,
     and for a convolution ``conv`` (the SplitConv), ``segs`` = [(c0, c1, destination index, off, mode)], ``kw``, ``code``
-    and ``args`` (the ConvArgs fields as passed); for the others ``ints`` = the call's integer arguments by position."""
+    and ``args`` (the ConvArgs fields as passed); for the others ``ints`` = the call's integer arguments by position.  The
+    tap also keeps ``inputs_after``: its input as the launch left it."""
 
     def __init__(self, name):
         self.name = name
@@ -88,6 +91,7 @@ class Launch:
         self.ints = {}
         self.in_ptr = None
         self.dst_ptrs = []
+        self.inputs_after = None
 
     def __repr__(self):
         if self.conv is not None:
@@ -127,17 +131,21 @@ class Recorder:
         return t.detach().clone()
 
     def __enter__(self):
-        from tise_toolbox_amd import _lib, trunk
+        from tise_toolbox_amd import _lib, device, trunk
         from tise_toolbox_amd.conv_split import SplitConv
         rec = self
-        self._orig = (SplitConv.__call__, _lib.call, trunk._p)
-        orig_call, orig_lib, orig_p = self._orig
+        self._orig = (SplitConv.__call__, _lib.call, trunk._p, device._ptr)
+        orig_call, orig_lib, orig_p, orig_ptr = self._orig
         self._kw = keep_weights()
         self._kw.__enter__()
 
         def p(t):                                                # trunk._p: remember which tensor a raw pointer is
             rec._tensors[t.data_ptr()] = t
             return orig_p(t)
+
+        def ptr(t):                                              # device._ptr: the same for the tap's wrapper
+            rec._tensors[t.data_ptr()] = t
+            return orig_ptr(t)
 
         def conv_call(self, xs, segs, pooled_input=False, **kw):   # signature handling as tools/split_layer_probe.py
             fr = dict(conv=self, segs=list(segs), kw=dict(kw, pooled_input=pooled_input), launch=None)
@@ -190,16 +198,18 @@ class Recorder:
             L.in_ptr, L.dst_ptrs = args[ins[0]].value, [t.data_ptr() for t in dst]
             r = orig_lib(name, *args)
             L.dsts = [(b, rec._clone(t)) for b, t in zip(before, dst)]
+            if name == TAP:
+                L.inputs_after = [rec._clone(tensor(i)) for i in ins]
             rec.launches.append(L)
             return r
 
-        SplitConv.__call__, _lib.call, trunk._p = conv_call, lib_call, p
+        SplitConv.__call__, _lib.call, trunk._p, device._ptr = conv_call, lib_call, p, ptr
         return self
 
     def __exit__(self, *exc):
-        from tise_toolbox_amd import _lib, trunk
+        from tise_toolbox_amd import _lib, device, trunk
         from tise_toolbox_amd.conv_split import SplitConv
-        SplitConv.__call__, _lib.call, trunk._p = self._orig
+        SplitConv.__call__, _lib.call, trunk._p, device._ptr = self._orig
         self._kw.__exit__(*exc)
         self._tensors.clear()
 
@@ -383,6 +393,33 @@ def check_mean(L):
     return res
 
 
+def check_tap(L, trunk):
+    """tise_split_tap_rows: the scalars are the trunk's SPATIAL_*; row i of the destination is, bit for bit,
+    merge(input)[i, :, :, c0:c0+nc] flattened in h, w, c order (hi + lo * 2**-11 is exact in fp64, so its fp32 rounding is
+    the kernel's one fp32 addition) and exactly +0 from column hw * nc on; the input's bits are what they were.  Returns the
+    number of values compared."""
+    i = L.ints
+    n, hw, C, c0, nc, ld = i[1], i[2], i[3], i[4], i[5], i[7]
+    x = L.inputs[0]
+    what = f"tap {L!r}"
+    assert (c0, nc, ld) == (trunk.SPATIAL_C0, trunk.SPATIAL_NC, trunk.SPATIAL_LD), \
+        f"{what}: channels [{c0}, {c0 + nc}) into rows of {ld}, the trunk states [{trunk.SPATIAL_C0}, {trunk.SPATIAL_C0 + trunk.SPATIAL_NC}) and {trunk.SPATIAL_LD}"
+    assert x.dtype == torch.float16 and x.dim() == 4 and x.shape[0] == n and x.shape[1] * x.shape[2] == hw and x.shape[3] == 2 * C, \
+        f"{what}: input {tuple(x.shape)} is not the (n, h, w, 2C) the scalars state"
+    assert 0 <= c0 and c0 + nc <= C and hw * nc <= ld, what
+    before, after = L.dsts[0]
+    assert tuple(after.shape) == (n, ld) and after.dtype == torch.float32, f"{what}: destination {tuple(after.shape)}"
+    used = hw * nc
+    want = merge64(x)[..., c0:c0 + nc].float().reshape(n, used)
+    bad = bits(after[:, :used]) != bits(want)
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} of {bad.numel()} values are not merge(input)[..., {c0}:{c0 + nc}] in h, w, c order " \
+                                f"(first at row, column {tuple(int(v) for v in bad.nonzero()[0])})"
+    pad = bits(after[:, used:])
+    assert not bool((pad != 0).any()), f"{what}: {int((pad != 0).sum())} padding columns from {used} on are not +0"
+    assert L.inputs_after is not None and torch.equal(bits(L.inputs_after[0]), bits(x)), f"{what}: the launch changed its input"
+    return bad.numel()
+
+
 def check_launch(L, trunk):
     """Dispatch on the launch's kind; returns (kind, figure) for the printed table."""
     if L.conv is not None:
@@ -390,6 +427,8 @@ def check_launch(L, trunk):
         return ("fc" if fc else "conv"), check_conv(L, fc)
     if L.name in STEMS:
         return "stem", check_stem(L, trunk)
+    if L.name == TAP:
+        return "tap", check_tap(L, trunk)
     if "pool" in L.name:
         return "pool", check_pool(L)
     return "mean", check_mean(L)
@@ -418,13 +457,24 @@ def own_rows(L):
 def check_assembly(launches):
     """The segment lists of trunk.py as a whole: every element of every tensor a launch reads was written by exactly one
     earlier launch -- a segment that lands 8 channels off inside a concat buffer overlaps its neighbour's slice (reported at
-    that launch) and leaves a gap (reported at the first launch that reads the buffer).  Returns the list of failures.
+    that launch) and leaves a gap (reported at the first launch that reads the buffer).  The tap reads channels
+    [c0, c0 + nc) of its source only: those must have been written (once: an overlap is reported at its writer) by earlier
+    launches -- a tap in front of the block that fills them, or on a buffer no launch wrote, is reported at the tap; it does
+    not close the buffer to further writers.  Returns the list of failures.
     (Two whole branches of equal width written to each other's slices would pass here: every later layer then sees its
     input channels permuted, which the end-to-end tests catch at any tolerance.)"""
     state, fails = {}, []                                         # data pointer -> [written mask, sealed by a reader]
     for k, L in enumerate(launches):
         st = state.get(L.in_ptr)
-        if st is not None:
+        if L.name == TAP:
+            i = L.ints
+            need = raw_mask(i[3], i[4], i[4] + i[5], True, L.inputs[0].device)
+            if st is None or st[0].numel() != need.numel():
+                fails.append(f"launch {k}: tap {L!r} reads a tensor no earlier launch has written")
+            elif not bool(st[0][need].all()):
+                fails.append(f"launch {k}: tap {L!r} reads {int((~st[0][need]).sum())} raw row elements of channels "
+                             f"[{i[4]}, {i[4] + i[5]}) that no earlier launch has written")
+        elif st is not None:
             if not bool(st[0].all()) and not st[1]:
                 fails.append(f"launch {k}: {L!r} reads a tensor with {int((~st[0]).sum())} raw row elements no launch has written")
             st[1] = True

@@ -8,6 +8,7 @@ import ctypes
 import functools
 import hashlib
 import os
+import time
 
 import numpy as np
 import pytest
@@ -70,6 +71,8 @@ SHAPES = [
     (20, 24, 17, 19), (20, 24, 15, 19), (40, 24, 33, 7), (40, 24, 31, 7),  # oh one more / one less than a multiple of the row tile (16)
     (1, 1, 1, 1), (1, 1, 37, 41), (2, 3, 5, 4),
     (256, 256, 299, 299),    # the flagship shape (16-byte loads, 19 row tiles)
+    (37, 53, 41, 52), (37, 53, 36, 52),   # w / ow just above 1: 7 taps on x, the first size past the register-coefficient border
+                                          # (ksx <= 5) of hpass; the vertical pass has 5 taps (up) and 7 (just below 1) beside it
 ]
 
 
@@ -89,7 +92,8 @@ def test_batch_kernel_equals_restatement(cuda_device, shape):
         assert np.array_equal(_run(cuda_device, x, (oh, ow), **RAW), x.astype(np.float32))
 
 
-@pytest.mark.parametrize("shape", [(37, 53, 41, 37), (64, 2000, 37, 100), (2000, 64, 37, 100), (9, 5, 11, 13), (40, 24, 33, 7)],
+@pytest.mark.parametrize("shape", [(37, 53, 41, 37), (64, 2000, 37, 100), (2000, 64, 37, 100), (9, 5, 11, 13), (40, 24, 33, 7),
+                                   (18, 26, 9, 13)],         # bilinear at scale 2: support 2, 5 taps, the register path while shrinking
                          ids=lambda s: "%dx%d-%dx%d" % s)
 def test_batch_kernel_bilinear(cuda_device, shape):
     h, w, oh, ow = shape
@@ -114,10 +118,12 @@ def test_clip_and_affine(cuda_device):
         _same_bits(_run(cuda_device, x, (oh, ow), clip=clip, sub=sub, div=div), ref.affine(raw, clip, sub, div), f"{clip} {sub} {div}")
 
 
-@pytest.mark.parametrize("shape", [(64, 20, 17, 31), (9, 7, 20, 18), (300, 2, 37, 41), (37, 53, 37, 41), (37, 53, 41, 53)],
+@pytest.mark.parametrize("shape", [(64, 20, 17, 31), (9, 7, 20, 18), (300, 2, 37, 41), (37, 53, 37, 41), (37, 53, 41, 53),
+                                   (37, 53, 41, 52), (37, 53, 36, 52)],
                          ids=lambda s: "%dx%d-%dx%d" % s)
 def test_vertical_first_order(cuda_device, shape):
-    """order = 1 at any shape is the restatement's vertical-first result (down, up, a skipped pass on either axis)."""
+    """order = 1 at any shape is the restatement's vertical-first result (down, up, a skipped pass on either axis, and the
+    7-tap horizontal pass, the first past the register-coefficient border, as the FINAL pass on float32 rows)."""
     h, w, oh, ow = shape
     cases = [("rand", 120), ("bw", 121), ("rand", 122)]
     x = np.stack([ref.content(k, s, h, w) for k, s in cases])
@@ -216,6 +222,201 @@ def test_ragged_refuses_before_enqueueing(cuda_device):
         device.resize_f32(wide.unsqueeze(0), (4, 4))
     with pytest.raises(ValueError):
         device.resize_ragged_f32([], (4, 4))
+
+
+# ---- launch edges and plan paths (the u8 kernel's are pinned in test_gpu_resize.py; this file's kernel has its own copy) ---------
+def test_grid_limit_of_65535_images(cuda_device):
+    """The image index of tise_resize_f32 is blockIdx.y: 65 535 sources are accepted, 65 536 refused with nothing written.
+    A 1 x 1 source has one tap of weight 1.0 on each axis, so every output pixel is the source pixel after clip and affine:
+    held to the restatement on a sample of images, and to that closed form (two fp32 operations, ref.affine) on every value
+    of all 65 535, both layouts and both filters."""
+    from tise_toolbox_amd import _lib
+    n = 65535
+    rng = np.random.default_rng(65535)
+    imgs = rng.integers(0, 256, (n + 1, 1, 1, 3), dtype=np.uint8)
+    clip = (10.0, 200.0)                                          # both clips act on some of the bytes
+    want = ref.affine(np.broadcast_to(imgs[:n].astype(np.float32), (n, 2, 2, 3)), clip, 128.0, 128.0)
+    for filt in ref.FILTERS:
+        for k in (0, 1, 4097, n - 1):
+            _same_bits(ref.clean_input(imgs[k], (2, 2), filt, clip=clip), want[k], f"restatement, image {k} {filt}")
+        for nhwc in (True, False):
+            _same_bits(_run(cuda_device, imgs[:n], (2, 2), filt, nhwc=nhwc, clip=clip), want, f"{filt} nhwc={nhwc}")
+    src = torch.as_tensor(imgs, device=cuda_device)
+    dst = torch.full((n + 1, 2, 2, 3), float("nan"), dtype=torch.float32, device=cuda_device)
+    for filt in (0, 1):
+        st = _lib.load().tise_resize_f32(ctypes.c_void_p(src.data_ptr()), n + 1, 1, 1, ctypes.c_void_p(dst.data_ptr()), 2, 2, 1, filt,
+                                         0.0, 255.0, 128.0, 128.0, 0, _stream())
+        assert st == _lib.TISE_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert torch.isnan(dst).all()                                # nothing ran
+
+
+RAGGED_CHUNK = 4096        # images per launch of tise_resize_ragged_f32 (csrc/resize_f32.hip)
+
+# Nine base images per output size, of RAGGED's kinds.  -> (5, 7): (2000, 64) and (64, 2000) are refused there (no tile fits
+# LDS), so the streamed kind is (800, 64) (641 staged rows: 123 KB streamed, 177 KB with float32 rows) and the many-tap kind
+# (16, 2000) (1145 taps per window, 97 KB).
+BASES = {
+    (37, 100): RAGGED,
+    (5, 7): [(3, 4), (16, 2000), (800, 64), (4000, 9), (5, 11), (9, 7), (5, 7), (1, 1), (9, 5)],
+}
+OVER_48K = {(37, 100): 1, (5, 7): 2}       # a base whose workgroup needs more than 48 KB of LDS: (64, 2000) / (800, 64)
+
+
+@functools.lru_cache(maxsize=None)
+def _bases(out_hw):
+    """The nine base images of an output size and the restatement's network input of each, computed once and shared."""
+    imgs = [ref.content("bw" if i % 3 == 1 else "rand", 400 + i, h, w) for i, (h, w) in enumerate(BASES[out_hw])]
+    want = np.stack([ref.clean_input(im, out_hw) for im in imgs])                  # order: Pillow's rule
+    want.setflags(write=False)
+    return imgs, want
+
+
+def _base_views(dev, imgs):
+    """The base images as views of ONE device buffer, each one byte after the other's end: some at odd addresses."""
+    flat = torch.empty(sum(im.size + 1 for im in imgs), dtype=torch.uint8, device=dev)
+    views, pos = [], 1
+    for im in imgs:
+        v = flat[pos:pos + im.size].view(im.shape)
+        v.copy_(torch.as_tensor(im))
+        views.append(v)
+        pos += im.size + 1
+    assert any(v.data_ptr() % 2 for v in views) and all(v.is_contiguous() for v in views)
+    return views
+
+
+def _ragged_nan(crops, out_hw, nhwc, pinned):
+    """tise_resize_ragged_f32 as device.resize_ragged_f32 calls it (Pillow's rule per image, a page-locked table, the current
+    stream), into a destination pre-filled with NaN.  -> (n, oh, ow, 3) view of what the kernel wrote."""
+    from tise_toolbox_amd import _lib, device
+    oh, ow = out_hw
+    n = len(crops)
+    dev = crops[0].device
+    dst = torch.full((n, oh, ow, 3) if nhwc else (n, 3, oh, ow), float("nan"), dtype=torch.float32, device=dev)
+    ptrs = np.fromiter((c.data_ptr() for c in crops), dtype=np.uint64, count=n)
+    hs = np.fromiter((c.shape[0] for c in crops), dtype=np.int32, count=n)
+    ws = np.fromiter((c.shape[1] for c in crops), dtype=np.int32, count=n)
+    orders = np.fromiter((1 if device.pillow_vertical_first(c.shape[0], c.shape[1], oh) else 0 for c in crops), dtype=np.int32, count=n)
+    need = n * (64 + 4 * oh) + 16 * (n // RAGGED_CHUNK + 1)
+    assert pinned.numel() >= need and pinned.is_pinned()
+    ws_dev = torch.empty(need, dtype=torch.uint8, device=dev)
+    bad = ctypes.c_int64(-1)
+    st = _lib.load().tise_resize_ragged_f32(ptrs.ctypes.data, hs.ctypes.data, ws.ctypes.data, orders.ctypes.data, n,
+                                            ctypes.c_void_p(dst.data_ptr()), oh, ow, 1 if nhwc else 0, 1, 0.0, 255.0, 128.0, 128.0,
+                                            ctypes.c_void_p(ws_dev.data_ptr()), need, ctypes.c_void_p(pinned.data_ptr()),
+                                            ctypes.byref(bad), _stream())
+    assert st == _lib.TISE_OK, (st, bad.value)
+    torch.cuda.current_stream().synchronize()                    # the table and the workspace are read until here
+    return dst if nhwc else dst.permute(0, 2, 3, 1)
+
+
+def _assert_images_equal(got, nine, idx, what):
+    """got[i] == nine[idx[i]] in every bit, on the device; the message names the first and last image that differ."""
+    g, w = got.contiguous().view(torch.int32), nine.contiguous().view(torch.int32)
+    assert not torch.isnan(got).any(), f"{what}: some of the destination was not written"
+    same = torch.cat([(g[s:s + 1024] == w[idx[s:s + 1024]]).flatten(1).all(dim=1) for s in range(0, len(idx), 1024)])
+    bad = torch.nonzero(~same).flatten().tolist()
+    assert not bad, f"{what}: {len(bad)} of {len(idx)} images differ from their twin of the 9-image call: first {bad[0]}, last {bad[-1]}"
+
+
+@pytest.fixture(scope="module")
+def pinned_table():
+    return torch.empty(8193 * (64 + 4 * 37) + 16 * 3, dtype=torch.uint8).pin_memory()
+
+
+# n: one full launch, one image past it (a second launch of one image), two full launches and one image
+@pytest.mark.parametrize("n", [RAGGED_CHUNK, RAGGED_CHUNK + 1, 2 * RAGGED_CHUNK + 1])
+@pytest.mark.parametrize("out_hw", [(5, 7), (37, 100)], ids=lambda s: "%dx%d" % s)
+def test_ragged_across_the_chunk_border(cuda_device, pinned_table, out_hw, n):
+    """tise_resize_ragged_f32 launches 4096 images at a time, each launch with its own part of the table and its own
+    destination offset.  The crops are views cycling through nine base images (some at odd addresses), both layouts.  The
+    9-image call is held to the restatement; image i of the big call must equal image i mod 9 of it, bit for bit, compared on
+    the device over every value.  At n = 4097 a second run keeps both bases that need more than 48 KB of LDS out of the first
+    launch and puts one in the second launch alone, whose hipFuncSetAttribute then decides it."""
+    imgs, want = _bases(out_hw)
+    views = _base_views(cuda_device, imgs)
+    big = [i for i, im in enumerate(imgs) if im.shape[:2] in ((64, 2000), (2000, 64), (16, 2000), (800, 64))]
+    assert OVER_48K[out_hw] in big
+    runs = [torch.arange(n) % 9]
+    if n == RAGGED_CHUNK + 1:
+        small = torch.tensor([i for i in range(9) if i not in big])
+        runs.append(torch.cat([small[torch.arange(RAGGED_CHUNK) % len(small)], torch.tensor([OVER_48K[out_hw]])]))
+    for nhwc in (True, False):
+        nine = _ragged_nan(views, out_hw, nhwc, pinned_table)
+        _same_bits(nine.cpu().numpy(), want, f"the 9-image call, nhwc={nhwc}")
+        for r, idx in enumerate(runs):
+            got = _ragged_nan([views[i] for i in idx.tolist()], out_hw, nhwc, pinned_table)
+            _assert_images_equal(got, nine, idx.to(cuda_device), f"n={n} run {r} nhwc={nhwc}")
+
+
+def test_ragged_two_launches_on_a_side_stream(cuda_device):
+    """device.resize_ragged_f32 (its ring of page-locked tables in use) on a side stream, 4097 crops of three sizes and an
+    output size this process has not planned: plan upload, table copy and both launches with no help from the default stream.
+    The result of this shape is allocated here for the first time, so no earlier result can stand in for a missing write."""
+    from tise_toolbox_amd import device
+    oh, ow = 6, 9
+    sizes = [(23, 29), (31, 17), (13, 41)]
+    imgs = [ref.content("rand", 500 + i, h, w) for i, (h, w) in enumerate(sizes)]
+    want = torch.from_numpy(np.stack([ref.clean_input(im, (oh, ow)) for im in imgs])).to(cuda_device)
+    n = RAGGED_CHUNK + 1
+    idx = torch.arange(n) % 3
+    side = torch.cuda.Stream(device=cuda_device)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        views = _base_views(cuda_device, imgs)
+        for cl in (True, False):
+            got = device.resize_ragged_f32([views[i] for i in idx.tolist()], (oh, ow), channels_last=cl)
+            assert tuple(got.shape) == (n, 3, oh, ow)
+            side.synchronize()
+            _assert_images_equal(got.permute(0, 2, 3, 1), want, idx.to(cuda_device), f"side stream, channels_last={cl}")
+    side.synchronize()
+
+
+def test_plan_cache_eviction_buffer_reuse_and_reallocation(cuda_device, pinned_table):
+    """More distinct source sizes than the f32 plan cache holds (8192), as the u8 sibling in test_gpu_resize.py.  First all
+    8464 sizes in ONE tise_resize_ragged_f32 call of three launches: planning the third launch's sizes evicts plans whose
+    launch is still in flight (the synchronisation in get_plan_f orders the overwrite behind it); all 8464 results are held to
+    the restatement.  Then device.resize_f32 one size at a time over every 7th size: the cache holds the last 8192, so the
+    first 46 calls of that scan miss, each evicting the least recently used plan and writing its table into the victim's
+    buffer, and the rest hit.  (Over ALL sizes, where every call misses, the test took 5.1 s on the MI355X machine -- 3.6 s of
+    it the restatement on the host, 1.1 s that scan -- against 2.3 s for its u8 sibling in test_gpu_resize.py; every 7th
+    keeps it within twice the sibling.)  Then the first 50 sizes again (42 of them evicted: planned again into reused
+    buffers), the last 50 (still cached), and 256 x 256 -> 299 x 299, a plan larger than any of those buffers with their
+    slack, allocated anew.  Every result is held to the restatement."""
+    from tise_toolbox_amd import device
+    oh, ow = 5, 7
+    sizes = [(h, w) for h in range(1, 93) for w in range(1, 93)]
+    assert len(sizes) > 8192 + 50 and len(sizes) <= 3 * RAGGED_CHUNK
+    rng = np.random.default_rng(8192)
+    pool = rng.integers(0, 256, (92 * 92 * 3 + 8464,), dtype=np.uint8)
+    pool_dev = torch.as_tensor(pool, device=cuda_device)
+
+    def image(i, p=pool):
+        h, w = sizes[i]
+        return p[i:i + h * w * 3].reshape(h, w, 3)                     # a different window of the pool for every size, any address
+
+    t0 = time.time()
+    want = np.stack([ref.clean_input(image(i), (oh, ow)) for i in range(len(sizes))])
+    t1 = time.time()
+    got = _ragged_nan([image(i, pool_dev) for i in range(len(sizes))], (oh, ow), True, pinned_table)
+    _same_bits(got.cpu().numpy(), want, "one ragged call over 8464 sizes")
+    t2 = time.time()
+
+    def run(indices):
+        for start in range(0, len(indices), 92):
+            chunk = indices[start:start + 92]
+            outs = [device.resize_f32(image(i, pool_dev).unsqueeze(0), (oh, ow)) for i in chunk]
+            _same_bits(torch.cat(outs).permute(0, 2, 3, 1).cpu().numpy(), want[chunk], f"sizes {sizes[chunk[0]]} .. {sizes[chunk[-1]]}")
+
+    run(list(range(0, len(sizes), 7)))
+    run(list(range(50)))                                              # evicted by now: planned again
+    run(list(range(len(sizes) - 50, len(sizes))))                     # still cached
+    print(f"restatement of {len(sizes)} sizes on the host {t1 - t0:.2f} s; one ragged call {t2 - t1:.2f} s; one size at a time {time.time() - t2:.2f} s")
+    cases = [("rand", 100), ("bw", 101), ("rand", 102)]
+    x = np.stack([ref.content(k, s, 256, 256) for k, s in cases])
+    big = ref.affine(np.stack([_want(k, s, 256, 256, 299, 299, "bicubic", 0) for k, s in cases]), **STD)
+    for nhwc in (True, False):
+        _same_bits(_run(cuda_device, x, (299, 299), nhwc=nhwc), big, f"256 x 256 -> 299 x 299 nhwc={nhwc}")
 
 
 # ---- engine ----------------------------------------------------------------------------------------------------------------

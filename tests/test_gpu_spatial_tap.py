@@ -50,6 +50,41 @@ def test_tap_kernel_matches_merge_bit_for_bit(cuda_device, n, h, w, C, c0, nc, l
         assert torch.equal(_bits(device.split_tap_rows(x, c0, nc, ld)), _bits(out))
 
 
+# The launch caps its grid at 16 384 workgroups of 256 threads: n * ld above TAP_STRIDE goes round the grid-stride loop.
+TAP_STRIDE = 16384 * 256
+# (n, h, w, C, c0, nc, ld), each just past the cap
+TAP_PAST_THE_CAP = [(2049, 17, 17, 16, 0, 7, 2048),     # the first n at which sFID's rows (ld = 2048) stride; C = 16: all tail
+                    (2071, 17, 17, 16, 0, 7, 2027),     # odd ld: n * ld is odd, a partial last workgroup, rows shift per round
+                    (32515, 1, 3, 48, 28, 7, 129),      # crosses from the 32-block into the 16-wide tail, odd total
+                    (32515, 2, 2, 64, 30, 4, 129)]      # crosses a 32-block boundary, odd total
+
+
+@pytest.mark.parametrize("n,h,w,C,c0,nc,ld", TAP_PAST_THE_CAP, ids=lambda v: str(v))
+def test_tap_kernel_past_the_grid_cap(cuda_device, n, h, w, C, c0, nc, ld):
+    """More output values than the capped grid has threads: the second round of the loop writes the tail.  Every value is
+    bit-equal to conv_split.merge's slice in h, w, c order, the padding is exactly +0 and the source's bits are unchanged."""
+    import ctypes
+    from tise_toolbox_amd import _lib
+    from tise_toolbox_amd.conv_split import merge, split
+    total = n * ld
+    assert TAP_STRIDE < total < 2 * TAP_STRIDE and (ld == 2048 or total % 256)
+    g = torch.Generator(device=cuda_device).manual_seed(100 * C + c0)
+    t = split(torch.randn((n, h, w, C), generator=g, device=cuda_device) * 3.0).contiguous()
+    before = t.clone()
+    want = merge(t)[..., c0:c0 + nc].reshape(n, -1)
+    out = torch.full((n, ld), float("nan"), dtype=torch.float32, device=cuda_device)
+    _lib.call("tise_split_tap_rows", ctypes.c_void_p(t.data_ptr()), n, h * w, C, c0, nc, ctypes.c_void_p(out.data_ptr()), ld,
+              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    used = h * w * nc
+    assert used < ld
+    rows = torch.nonzero((_bits(out[:, :used]) != _bits(want)).any(dim=1)).flatten().tolist()
+    assert not rows, f"{len(rows)} of {n} rows differ from merge: first {rows[0]}, last {rows[-1]}"
+    pad = _bits(out[:, used:])
+    assert pad.numel() == n * (ld - used) and bool((pad == 0).all())                                  # +0.0: no sign bit, no NaN left
+    assert not bool(torch.signbit(out[:, used:]).any())
+    assert torch.equal(t.view(torch.int16), before.view(torch.int16))
+
+
 def test_tap_refusals(cuda_device):
     from tise_toolbox_amd import device
     t = torch.zeros((1, 2, 2, 128), dtype=torch.float16, device=cuda_device)
@@ -132,6 +167,29 @@ def test_spatial_engine_changes_nothing_else(cuda_device, engines, images):
     assert tuple(fa.shape) == (4, 2048) and tuple(la.shape) == (4, 1008)
     assert torch.equal(_bits(fa), _bits(fb)) and torch.equal(_bits(la), _bits(lb))
     assert engines["tf1"].fused._spatial_rows is None and not engines["tf1"].spatial
+
+
+def test_spatial_engine_changes_nothing_else_on_the_clean_route(cuda_device, split_conv, images):
+    """The other float route: resize="clean" with and without the tap gives the same pool3 and logits, bit for bit, and the
+    tap's rows there are the tap of the SAME trunk -- the rows a resize="tf1" engine's trunk gives on the clean input."""
+    from tise_toolbox_amd import device
+    from tise_toolbox_amd.engine import RealismEngine
+    kw = dict(dims=2048, seed=0, network=NET, with_logits=True, resize="clean")
+    u8 = torch.as_tensor(np.array(images[0]), device=cuda_device)
+    with_tap, without = RealismEngine(spatial=True, **kw), RealismEngine(**kw)
+    fa, la = with_tap.features_from_u8(u8)
+    fa, la = fa.clone(), la.clone()
+    rows = with_tap.spatial_rows().clone()
+    fb, lb = without.features_from_u8(u8)
+    assert tuple(fa.shape) == (4, 2048) and tuple(la.shape) == (4, 1008) and tuple(rows.shape) == (4, 2048)
+    assert torch.equal(_bits(fa), _bits(fb)) and torch.equal(_bits(la), _bits(lb))
+    assert without.fused._spatial_rows is None and not without.spatial
+    assert bool((_bits(rows[:, 2023:]) == 0).all()) and bool(rows[:, :2023].any(1).all())
+    x = device.resize_f32(u8, (299, 299))                               # the clean input, through the tf1 engine's trunk
+    tf1_eng = RealismEngine(dims=2048, seed=0, network=NET, with_logits=True, resize="tf1", spatial=True)
+    fc, lc = tf1_eng._trunk(x, prenormalized=True)
+    assert torch.equal(_bits(fc), _bits(fa)) and torch.equal(_bits(lc), _bits(la))
+    assert torch.equal(_bits(tf1_eng.spatial_rows()), _bits(rows))
 
 
 def test_tf1_route_feeds_the_restatements_bits(cuda_device, engines, images):

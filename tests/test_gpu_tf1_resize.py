@@ -59,6 +59,59 @@ def test_kernel_matches_restatement_bit_for_bit(cuda_device, n, h, w, oh, ow):
     _same_bits(got, ref.network_input_tf1(x, (oh, ow)), f"{(n, h, w)} -> {(oh, ow)}")
 
 
+# The launch caps its grid at GRID_CAP workgroups of 256 threads; a thread takes pixels i, i + stride, ... (csrc/resize_tf1.hip).
+GRID_CAP = 16384
+STRIDE = GRID_CAP * 256                                          # 4 194 304 output pixels per round of the loop
+
+# (n, h, w, oh, ow): just past the cap.  The first is the product's output size; the second is not square, its pixel count is
+# no multiple of 256 (a partial last workgroup in the second round) and ow does not divide the stride, so a thread's ox, oy and
+# img all change from one iteration to the next.
+PAST_THE_CAP = [(48, 8, 8, 299, 299), (94, 5, 6, 149, 301)]
+
+
+@pytest.mark.parametrize("n,h,w,oh,ow", PAST_THE_CAP, ids=lambda v: str(v))
+def test_past_the_grid_cap_bit_for_bit(cuda_device, n, h, w, oh, ow):
+    """More output pixels than the capped grid has threads: the second iteration of the grid-stride loop writes the tail.
+    Every value is held to the restatement, so a wrong stride, a loop left early or an index that wraps shows."""
+    pixels = n * oh * ow
+    assert STRIDE < pixels < 2 * STRIDE
+    if (oh, ow) != (299, 299):
+        assert pixels % 256 != 0 and STRIDE % ow != 0 and STRIDE % (oh * ow) != 0
+    x = _source(n, h, w)
+    got = _run(torch.as_tensor(np.array(x), device=cuda_device), oh, ow)
+    assert not np.isnan(got).any()                               # every output was written
+    _same_bits(got, ref.network_input_tf1(x, (oh, ow)), f"{(n, h, w)} -> {(oh, ow)}")
+
+
+def test_several_rounds_of_the_grid_stride_loop(cuda_device):
+    """600 images -> 299 x 299 are 53.6 M pixels, 13 rounds of the loop (a 1000-image pass of the product takes 22).  The
+    sources cycle through 7 distinct images; a 7-image launch (one round, no loop) is held to the restatement on the host,
+    and the 644 MB result is compared with it on the device, image i against image i mod 7, bit for bit.  Nothing of the
+    big result is sampled and nothing of it is copied back."""
+    n, k, h, w, oh, ow = 600, 7, 4, 4, 299, 299
+    assert n * oh * ow > 12 * STRIDE
+    base = _source(k, h, w)
+    small_src = torch.as_tensor(np.array(base), device=cuda_device)
+    small = torch.full((k, oh, ow, 3), float("nan"), dtype=torch.float32, device=cuda_device)
+    from tise_toolbox_amd import _lib
+    _lib.call("tise_resize_tf1_f32", ctypes.c_void_p(small_src.data_ptr()), k, h, w, ctypes.c_void_p(small.data_ptr()), oh, ow,
+              128.0, 2.0 ** -7, _stream())
+    _same_bits(small.cpu().numpy(), ref.network_input_tf1(base, (oh, ow)), "the 7-image launch")
+
+    idx = torch.arange(n, device=cuda_device) % k
+    src = small_src[idx].contiguous()
+    dst = torch.full((n, oh, ow, 3), float("nan"), dtype=torch.float32, device=cuda_device)
+    _lib.call("tise_resize_tf1_f32", ctypes.c_void_p(src.data_ptr()), n, h, w, ctypes.c_void_p(dst.data_ptr()), oh, ow,
+              128.0, 2.0 ** -7, _stream())
+    want = small.view(torch.int32)
+    got = dst.view(torch.int32)
+    full = (n // k) * k
+    same = (got[:full].view(n // k, k, oh, ow, 3) == want).flatten(2).all(dim=2).flatten()
+    same = torch.cat([same, (got[full:] == want[:n - full]).flatten(1).all(dim=1)])
+    bad = torch.nonzero(~same).flatten().tolist()
+    assert not bad, f"{len(bad)} of {n} images differ from their 7-image twin: first {bad[0]}, last {bad[-1]}"
+
+
 def test_raw_values_without_the_affine(cuda_device):
     x = _source(1, 37, 53)
     got = _run(torch.as_tensor(np.array(x), device=cuda_device), 5, 7, sub=0.0, mul=1.0)

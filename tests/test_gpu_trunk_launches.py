@@ -59,7 +59,17 @@ CONFIGS = {
     # the documented A/B switches that reach the remaining product instances: Conv2d_2b's padded
     # kernel on the plain tensor, and both stem pools taken whole inside their consumers' operand loads
     "torchvision-plain-2b-pools-in-consumers": ("torchvision", 2048, {"TISE_CONV_PADBUF": "0", "TISE_POOL2_SPLIT": "0"}, "u8"),
+    # the float route of the ADM suite: TensorFlow 1's resize on the device, the fp32 stem on the Inception-2015 weights and
+    # the spatial tap behind Mixed_6d (ENGINE_KW below)
+    "inception-2015-tf1-spatial": ("inception-2015", 2048, {}, "fp32"),
 }
+# id -> further RealismEngine arguments; the fp32 input of these is device.resize_tf1_f32 of the audit images
+ENGINE_KW = {"inception-2015-tf1-spatial": dict(resize="tf1", spatial=True)}
+SPATIAL_CFG = "inception-2015-tf1-spatial"
+# the tap's launch, stated here and not read from the trunk: channels [0, 7) of Mixed_6d's 17 x 17 x 768 output (sblocks[6];
+# Mixed_6e is sblocks[7]) into rows of 2048
+TAP_SCALARS = dict(hw=289, C=768, c0=0, nc=7, ld=2048)
+TAP_BLOCK = 6
 CLASSES = {"torchvision": 1000, "inception-2015": 1008, "slim": 51}
 
 # Every kernel instance the dispatchers can launch for the product, read off csrc/conv_split.hip (tise_conv_split_f16,
@@ -92,7 +102,7 @@ class Audit:
         self.names = collections.Counter()
 
 
-def _engine(network, dims, env):
+def _engine(network, dims, env, **kw):
     from tise_toolbox_amd.engine import RealismEngine
     from tise_toolbox_amd.trunk import SplitTrunk
     with pytest.MonkeyPatch.context() as mp:
@@ -100,7 +110,7 @@ def _engine(network, dims, env):
         for k, v in env.items():
             mp.setenv(k, v)
         with A.keep_weights():
-            eng = RealismEngine(dims=dims, seed=0, with_logits=dims == 2048, network=network)
+            eng = RealismEngine(dims=dims, seed=0, with_logits=dims == 2048, network=network, **kw)
     assert type(eng.fused) is SplitTrunk
     return eng
 
@@ -108,23 +118,29 @@ def _engine(network, dims, env):
 def _run_audit(cfg, dev):
     from tise_toolbox_amd import device
     network, dims, env, entry = CONFIGS[cfg]
-    eng = _engine(network, dims, env)
+    eng = _engine(network, dims, env, **ENGINE_KW.get(cfg, {}))
     trunk = eng.fused
     imgs = torch.as_tensor(_cases.smooth_images(3, 256, 256, seed=0), device=dev)
 
     # resized by the product's own kernel, outside the recording (the recorder admits the trunk's entry points only)
-    x = device.resize_u8_only(imgs, (299, 299)) if entry == "u8" else device.resize_bilinear_u8(imgs, (299, 299), eng.lut, channels_last=True)
+    if cfg in ENGINE_KW:
+        x = device.resize_tf1_f32(imgs, (299, 299), 128, 2.0 ** -7, channels_last=True)
+    else:
+        x = device.resize_u8_only(imgs, (299, 299)) if entry == "u8" else device.resize_bilinear_u8(imgs, (299, 299), eng.lut, channels_last=True)
 
     def forward():
         f = trunk.forward_u8(x, eng.lut_dev) if entry == "u8" else trunk(x)
-        return f.flatten(1).clone(), (trunk.fc_logits(3).clone() if trunk.sfc is not None else None)
+        rows = trunk._spatial_rows.clone() if trunk.spatial else None
+        return f.flatten(1).clone(), (trunk.fc_logits(3).clone() if trunk.sfc is not None else None), rows
     with A.Recorder() as rec:
-        feats, logits = forward()
+        feats, logits, rows = forward()
     plain = forward()
     assert tuple(feats.shape) == (3, dims) and (logits is None or tuple(logits.shape) == (3, CLASSES[network]))
+    assert (rows is not None) == (cfg == SPATIAL_CFG) and (rows is None or tuple(rows.shape) == (3, TAP_SCALARS["ld"]))
     au = Audit()
     au.failures += A.check_assembly(rec.launches)
-    if not (torch.equal(feats, plain[0]) and (logits is None or torch.equal(logits, plain[1]))):
+    if not (torch.equal(feats, plain[0]) and (logits is None or torch.equal(logits, plain[1])) and
+            (rows is None or torch.equal(A.bits(rows), A.bits(plain[2])))):
         au.failures.append("the recorded forward and a plain one differ: recording must change nothing")
     for k, L in enumerate(rec.launches):
         au.names[L.name] += 1
@@ -139,6 +155,14 @@ def _run_audit(cfg, dev):
         if L.conv is not None:
             au.instances.setdefault(A.instance_of(L), []).append(repr(L))
     au.members = A.conv_members(rec.launches)
+    au.sequence = [(L.name, repr(L)) for L in rec.launches]
+    # where the launches of Mixed_6d and Mixed_6e are: the convolutions of sblocks[6] and sblocks[7] by identity
+    from tise_toolbox_amd.conv_split import SplitConv
+    au.block_launches = [[k for k, L in enumerate(rec.launches) if any(L.conv is c for c in trunk.sblocks[b][1].values() if isinstance(c, SplitConv))]
+                         for b in (TAP_BLOCK, TAP_BLOCK + 1)] if dims == 2048 else None
+    au.taps = [(k, dict(L.ints), L.in_ptr, [d[1] for d in L.dsts], rows) for k, L in enumerate(rec.launches) if L.name == A.TAP]
+    au.readers = {k: L.in_ptr for k, L in enumerate(rec.launches)}
+    au.writers = {k: list(L.dst_ptrs) for k, L in enumerate(rec.launches)}
     au.stems = [(3, 32, 3, 3, 2, 2, 0, 0, *L.dsts[0][1].shape[1:3]) for L in rec.launches if L.name in A.STEMS]
     au.sizes = A.tensor_sizes(rec.launches)
     au.flags = (trunk.stem_mfma, trunk.fuse_pool, trunk.pool_in_2b, trunk.pool2_split, trunk.pad2b)
@@ -181,6 +205,36 @@ def test_every_launch_matches_fp64_from_its_own_input(audits, cfg):
     assert au.names[stem[entry]] == 1 and sum(au.names[s] for s in A.STEMS) == 1
     if env.get("TISE_POOL_FUSE") == "0" and dims == 2048:       # the stand-alone stem pools + Mixed_6a / 7a's pool branches
         assert au.names["tise_maxpool3s2_split_nhwc"] == 4
+    assert au.names[A.TAP] == (1 if cfg == SPATIAL_CFG else 0)
+
+
+def test_the_spatial_float_route_launches_the_u8_routes_trunk_and_one_tap(audits):
+    """The engine adm_eval builds (Inception-2015, TensorFlow 1's resize, spatial) against the audited ``inception-2015``
+    forward: one fp32 stem in place of the u8 one, exactly one tap, every other launch the same launch in the same order.
+    The tap's scalars are the ones stated at the top of this file (not read from the trunk), its source is the buffer
+    Mixed_6d's last launch wrote and Mixed_6e's first launch reads, and it sits between exactly those two: after every
+    launch of sblocks[6]'s convolutions and before every launch of sblocks[7]'s, with nothing but that block boundary's
+    pools beside it.  Its rows are the rows the engine hands out.  (Each launch's values: the test above.)"""
+    au, base = audits(SPATIAL_CFG), audits("inception-2015")
+    assert not au.failures, au.failures
+    assert len(au.taps) == 1, f"{len(au.taps)} taps launched"
+    k, ints, src, dsts, rows = au.taps[0]
+    what = f"the tap (launch {k}: {au.sequence[k][1]})"
+    rest = [s for s in au.sequence if s[0] != A.TAP]
+    assert [s[0] for s in rest if s[0] in A.STEMS] == ["tise_stem_conv3x3s2_split"]
+    assert [s[0] for s in base.sequence if s[0] in A.STEMS] == ["tise_stem_conv3x3s2_split_u8_mfma"]
+    assert [s for s in rest if s[0] not in A.STEMS] == [s for s in base.sequence if s[0] not in A.STEMS], "the float route launches another trunk"
+    assert (ints[1], ints[2], ints[3], ints[4], ints[5], ints[7]) == (3, *(TAP_SCALARS[f] for f in ("hw", "C", "c0", "nc", "ld"))), (what, ints)
+    b6, b7 = au.block_launches
+    assert b6 and b7 and max(b6) < k < min(b7), f"{what} is not between Mixed_6d's launches {b6} and Mixed_6e's {b7}"
+    between = [au.sequence[j][0] for j in range(max(b6) + 1, min(b7)) if j != k]
+    assert all("pool" in name for name in between), (what, between)
+    last_writer = max(j for j in range(k) if src in au.writers[j])
+    first_reader = min(j for j in range(k + 1, len(au.sequence)) if au.readers[j] == src)
+    assert min(b6) <= last_writer < k, f"{what} reads a buffer Mixed_6d did not write (last written by launch {last_writer})"
+    assert k < first_reader <= min(b7), f"{what} reads a buffer Mixed_6e does not read (next read by launch {first_reader})"
+    assert not any(au.readers[j] == src for j in range(min(b6), k)), f"{what}: its source was read inside Mixed_6d"
+    assert torch.equal(A.bits(dsts[0]), A.bits(rows)), f"{what}: the engine's rows are not what the launch wrote"
 
 
 def test_every_convolution_of_the_graph_is_launched_once(audits):
@@ -273,7 +327,7 @@ def test_split_mean_launches_of_the_trunk(audits):
 
 # ------------------------------------------------------------------------------------------------------ batch 5000
 BATCH_CASES = {"torchvision": ("torchvision", {}), "torchvision-separate-pools": ("torchvision", {"TISE_POOL_FUSE": "0"}),
-               "inception-2015": ("inception-2015", {})}
+               "inception-2015": ("inception-2015", {}), SPATIAL_CFG: ("inception-2015", {})}
 # the tensors whose 2^31-element (fp16 split maps) or 2^32-byte (fp32 network input) mark a full device batch must pass:
 # Conv2d_1a's output and Conv2d_2a's zero-bordered one, Conv2d_4a's half-pooled map, the 35 x 35 x 288 and 17 x 17 x 768 maps
 EDGE_TENSORS = ["149x149x64 float16", "71x35x384 float16", "35x35x576 float16", "17x17x1536 float16"]
@@ -288,7 +342,9 @@ def test_a_full_device_batch_is_beyond_the_32_bit_marks(audits):
     """The batch-5000 cases below cover the edge they are there for: from the recorded launch shapes, the number of images
     at which each activation tensor passes 2^31 elements and 2^32 bytes; ``engine.DEVICE_BATCH_DEFAULT`` lies beyond every
     one of EDGE_TENSORS' marks (the last: the 17 x 17 x 768 maps at 4838 images) and beyond the fp32 network input's 4 GiB
-    (4004 images).  Fails when the default batch is lowered or a layout change moves a tensor off the list."""
+    (4004 images).  The u8 cases never hold that input; ``inception-2015-tf1-spatial`` does: its input is ONE
+    tise_resize_tf1_f32 launch of 5000 images (5.4 GB) that the fp32 stem reads whole, and its tap reads the 17 x 17 x 1536
+    map past 2^31 elements.  Fails when the default batch is lowered or a layout change moves a tensor off the list."""
     from tise_toolbox_amd.engine import DEVICE_BATCH_DEFAULT as B
     sizes = dict(audits("torchvision-fp32-input").sizes)
     for cfg in BATCH_CASES:
@@ -311,43 +367,80 @@ def _first_last(a, b):
     return None if rows.numel() == 0 else (int(rows[0]), int(rows[-1]), int(rows.numel()))
 
 
+def _float_input(B, dev):
+    """The fp32 network input of the spatial case: ONE device.resize_tf1_f32 call on B distinct 32 x 32 images (5.4 GB at
+    5000: past 4 GiB, about 107 rounds of the kernel's grid-stride loop).  Every value is pinned: bit-equal to the same
+    call on 250-image slices (launches of 6 rounds each, the kind tests/test_gpu_tf1_resize.py holds to the restatement
+    past the grid cap), and the first and last 4 images to the restatement itself."""
+    import numpy as np
+    from tests import _tf1_resize_ref as tf1
+    from tise_toolbox_amd import device
+    src = torch.as_tensor(np.random.default_rng(5).integers(0, 256, (B, 32, 32, 3), dtype=np.uint8), device=dev)   # distinct images
+    x = device.resize_tf1_f32(src, (299, 299), 128, 2.0 ** -7, channels_last=True)
+    assert tuple(x.shape) == (B, 3, 299, 299) and x.numel() * 4 > 2 ** 32
+    for i in range(0, B, 250):
+        part = device.resize_tf1_f32(src[i:i + 250], (299, 299), 128, 2.0 ** -7, channels_last=True)
+        assert torch.equal(A.bits(x[i:i + 250].permute(0, 2, 3, 1)), A.bits(part.permute(0, 2, 3, 1))), \
+            f"the {B}-image resize differs from the 250-image call at images {i}..{i + 249}: first / last / count {_first_last(x[i:i + 250], part)}"
+    for sl in (slice(0, 4), slice(B - 4, B)):
+        want = tf1.network_input_tf1(src[sl].cpu().numpy(), (299, 299))
+        got = x[sl].permute(0, 2, 3, 1).contiguous().cpu().numpy()
+        assert np.array_equal(got.view(np.int32), want.view(np.int32)), f"images {sl} of the {B}-image resize differ from the restatement"
+    return x
+
+
 @pytest.mark.parametrize("case", list(BATCH_CASES))
 def test_batch_5000_every_image_bit_for_bit(cuda_device, case):
     """pool3 and the logits of every image of one ``engine.DEVICE_BATCH_DEFAULT``-image pass are the bits a 250-image pass
     gives (a first / last differing image names the tensor whose 32-bit mark was crossed), and at the fed paths' 1000 images
-    the bits single-image passes give for the first and last 8 images."""
+    the bits single-image passes give for the first and last 8 images.  The spatial case runs the float route: the fp32 input
+    of ``_float_input`` through the fp32 stem, and the spatial rows of every pass are compared like pool3 and the logits --
+    the stem reads past 2^32 bytes, and the tap strides (5000 x 2048 values) over a source past 2^31 elements."""
     import bench
     from tise_toolbox_amd import device
     from tise_toolbox_amd.engine import DEVICE_BATCH_DEFAULT as B, FEED_DEVICE_BATCH_DEFAULT as FB
     network, env = BATCH_CASES[case]
-    eng = _engine(network, 2048, env)
+    eng = _engine(network, 2048, env, **ENGINE_KW.get(case, {}))
     trunk, lut = eng.fused, eng.lut_dev
     t0 = time.time()
-    u8 = torch.empty((B, 299, 299, 3), dtype=torch.uint8, device=cuda_device)
-    for i in range(0, B, 500):                                   # distinct images, resized by the product's own kernel
-        device.resize_u8_only(bench.synth_images_device(i, min(i + 500, B), cuda_device, seed=0), (299, 299), out=u8[i:i + 500])
+    if case in ENGINE_KW:
+        u8 = _float_input(B, cuda_device)                        # (B, 3, 299, 299) fp32 in channels_last storage
 
-    def run(x):
-        f = trunk.forward_u8(x, lut).flatten(1).clone()
-        return f, trunk.fc_logits(x.shape[0]).clone()
+        def run(x):
+            f = trunk(x).flatten(1).clone()
+            return f, trunk.fc_logits(x.shape[0]).clone(), A.bits(trunk._spatial_rows).clone()
+    else:
+        u8 = torch.empty((B, 299, 299, 3), dtype=torch.uint8, device=cuda_device)
+        for i in range(0, B, 500):                                   # distinct images, resized by the product's own kernel
+            device.resize_u8_only(bench.synth_images_device(i, min(i + 500, B), cuda_device, seed=0), (299, 299), out=u8[i:i + 500])
+
+        def run(x):
+            f = trunk.forward_u8(x, lut).flatten(1).clone()
+            return f, trunk.fc_logits(x.shape[0]).clone(), torch.empty((x.shape[0], 0), dtype=torch.int32, device=x.device)   # no rows
     try:
-        full_f, full_l = run(u8)
+        full_f, full_l, full_r = run(u8)
         assert tuple(full_f.shape) == (B, 2048) and tuple(full_l.shape) == (B, CLASSES[network])
+        assert tuple(full_r.shape) == (B, TAP_SCALARS["ld"] if case in ENGINE_KW else 0)
+        if case in ENGINE_KW:                                    # the rows are values, not zeros, and their padding is +0
+            used = TAP_SCALARS["hw"] * TAP_SCALARS["nc"]
+            assert bool((full_r[:, :used] != 0).any(1).all()) and not bool(full_r[:, used:].any())
         assert bool(torch.isfinite(full_f).all()) and full_f.std(0).mean().item() > 0
         # a slice of 299 x 299 x 3 byte images starts on an odd address; the engine hands the trunk a fresh tensor per batch
         parts = [run(u8[i:i + 250].clone()) for i in range(0, B, 250)]
-        part_f, part_l = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+        part_f, part_l, part_r = (torch.cat([p[j] for p in parts]) for j in range(3))
         del parts
         assert torch.equal(full_f, part_f), f"{case}: pool3 of a {B}-image pass differs from 250-image passes: first / last / count {_first_last(full_f, part_f)}"
         assert torch.equal(full_l, part_l), f"{case}: logits differ: first / last / count {_first_last(full_l, part_l)}"
-        fed_f, fed_l = run(u8[:FB].clone())
+        assert torch.equal(full_r, part_r), f"{case}: the spatial rows differ: first / last / count {_first_last(full_r, part_r)}"
+        fed_f, fed_l, fed_r = run(u8[:FB].clone())
         assert torch.equal(fed_f, full_f[:FB]) and torch.equal(fed_l, full_l[:FB]), _first_last(fed_f, full_f[:FB])
+        assert torch.equal(fed_r, full_r[:FB]), f"{case}: the spatial rows: first / last / count {_first_last(fed_r, full_r[:FB])}"
         for i in list(range(8)) + list(range(FB - 8, FB)):
-            one_f, one_l = run(u8[i:i + 1].clone())
-            assert torch.equal(one_f, fed_f[i:i + 1]) and torch.equal(one_l, fed_l[i:i + 1]), (case, i)
+            one_f, one_l, one_r = run(u8[i:i + 1].clone())
+            assert torch.equal(one_f, fed_f[i:i + 1]) and torch.equal(one_l, fed_l[i:i + 1]) and torch.equal(one_r, fed_r[i:i + 1]), (case, i)
         torch.cuda.synchronize()
         print(f"{case}: {B} images bit-identical to 20 passes of 250; {FB} to single images; {time.time() - t0:.1f} s")
     finally:
         del u8, eng, trunk
-        full_f = full_l = part_f = part_l = fed_f = fed_l = None
+        full_f = full_l = part_f = part_l = fed_f = fed_l = full_r = part_r = fed_r = None
         torch.cuda.empty_cache()
