@@ -420,7 +420,8 @@ int tise_is_finalize(const double* acc_dev, int C_eff, int64_t n_total, int spli
  *               no sum.  Bitwise reproducible (fixed summation order, no atomics).
  *   ws_dev      ws_bytes >= tise_calib_workspace_bytes(rows, C, n_bins) of device scratch
  * Rejected before any HIP call (TISE_ERR_INVALID_ARG): a NULL pointer, rows < 0, C < 1, c0 < 0,
- * ld < c0 + C, n_bins outside 1..64, T <= 0 or not finite, a workspace too small.
+ * ld < c0 + C, n_bins outside 1..64, T <= 0 or not finite, T so small that 1 / T is not finite
+ * (below 5.56e-309), T > 2^100 (the kernel's column padding relies on it), a workspace too small.
  * ------------------------------------------------------------------------------------------ */
 int tise_calib_workspace_bytes(int64_t rows, int C, int n_bins, size_t* bytes);
 int tise_calib_eval(const float* logits_dev, int64_t rows, int64_t ld, int c0, int C, const int32_t* labels_dev,

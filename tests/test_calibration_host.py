@@ -109,6 +109,53 @@ def test_ece_from_bins():
     assert got == pytest.approx(0.2 * 0.4 + 0.1 * 0.6, abs=1e-15)
 
 
+# ---- the GPU tests' oracle against mpmath ------------------------------------------------------------------------------------
+def _oracle_cases(C):
+    """(z, labels, T): seeded rows with |d| / T up to ~700 and tied maxima (make_logits), then hand-built rows: two, three
+    and C tied maxima with the label on and off the tie, X = max|d| / T at 690 .. 705, a row of equal logits."""
+    from tests import _calib_ref as R
+    out = []
+    for T, seed in ((0.05, 1), (0.598, 2), (10.0, 3)):
+        z, y = R.make_logits(8, C, T, seed=100 * C + seed)
+        out.append((z, y, T))
+    for T in (0.2188, 1.0):
+        rng = np.random.default_rng(C)
+        z = (rng.standard_normal((7, C)) * T).astype(np.float32)
+        y = rng.integers(0, C, size=7)
+        z[0, [0, C - 1]] = z[0].max() + 1.0                   # two tied maxima, label on the second
+        y[0] = C - 1
+        z[1, :min(3, C)] = z[1].max() + 0.5                   # three (C = 2: two), label off the tie where there is room
+        y[1] = C - 1
+        z[2] = 1.25                                          # all equal: s = C, nll = log C, g = 0
+        for i, X in ((3, 690.0), (4, 700.0), (5, 705.0)):
+            z[i, y[i]] = z[i].max() + 1.0                    # label on the maximum ...
+            z[i, (y[i] + 1) % C] = z[i].max() - np.float32(X * T)          # ... and one logit X T below it
+        z[6, (y[6] + 1) % C] = z[6].max() + np.float32(700.0 * T)          # the label 700 T below the maximum
+        out.append((z, y, T))
+    return out
+
+
+@pytest.mark.parametrize("C", [2, 129, 1025, 2049])
+def test_oracle_is_within_its_own_bound_of_mpmath(C):
+    """The fp64 oracle the GPU tests compare the kernel with (tests/_calib_ref.oracle_rows) lies, row by row, within the
+    undoubled bound b_nll / b_g of the same formulas at 60 digits; fl32(1 / s) and the first argmax agree wherever
+    1 / s is clear of an fp32 rounding boundary.  That is what entitles the GPU tests to allow twice the bound."""
+    from tests import _calib_ref as R
+    worst = [0.0, 0.0]
+    for z, y, T in _oracle_cases(C):
+        o = R.oracle_rows(z, y, T)
+        for i in range(z.shape[0]):
+            nll, g, inv_s = R.mp_row(z[i], y[i], T)
+            e_nll, e_g = R.mp_abs_err(o["nll"][i], nll), R.mp_abs_err(o["g"][i], g)
+            assert e_nll <= o["b_nll"][i], (C, T, i, e_nll, o["b_nll"][i])
+            assert e_g <= o["b_g"][i], (C, T, i, e_g, o["b_g"][i])
+            worst = [max(worst[0], e_nll / o["b_nll"][i]), max(worst[1], e_g / o["b_g"][i] if o["b_g"][i] else 0.0)]
+            if R.fp32_midpoint_distance(inv_s) > 1e-10:
+                assert o["conf"][i] == np.float32(float(inv_s)), (C, T, i)
+            assert o["pred"][i] == int(np.flatnonzero(z[i] == z[i].max())[0])
+    print(f"C={C}: worst oracle error / bound  nll {worst[0]:.3f}  g {worst[1]:.3f}")
+
+
 # ---- labels ------------------------------------------------------------------------------------------------------------------
 def _touch(p):
     os.makedirs(os.path.dirname(p), exist_ok=True)
@@ -184,7 +231,9 @@ def test_calib_eval_rejects_bad_arguments_without_a_gpu():
         return lib.tise_calib_eval(z, rows, ld, c0, C, y, T, e, nb, o, w, wb, None)
     for kw in (dict(z=None), dict(y=None), dict(e=None), dict(o=None), dict(w=None), dict(rows=-1), dict(C=0),
                dict(c0=-1), dict(ld=49), dict(c0=1, ld=50), dict(nb=0), dict(nb=65), dict(T=0.0), dict(T=-1.0),
-               dict(T=float("inf")), dict(T=float("nan")), dict(wb=8)):
+               dict(T=float("inf")), dict(T=float("nan")), dict(wb=8),
+               # outside the domain of the arithmetic: 1 / T is not finite; the -FLT_MAX padding needs T <= 2^100
+               dict(T=5e-324), dict(T=1e-310), dict(T=2.0 ** 101), dict(T=np.nextafter(2.0 ** 100, np.inf))):
         assert call(**kw) == bad, kw
 
 

@@ -26,91 +26,21 @@ import numpy as np
 import pytest
 import torch
 
+from tests._calib_ref import U, embed, gamma, make_logits, oracle, rows_per_block  # noqa: F401
 from tise_toolbox_amd import _lib, calibration, device
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -53
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "calib_*.npz")))
 TEMPS = (0.05, 0.2188, 0.598, 1.0, 10.0)
 
 
-def gamma(n):
-    return n * U / (1.0 - n * U)
-
-
-def rows_per_block(C):
-    """Rows one block takes per grid step (csrc/calibrate.hip, calib_shape): 4 waves x 64 / G rows."""
-    g = 4 if C <= 64 else 8 if C <= 128 else 16 if C <= 256 else 64
-    return 4 * (64 // g)
-
-
 @pytest.fixture(scope="module")
 def dev(cuda_device):
     torch.cuda.set_device(cuda_device)
     return cuda_device
-
-
-def make_logits(rows, C, T, seed, ties=True):
-    """fp32 logits with |z - m| / T up to ~700, some rows with exactly tied maxima, and rows whose confidence is exactly
-    1 / k (k tied maxima, every other logit 1e4 below: exp underflows to 0) -- 1/2, 1/4, 1/5 ... sit on bin edges."""
-    rng = np.random.default_rng(seed)
-    spread = rng.uniform(0.05, 1.0, size=(rows, 1)) * 700.0 * T / 4.0
-    z = (rng.standard_normal((rows, C)) * spread).astype(np.float32)
-    labels = rng.integers(0, C, size=rows)
-    if ties and C >= 2:
-        for i in range(0, rows, 7):                          # tied maxima: the first index must win
-            k = min(C, int(rng.integers(2, 6)))
-            cols = np.sort(rng.choice(C, size=k, replace=False))
-            z[i, cols] = z[i].max() + 1.0
-            labels[i] = cols[i % 2]                          # the first tied column or the second
-        for i in range(3, rows, 11):                         # exact confidences 1/k
-            k = [1, 2, 4, 5, 10, 15][i % 6]
-            if k > C:
-                continue
-            z[i] = -1e4
-            z[i, rng.choice(C, size=k, replace=False)] = 0.0
-    return z, labels.astype(np.int64)
-
-
-def embed(z, c0, extra_cols, dev):
-    """Put (rows, C) logits at column c0 of a NaN-filled (rows + 1, c0 + C + extra_cols) device buffer."""
-    rows, C = z.shape
-    ld = c0 + C + extra_cols
-    buf = torch.full((rows + 1, ld), float("nan"), dtype=torch.float32, device=dev)
-    buf[:rows, c0:c0 + C] = torch.from_numpy(z).to(dev)
-    return buf[:rows], ld
-
-
-def oracle(z, labels, T, n_bins):
-    """fp64 numpy restatement of the kernel's formulas, plus per-row error bounds (module docstring)."""
-    x = z.astype(np.float64)
-    n, C = x.shape
-    m = x.max(axis=1)
-    d = x - m[:, None]
-    e = np.exp(d * (1.0 / T))
-    s = e.sum(axis=1)
-    sd = (d * e).sum(axis=1)
-    dy = x[np.arange(n), labels] - m
-    nll = np.log(s) - dy * (1.0 / T)
-    g = (dy - sd / s) / T / T
-    X = np.abs(d).max(axis=1) / T
-    K = C + 2 * X + 8
-    b_nll = U * (K + np.abs(nll) + 2 * np.abs(dy) / T)
-    b_g = U * (K + 4) * (np.abs(dy) + (np.abs(d) * e).sum(axis=1) / s) / T ** 2
-    conf = (1.0 / s).astype(np.float32)
-    pred = np.argmax(z, axis=1)                              # first maximum
-    edges = torch.linspace(0, 1, n_bins + 1).numpy()
-    cnt, csum, cor = np.zeros(n_bins), np.zeros(n_bins), np.zeros(n_bins)
-    for b in range(n_bins):
-        inb = (conf > edges[b]) & (conf <= edges[b + 1])
-        cnt[b] = inb.sum()
-        csum[b] = conf[inb].astype(np.float64).sum()
-        cor[b] = (pred[inb] == labels[inb]).sum()
-    return {"nll": nll.sum(), "g": g.sum(), "b_nll": 2 * (b_nll.sum() + gamma(n) * np.abs(nll).sum()),
-            "b_g": 2 * (b_g.sum() + gamma(n) * np.abs(g).sum()), "count": cnt, "conf": csum, "correct": cor}
 
 
 def check_case(dev, rows, C, T, seed, c0=0, extra_cols=0, n_bins=15):

@@ -18,6 +18,13 @@
 // out[3] instead.  The label selects z_y among the values already loaded (no indexed read: a bad label cannot read
 // out of bounds).
 //
+// Domain: T with a finite 1 / T (T > 2^-1024 = 5.56e-309; for a smaller, subnormal T inv_t is +inf and the maximum's own term would
+// be exp(0 * inf) = NaN) and T <= 2^100; anything else is refused on the host before a launch.  The upper limit is what
+// the register forms' padding relies on: a padded column holds -FLT_MAX and contributes exp((-FLT_MAX - m) / T), which
+// is exactly 0 only while (FLT_MAX + m) / T stays above ~745.  With a row maximum m >= -2^127 and T <= 2^100 the
+// argument is <= -(2^27 - 16), far below that.  A row whose maximum lies below -2^127 is outside the documented input
+// (the fp32 logits of a network); the streaming form has no padding and no such limit.
+//
 // Output (4 + 3 n_bins doubles): [sum nll, sum g, rows with a non-finite logit, rows with a bad label,
 //                                 count[b], sum conf[b], sum correct[b]  (b < n_bins)]
 // The counts are exact (integers below 2^53); the sums are fp64 in a fixed order.
@@ -40,6 +47,7 @@ namespace {
 #define CALIB_WAVES 4
 #define CALIB_MAX_BLOCKS 2048
 #define CALIB_MAX_BINS 64
+#define CALIB_MAX_TEMPERATURE 0x1p100              // largest T accepted (see "Domain" above)
 
 struct RowTerms {
     double nll, g;
@@ -89,7 +97,8 @@ __device__ __forceinline__ void finish_row(float m, float zy, double s, double s
 
 // one row held in registers: K values per lane, lane j of the group holds columns j, j + G, j + 2G, ...
 // Columns past C hold -FLT_MAX (finite, never loaded): below every real maximum or tied with it at a higher column, so
-// never the argmax; in the sums exp(d / T) underflows to exactly 0 and d * 0 = -0, so they add nothing -- the loops run
+// never the argmax; in the sums exp(d / T) underflows to exactly 0 (for T <= 2^100 and m >= -2^127: "Domain" in the
+// header) and d * 0 = -0, so they add nothing -- the loops run
 // without a branch per value (measured: the predicated form was VALU-issue bound at 115 us for 50 000 x 1000).
 template <int G, int K>
 __device__ __forceinline__ void row_terms_reg(const float* __restrict__ z, int C, int y, double inv_t, int gl,
@@ -278,6 +287,9 @@ int tise_calib_eval(const float* logits_dev, int64_t rows, int64_t ld, int c0, i
         ld < (int64_t)c0 + C || n_bins < 1 || n_bins > CALIB_MAX_BINS || !(temperature > 0.0) ||
         !std::isfinite(temperature))
         return TISE_ERR_INVALID_ARG;
+    // the domain the arithmetic supports (header): 1 / T finite, so the maximum's own term is exp(0 * inv_t) = 1 and not
+    // exp(0 * inf) = NaN; T <= 2^100, so the register forms' -FLT_MAX padding still underflows to exactly 0
+    if (!std::isfinite(1.0 / temperature) || temperature > CALIB_MAX_TEMPERATURE) return TISE_ERR_INVALID_ARG;
     const int nblk = calib_blocks(rows, C);
     const int P = 4 + 3 * n_bins;
     if (nblk > 0 && (!ws_dev || ws_bytes < (size_t)nblk * P * sizeof(double))) return TISE_ERR_INVALID_ARG;

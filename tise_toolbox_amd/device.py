@@ -860,7 +860,8 @@ class CalibrationEvaluator:
     """NLL / dNLL/dT / ECE bins of temperature-scaled logits (tise_calib_eval): one pass over resident logits per call.
 
     logits: (rows, ld) fp32 CUDA tensor (row stride ld, unit column stride); the classes are columns [c0, c0 + C) with
-    C = ld - c0 unless given.  labels: (rows,) integer class indices, kept on the device as int32."""
+    C = ld - c0 unless given.  labels: (rows,) integer class indices, kept on the device as int32; a non-integer dtype
+    or a value outside int32 raises ValueError (a value inside int32 but outside [0, C) is the device's to count)."""
 
     def __init__(self, logits, labels, c0=0, num_classes=None, n_bins=15):
         _require_cuda(logits)
@@ -875,6 +876,17 @@ class CalibrationEvaluator:
         labels = torch.as_tensor(labels)
         if labels.shape != (self.rows,):
             raise ValueError(f"labels must have shape ({self.rows},), not {tuple(labels.shape)}")
+        # the int32 conversion below wraps (2**32 + 3 -> 3) and truncates (1.7 -> 1): a label the device would have
+        # counted as bad must not turn into a valid class on the way there
+        if labels.dtype in (getattr(torch, "uint16", None), getattr(torch, "uint32", None)):
+            labels = labels.to(torch.int64)
+        if labels.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError(f"labels must be integer class indices, not a {labels.dtype} tensor")
+        if labels.dtype == torch.int64 and self.rows:
+            lo, hi = (int(v) for v in torch.aminmax(labels))
+            for v in (lo, hi):
+                if not -2 ** 31 <= v < 2 ** 31:
+                    raise ValueError(f"label {v} does not fit the device's int32 labels")
         self.labels = labels.to(logits.device, torch.int32).contiguous()
         self.n_bins = int(n_bins)
         # the reference's bin edges: torch.linspace(0, 1, n_bins + 1) in fp32 on the CPU (temperature_scaling.py:96)
