@@ -8,18 +8,21 @@
 //                        v_mfma_f32_32x32x16_f16, operands global -> LDS by global_load_lds_dwordx4 in 128-BYTE rows
 //                        (a K-step of 64 halves is one line), two stages, XOR-swizzled LDS rows (conflict-free
 //                        ds_read_b128), epilogue staged per wave so that rows leave as full lines.
-//   layernorm_f16_kernel one wave per row, fp32 mean / variance (CLIP's LayerNorm computes in fp32), eps inside sqrt.
+//   gemm16_f16_kernel    the same two tile sizes on v_mfma_f32_16x16x32_f16 (the default 128 x 128 instance).
+//                        All share gemm_tile (XCD remap -> m0 / n0) and gemm_epilogue (bias, act, rounding, staging, the
+//                        full-line store); a kernel body is its DMA, its K-loop and its accumulator map.
+//   layernorm_kernel     one wave per row, fp32 mean / variance (CLIP's LayerNorm computes in fp32), eps inside sqrt.
 //   attention_f16_kernel one WAVE per (sequence, head): S <= 96 tokens, head dim 64: K Q^T and V^T P^T on the matrix
 //                        cores with operands loaded straight into the MFMA layout, fp32 softmax in registers.
 //   attention_long_f16_kernel  any S (ViT-L/14@336: 577 tokens), non-causal: 4 waves x 32 queries of one (sequence, head)
 //                        share each 64-key K / V tile in LDS; the same two products, online softmax with the exact running
 //                        maximum.
-//   vit_tokens_f16_kernel / text_tokens_f16_kernel / patchify_f16_kernel / patchify_pad_f16_kernel (any patch size, rows
-//   padded with zeros to the GEMM's K-step) / gather_rows_f16_kernel: token assembly.
+//   vit_tokens_kernel / text_tokens_f16_kernel / patchify_f16_kernel / patchify_pad_f16_kernel (any patch size, rows
+//   padded with zeros to the GEMM's K-step) / gather_rows_kernel: token assembly.
 // The DINOv2 tower of FD-DINOv2 (dinov2_hip.HipDino) keeps its residual stream in fp32 -- what torch.autocast(fp16) computes:
 //   the GEMM kernels' epilogue is a template parameter (EPI_F16 above, EPI_RES32: out32 = res32 + scale * (A W^T + bias), fp32
-//   after the accumulator), act 2 (tise_gemm_f16_act only) is the exact (erf) GELU, and layernorm_f32_kernel / vit_tokens_f32_kernel /
-//   gather_rows_f32_kernel are the fp32-stream siblings of the kernels above.
+//   after the accumulator), act 2 (tise_gemm_f16_act only) is the exact (erf) GELU, and layernorm_kernel / vit_tokens_kernel /
+//   gather_rows_kernel are templates over their element types: the float instances are the fp32 stream's.
 #include <hip/hip_fp16.h>
 #include <cstdlib>
 #include "common.h"
@@ -88,6 +91,121 @@ __device__ __forceinline__ void gemm_store_res32(const GemmArgs& p, const unsign
     }
 }
 
+// The tile of a workgroup: blockIdx.x is remapped so that the workgroups one XCD receives (every eighth) are neighbours
+// in the tile order, then row-major over the N tiles.
+struct GemmTile { int m0, n0; };
+__device__ __forceinline__ GemmTile gemm_tile(unsigned bid, unsigned nwg, int N, int BM, int BN) {
+    const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+    bid = ((xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const unsigned tiles_n = (unsigned)(N + BN - 1) / BN;
+    return {(int)(bid / tiles_n) * BM, (int)(bid % tiles_n) * BN};
+}
+
+// The epilogue of every GEMM kernel: one 32 x 64 block of a wave's accumulators goes through the wave's 32 staging rows
+// (at the front of the finished operand stages) and leaves as full lines.  The kernel supplies only the map of its MFMA
+// shape: frag(g, h) = piece h (of NH) of column group g (of NG): the four accumulator values of this lane at row `row`
+// and columns `col` .. col + 3 of the block; col depends on g alone, so one bias fetch serves the NH pieces of a group.
+// The bias is added per element inside the act loop: added to a whole piece in front of the act branches it measured
+// 1-6 % slower on the tower GEMMs.
+//   EPI_F16    fp16(act(acc + bias)) into rows of GM_PITCH16 bytes, then 8 lanes per row, eight rows per pass: 16 bytes
+//              per lane [+ the fp16 residual, added in fp32 and rounded a second time]
+//   EPI_RES32  acc + bias in fp32 into rows of GM_PITCH32 bytes, then gemm_store_res32
+// Nothing beyond M / N is stored.
+struct GemmFrag { int row, col; float4_t v; };
+constexpr int GM_PITCH16 = 144;
+template <int EPI, int NG, int NH, typename Frag>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, unsigned char* lds, int wave, int lane, int mrow0, int ncol0,
+                                              Frag frag) {
+    unsigned char* st = lds + wave * (32 * (EPI == EPI_RES32 ? GM_PITCH32 : GM_PITCH16));
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int cl = frag(g, 0).col;
+        half4_t bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+        if (p.bias && ncol0 + cl < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + ncol0 + cl);
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            const GemmFrag f = frag(g, h);
+            if constexpr (EPI == EPI_RES32) {
+                float4_t v;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = f.v[k] + (float)bq[k];
+                *reinterpret_cast<float4_t*>(st + f.row * GM_PITCH32 + cl * 4) = v;
+            } else {
+                half4_t hv;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float v = f.v[k] + (float)bq[k];
+                    if (p.act == 1) v = v / (1.0f + __expf(-1.702f * v));
+                    else if (p.act == 2) v = gelu_erf(v);
+                    hv[k] = (_Float16)v;
+                }
+                *reinterpret_cast<half4_t*>(st + f.row * GM_PITCH16 + cl * 2) = hv;
+            }
+        }
+    }
+    if constexpr (EPI == EPI_RES32) {
+        gemm_store_res32(p, st, lane, mrow0, ncol0);
+    } else {
+#pragma unroll
+        for (int pass = 0; pass < 4; ++pass) {
+            const int r = pass * 8 + (lane >> 3), ch = lane & 7;
+            const int m = mrow0 + r, n = ncol0 + ch * 8;
+            half8_t v = *reinterpret_cast<const half8_t*>(st + r * GM_PITCH16 + ch * 16);
+            if (m < p.M && n < p.N) {
+                if (p.res) {
+                    const half8_t rr = *reinterpret_cast<const half8_t*>(p.res + (long long)m * p.ldr + n);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) v[k] = (_Float16)((float)v[k] + (float)rr[k]);
+                }
+                *reinterpret_cast<half8_t*>(p.out + (long long)m * p.ldo + n) = v;
+            }
+        }
+    }
+}
+
+// the map of the 32x32x16 shape: accumulator j (32 columns) of a 32-row block holds row lane & 31 and, in registers
+// 4 q .. 4 q + 3, columns 8 q + 4 (lane >> 5) ..: eight column groups g = 4 j + q of one piece
+__device__ __forceinline__ auto gemm32_frag(const float16_t (&acc)[2], int lane) {
+    return [&acc, lane](int g, int) {
+        const float16_t& a = acc[g >> 2];
+        const int q = 4 * (g & 3);
+        return GemmFrag{lane & 31, 8 * g + 4 * (lane >> 5), float4_t{a[q], a[q + 1], a[q + 2], a[q + 3]}};
+    };
+}
+
+// Operand DMA of the two 32x32x16 kernels (in scope: p, lds, m0, n0, wave, lane, A_BYTES): a wave fetches rows 32 wave .. + 31
+// of both operands of a stage as four pieces of 8 rows x 128 B each (lane -> row lane >> 3, 16-byte chunk lane & 7,
+// XOR-swizzled).  Rows beyond M / N read the zero page and do not advance.  Macros, not functions: through a function the
+// compiler groups the eight loads of a K-step and pads them with s_nop instead of placing the pointer updates between them.
+#define GM32_DMA_SETUP                                                                                    \
+    const unsigned char* zp = g_clip_zero_page;                                                           \
+    const unsigned char* pa[4];                                                                           \
+    const unsigned char* pw[4];                                                                           \
+    int ia[4], iw[4];                                                                                     \
+    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                        \
+        const int r = (4 * wave + g) * 8 + (lane >> 3);                                                   \
+        const int c = (lane & 7) ^ ((r >> 1) & 7);                                                        \
+        const bool oka = m0 + r < p.M, okw = n0 + r < p.N;                                                \
+        pa[g] = oka ? reinterpret_cast<const unsigned char*>(p.a + (long long)(m0 + r) * p.lda + c * 8) : zp;  \
+        ia[g] = oka ? 128 : 0;                                                                            \
+        pw[g] = okw ? reinterpret_cast<const unsigned char*>(p.w + (long long)(n0 + r) * p.ldw + c * 8) : zp;  \
+        iw[g] = okw ? 128 : 0;                                                                            \
+    }
+// one K-step (128 bytes of every row) into the stage at byte SOFF
+#define GM32_DMA_ISSUE(SOFF)                                                                              \
+    {                                                                                                     \
+        _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                    \
+            const unsigned char* s_ = pa[g];                                                               \
+            __builtin_amdgcn_global_load_lds(s_, (lds_ptr_t)(lds + (SOFF) + (4 * wave + g) * 1024), 16, 0, 0);            \
+            pa[g] = s_ + ia[g];                                                                            \
+        }                                                                                                  \
+        _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                    \
+            const unsigned char* s_ = pw[g];                                                               \
+            __builtin_amdgcn_global_load_lds(s_, (lds_ptr_t)(lds + (SOFF) + A_BYTES + (4 * wave + g) * 1024), 16, 0, 0);  \
+            pw[g] = s_ + iw[g];                                                                            \
+        }                                                                                                  \
+    }
+
 // 128 x 128 x 64 tiles: four waves (2 x 2 of 64 x 64), TWO LDS stages of 32 KB, two workgroups per CU -- the structure of
 // the convolution kernel (conv_split.hip).  The first version used 256 x 128 tiles with eight waves and three stages
 // (144 KB of LDS: one workgroup per CU), so the DMA latency in front of a tile's first K-step and its epilogue were
@@ -102,43 +220,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmArgs p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    const unsigned tiles_n = (unsigned)(p.N + BN - 1) / BN;
-    const unsigned nwg = gridDim.x;
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = ((xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int m0 = (int)(bid / tiles_n) * BM;
-    const int n0 = (int)(bid % tiles_n) * BN;
-    const unsigned char* zp = g_clip_zero_page;
-    // DMA pieces (8 rows x 128 B): this wave fetches rows 32*wave .. +31 of both operands
-    const unsigned char* pa[4];
-    const unsigned char* pw[4];
-    int ia[4], iw[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int r = (4 * wave + g) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        const bool oka = m0 + r < p.M, okw = n0 + r < p.N;
-        pa[g] = oka ? reinterpret_cast<const unsigned char*>(p.a + (long long)(m0 + r) * p.lda + c * 8) : zp;
-        ia[g] = oka ? 128 : 0;
-        pw[g] = okw ? reinterpret_cast<const unsigned char*>(p.w + (long long)(n0 + r) * p.ldw + c * 8) : zp;
-        iw[g] = okw ? 128 : 0;
-    }
-#define GS_ISSUE(SOFF)                                                                                    \
-    {                                                                                                     \
-        _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                    \
-            const unsigned char* s_ = pa[g];                                                               \
-            __builtin_amdgcn_global_load_lds(s_, (lds_ptr_t)(lds + (SOFF) + (4 * wave + g) * 1024), 16, 0, 0);            \
-            pa[g] = s_ + ia[g];                                                                            \
-        }                                                                                                  \
-        _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                    \
-            const unsigned char* s_ = pw[g];                                                               \
-            __builtin_amdgcn_global_load_lds(s_, (lds_ptr_t)(lds + (SOFF) + A_BYTES + (4 * wave + g) * 1024), 16, 0, 0);  \
-            pw[g] = s_ + iw[g];                                                                            \
-        }                                                                                                  \
-    }
+    const auto [m0, n0] = gemm_tile(blockIdx.x, gridDim.x, p.N, BM, BN);
+    GM32_DMA_SETUP
     float16_t acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -186,18 +269,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmArgs p) {
     }
     half8_t h_a[2], h_b[2];
     const int nsteps = p.K / GM_BK;
-    GS_ISSUE(0)
+    GM32_DMA_ISSUE(0)
     int step = 0;
     for (; step + 1 < nsteps; step += 2) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         GS_HEAD(0)
-        GS_ISSUE(STAGE)
+        GM32_DMA_ISSUE(STAGE)
         GS_COMPUTE(0)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         GS_HEAD(STAGE)
-        if (step + 2 < nsteps) GS_ISSUE(0)
+        if (step + 2 < nsteps) GM32_DMA_ISSUE(0)
         GS_COMPUTE(STAGE)
     }
     if (step < nsteps) {
@@ -207,60 +290,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_kernel(const GemmArgs p) {
         GS_COMPUTE(0)
     }
     __syncthreads();
-    constexpr int PITCH = 144;
-    unsigned char* st = lds + wave * (32 * (EPI == EPI_RES32 ? GM_PITCH32 : PITCH));
-    const int ncol0 = n0 + wn * 64;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        if constexpr (EPI == EPI_RES32) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int cl = j * 32 + 8 * g + 4 * (lane >> 5);
-                    const int n = ncol0 + cl;
-                    half4_t bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
-                    if (p.bias && n < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + n);
-                    float4_t f;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) f[k] = acc[i][j][4 * g + k] + (float)bq[k];
-                    *reinterpret_cast<float4_t*>(st + (lane & 31) * GM_PITCH32 + cl * 4) = f;
-                }
-            gemm_store_res32(p, st, lane, m0 + wm * 64 + i * 32, ncol0);
-            continue;
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int cl = j * 32 + 8 * g + 4 * (lane >> 5);
-                const int n = ncol0 + cl;
-                half4_t h, bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
-                if (p.bias && n < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + n);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float v = acc[i][j][4 * g + k] + (float)bq[k];
-                    if (p.act == 1) v = v / (1.0f + __expf(-1.702f * v));
-                    else if (p.act == 2) v = gelu_erf(v);
-                    h[k] = (_Float16)v;
-                }
-                *reinterpret_cast<half4_t*>(st + (lane & 31) * PITCH + cl * 2) = h;
-            }
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-            const int r = pass * 8 + (lane >> 3), ch = lane & 7;
-            const int m = m0 + wm * 64 + i * 32 + r, n = ncol0 + ch * 8;
-            half8_t v = *reinterpret_cast<const half8_t*>(st + r * PITCH + ch * 16);
-            if (m < p.M && n < p.N) {
-                if (p.res) {
-                    const half8_t rr = *reinterpret_cast<const half8_t*>(p.res + (long long)m * p.ldr + n);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = (_Float16)((float)v[k] + (float)rr[k]);
-                }
-                *reinterpret_cast<half8_t*>(p.out + (long long)m * p.ldo + n) = v;
-            }
-        }
-    }
+    for (int i = 0; i < 2; ++i)
+        gemm_epilogue<EPI, 8, 1>(p, lds, wave, lane, m0 + wm * 64 + i * 32, n0 + wn * 64, gemm32_frag(acc[i], lane));
 }
 
 // 256 x 256 x 64 tiles for the large GEMMs (at least four tiles per CU): eight waves (2 x 4, 128 x 64 per wave), two
@@ -276,42 +308,8 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_big_kernel(const GemmArgs p) 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;                   // 2 x 4 waves of 128 x 64
-    const unsigned tiles_n = (unsigned)(p.N + BN - 1) / BN;
-    const unsigned nwg = gridDim.x;
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = ((xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int m0 = (int)(bid / tiles_n) * BM;
-    const int n0 = (int)(bid % tiles_n) * BN;
-    const unsigned char* zp = g_clip_zero_page;
-    const unsigned char* pa[4];
-    const unsigned char* pw[4];
-    int ia[4], iw[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int r = (4 * wave + g) * 8 + (lane >> 3);        // 8 waves x 4 pieces x 8 rows = 256 rows of each operand
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        const bool oka = m0 + r < p.M, okw = n0 + r < p.N;
-        pa[g] = oka ? reinterpret_cast<const unsigned char*>(p.a + (long long)(m0 + r) * p.lda + c * 8) : zp;
-        ia[g] = oka ? 128 : 0;
-        pw[g] = okw ? reinterpret_cast<const unsigned char*>(p.w + (long long)(n0 + r) * p.ldw + c * 8) : zp;
-        iw[g] = okw ? 128 : 0;
-    }
-#define GB_ISSUE(SOFF)                                                                                    \
-    {                                                                                                     \
-        _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                    \
-            const unsigned char* s_ = pa[g];                                                               \
-            __builtin_amdgcn_global_load_lds(s_, (lds_ptr_t)(lds + (SOFF) + (4 * wave + g) * 1024), 16, 0, 0);            \
-            pa[g] = s_ + ia[g];                                                                            \
-        }                                                                                                  \
-        _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                    \
-            const unsigned char* s_ = pw[g];                                                               \
-            __builtin_amdgcn_global_load_lds(s_, (lds_ptr_t)(lds + (SOFF) + A_BYTES + (4 * wave + g) * 1024), 16, 0, 0);  \
-            pw[g] = s_ + iw[g];                                                                            \
-        }                                                                                                  \
-    }
+    const auto [m0, n0] = gemm_tile(blockIdx.x, gridDim.x, p.N, BM, BN);
+    GM32_DMA_SETUP
     float16_t acc[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -347,20 +345,20 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_big_kernel(const GemmArgs p) 
     }
     half8_t a_[2][4], b_[2][2];
     const int nsteps = p.K / GM_BK;
-    GB_ISSUE(0)
+    GM32_DMA_ISSUE(0)
     int step = 0;
     for (; step + 1 < nsteps; step += 2) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         GB_READS(0, 0, 0)
         __builtin_amdgcn_sched_barrier(0);
-        GB_ISSUE(STAGE)
+        GM32_DMA_ISSUE(STAGE)
         GB_COMPUTE(0)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         GB_READS(0, STAGE, 0)
         __builtin_amdgcn_sched_barrier(0);
-        if (step + 2 < nsteps) GB_ISSUE(0)
+        if (step + 2 < nsteps) GM32_DMA_ISSUE(0)
         GB_COMPUTE(STAGE)
     }
     if (step < nsteps) {
@@ -370,61 +368,13 @@ __global__ __launch_bounds__(512, 1) void gemm_f16_big_kernel(const GemmArgs p) 
         GB_COMPUTE(0)
     }
     __syncthreads();
-    constexpr int PITCH = 144;
-    unsigned char* st = lds + wave * (32 * (EPI == EPI_RES32 ? GM_PITCH32 : PITCH));
-    const int ncol0 = n0 + wn * 64;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if constexpr (EPI == EPI_RES32) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int cl = j * 32 + 8 * g + 4 * (lane >> 5);
-                    const int n = ncol0 + cl;
-                    half4_t bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
-                    if (p.bias && n < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + n);
-                    float4_t f;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) f[k] = acc[i][j][4 * g + k] + (float)bq[k];
-                    *reinterpret_cast<float4_t*>(st + (lane & 31) * GM_PITCH32 + cl * 4) = f;
-                }
-            gemm_store_res32(p, st, lane, m0 + wm * 128 + i * 32, ncol0);
-            continue;
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int cl = j * 32 + 8 * g + 4 * (lane >> 5);
-                const int n = ncol0 + cl;
-                half4_t h, bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
-                if (p.bias && n < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + n);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float v = acc[i][j][4 * g + k] + (float)bq[k];
-                    if (p.act == 1) v = v / (1.0f + __expf(-1.702f * v));
-                    else if (p.act == 2) v = gelu_erf(v);
-                    h[k] = (_Float16)v;
-                }
-                *reinterpret_cast<half4_t*>(st + (lane & 31) * PITCH + cl * 2) = h;
-            }
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-            const int r = pass * 8 + (lane >> 3), ch = lane & 7;
-            const int m = m0 + wm * 128 + i * 32 + r, n = ncol0 + ch * 8;
-            half8_t v = *reinterpret_cast<const half8_t*>(st + r * PITCH + ch * 16);
-            if (m < p.M && n < p.N) {
-                if (p.res) {
-                    const half8_t rr = *reinterpret_cast<const half8_t*>(p.res + (long long)m * p.ldr + n);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = (_Float16)((float)v[k] + (float)rr[k]);
-                }
-                *reinterpret_cast<half8_t*>(p.out + (long long)m * p.ldo + n) = v;
-            }
-        }
-    }
+    for (int i = 0; i < 4; ++i)
+        gemm_epilogue<EPI, 8, 1>(p, lds, wave, lane, m0 + wm * 128 + i * 32, n0 + wn * 64, gemm32_frag(acc[i], lane));
 }
+
+#undef GM32_DMA_SETUP
+#undef GM32_DMA_ISSUE
 
 // ------------------------------------------------------------------------------------------------
 // Round 4: both GEMM kernels on v_mfma_f32_16x16x32_f16 (gemm16_f16_kernel<BIG>).  Same tiles, LDS images, DMA and
@@ -446,15 +396,7 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : 2) void gemm16_f16_kerne
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = BIG ? (wave >> 2) : (wave >> 1), wn = BIG ? (wave & 3) : (wave & 1);
-    const unsigned tiles_n = (unsigned)(p.N + BN - 1) / BN;
-    const unsigned nwg = gridDim.x;
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = ((xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int m0 = (int)(bid / tiles_n) * BM;
-    const int n0 = (int)(bid % tiles_n) * BN;
+    const auto [m0, n0] = gemm_tile(blockIdx.x, gridDim.x, p.N, BM, BN);
     // DMA pieces (8 rows x 128 B): this wave fetches rows 32 wave .. +31 of both operands.  Source = one scalar base per
     // operand (advanced by 128 bytes per K-step on the scalar unit) + a constant 32-bit byte offset per lane and piece (the
     // `saddr` form of the instruction: no per-step vector arithmetic, 8 address registers instead of 24).  Rows beyond M
@@ -547,86 +489,61 @@ __global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : 2) void gemm16_f16_kerne
 #undef G16_ISSUE
 #undef G16_READS
 #undef G16_COMPUTE
-    // epilogue: 32 rows x 64 columns at a time through the wave's staging rows (as the kernels above); the accumulator
-    // block (i, j) holds row m = 16 i + (lane & 15) and the four columns n = 16 j + 4 (lane >> 4) + k of this lane
-    constexpr int PITCH = 144;
-    unsigned char* st = lds + wave * (32 * (EPI == EPI_RES32 ? GM_PITCH32 : PITCH));
-    const int ncol0 = n0 + wn * 64;
+    // epilogue: the accumulator block (i, j) holds row m = 16 i + (lane & 15) and the four columns n = 16 j + 4 (lane >> 4) + k
+    // of this lane: per 32 rows, four column groups of two pieces
 #pragma unroll
-    for (int i2 = 0; i2 < MI / 2; ++i2) {
-        if constexpr (EPI == EPI_RES32) {
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                const int cl = 16 * j + 4 * (lane >> 4);
-                const int n = ncol0 + cl;
-                half4_t bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
-                if (p.bias && n < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + n);
-#pragma unroll
-                for (int h2 = 0; h2 < 2; ++h2) {
-                    float4_t f;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) f[k] = acc[2 * i2 + h2][j][k] + (float)bq[k];
-                    *reinterpret_cast<float4_t*>(st + (16 * h2 + (lane & 15)) * GM_PITCH32 + cl * 4) = f;
-                }
-            }
-            gemm_store_res32(p, st, lane, m0 + wm * WM + i2 * 32, ncol0);
-            continue;
-        }
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const int cl = 16 * j + 4 * (lane >> 4);
-            const int n = ncol0 + cl;
-            half4_t bq = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
-            if (p.bias && n < p.N) bq = *reinterpret_cast<const half4_t*>(p.bias + n);
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                half4_t h;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float v = acc[2 * i2 + h2][j][k] + (float)bq[k];
-                    if (p.act == 1) v = v / (1.0f + __expf(-1.702f * v));
-                    else if (p.act == 2) v = gelu_erf(v);
-                    h[k] = (_Float16)v;
-                }
-                *reinterpret_cast<half4_t*>(st + (16 * h2 + (lane & 15)) * PITCH + cl * 2) = h;
-            }
-        }
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-            const int r = pass * 8 + (lane >> 3), ch = lane & 7;
-            const int m = m0 + wm * WM + i2 * 32 + r, n = ncol0 + ch * 8;
-            half8_t v = *reinterpret_cast<const half8_t*>(st + r * PITCH + ch * 16);
-            if (m < p.M && n < p.N) {
-                if (p.res) {
-                    const half8_t rr = *reinterpret_cast<const half8_t*>(p.res + (long long)m * p.ldr + n);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = (_Float16)((float)v[k] + (float)rr[k]);
-                }
-                *reinterpret_cast<half8_t*>(p.out + (long long)m * p.ldo + n) = v;
-            }
-        }
-    }
+    for (int i2 = 0; i2 < MI / 2; ++i2)
+        gemm_epilogue<EPI, NI, 2>(p, lds, wave, lane, m0 + wm * WM + i2 * 32, n0 + wn * 64, [&](int j, int h) {
+            return GemmFrag{16 * h + (lane & 15), 16 * j + 4 * (lane >> 4), acc[2 * i2 + h][j]};
+        });
 }
+
+// eight consecutive elements of a row, moved as 16-byte pieces (one of eight halves, two of four floats), read and
+// written as fp32
+template <typename T> struct Row8;
+template <> struct Row8<_Float16> {
+    half8_t h = {};
+    __device__ void load(const _Float16* src) { h = *reinterpret_cast<const half8_t*>(src); }
+    __device__ void store(_Float16* dst) const { *reinterpret_cast<half8_t*>(dst) = h; }
+    __device__ float get(int e) const { return (float)h[e]; }
+    __device__ void set(int e, float f) { h[e] = (_Float16)f; }
+};
+template <> struct Row8<float> {
+    float4_t q[2] = {};
+    __device__ void load(const float* src) {
+        q[0] = *reinterpret_cast<const float4_t*>(src);
+        q[1] = *reinterpret_cast<const float4_t*>(src + 4);
+    }
+    __device__ void store(float* dst) const {
+        *reinterpret_cast<float4_t*>(dst) = q[0];
+        *reinterpret_cast<float4_t*>(dst + 4) = q[1];
+    }
+    __device__ float get(int e) const { return q[e >> 2][e & 3]; }
+    __device__ void set(int e, float f) { q[e >> 2][e & 3] = f; }
+};
 
 // one wave per row: y = (x - mean) / sqrt(var + eps) * gamma + beta, statistics in fp32 (two passes over registers).
 // 16-byte loads and stores: lane l holds columns 8l .. 8l+7 and 512 + 8l .. (C <= 1024, C % 8 == 0) -- the first
 // version moved 2 bytes per lane and instruction and ran at 2 TB/s.
-__global__ __launch_bounds__(256) void layernorm_f16_kernel(const _Float16* __restrict__ x, long long ldx,
-                                                            const _Float16* __restrict__ gamma, const _Float16* __restrict__ beta,
-                                                            _Float16* __restrict__ out, long long ldo, int rows, int C, float eps) {
+// InT = _Float16 (x, gamma, beta and out in fp16): the CLIP towers, rsqrtf.  InT = float: the fp32 residual stream of the
+// DINOv2 tower (dinov2_hip.HipDino), 1 / sqrtf; OutT = _Float16 feeds the next GEMM, float is the tower's feature row.
+template <typename InT, typename OutT>
+__global__ __launch_bounds__(256) void layernorm_kernel(const InT* __restrict__ x, long long ldx, const InT* __restrict__ gamma,
+                                                        const InT* __restrict__ beta, OutT* __restrict__ out, long long ldo,
+                                                        int rows, int C, float eps) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const _Float16* xr = x + (long long)row * ldx;
+    const InT* xr = x + (long long)row * ldx;
     float v[2][8];
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int c = 512 * k + 8 * lane;
-        half8_t h = {};
-        if (c < C) h = *reinterpret_cast<const half8_t*>(xr + c);
+        Row8<InT> r;
+        if (c < C) r.load(xr + c);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { v[k][e] = (float)h[e]; s += v[k][e]; }
+        for (int e = 0; e < 8; ++e) { v[k][e] = r.get(e); s += v[k][e]; }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
@@ -641,18 +558,19 @@ __global__ __launch_bounds__(256) void layernorm_f16_kernel(const _Float16* __re
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
-    const float rstd = rsqrtf(q / (float)C + eps);
-    _Float16* o = out + (long long)row * ldo;
+    const float rstd = sizeof(InT) == 2 ? rsqrtf(q / (float)C + eps) : 1.0f / sqrtf(q / (float)C + eps);
+    OutT* o = out + (long long)row * ldo;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int c = 512 * k + 8 * lane;
         if (c < C) {
-            const half8_t g = *reinterpret_cast<const half8_t*>(gamma + c);
-            const half8_t bb = *reinterpret_cast<const half8_t*>(beta + c);
-            half8_t r;
+            Row8<InT> g, bb;
+            g.load(gamma + c);
+            bb.load(beta + c);
+            Row8<OutT> r;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) r[e] = (_Float16)((v[k][e] - mean) * rstd * (float)g[e] + (float)bb[e]);
-            *reinterpret_cast<half8_t*>(o + c) = r;
+            for (int e = 0; e < 8; ++e) r.set(e, (v[k][e] - mean) * rstd * g.get(e) + bb.get(e));
+            r.store(o + c);
         }
     }
 }
@@ -981,9 +899,11 @@ __global__ __launch_bounds__(256) void patchify_pad_f16_kernel(const _Float16* _
 }
 
 // x[b][0] = class_emb + pos[0];  x[b][1 + p] = patch_out[b * NP + p] + pos[1 + p]          (width W)
-__global__ __launch_bounds__(256) void vit_tokens_f16_kernel(const _Float16* __restrict__ patch_out, const _Float16* __restrict__ cls,
-                                                             const _Float16* __restrict__ pos, int B, int NP, int W,
-                                                             _Float16* __restrict__ x) {
+// patch_out is the fp16 output of the patch GEMM; class row, position table and tokens are T: _Float16 in the CLIP towers,
+// float in the fp32 stream of the DINOv2 tower.  One fp32 add per element.
+template <typename T>
+__global__ __launch_bounds__(256) void vit_tokens_kernel(const _Float16* __restrict__ patch_out, const T* __restrict__ cls,
+                                                         const T* __restrict__ pos, int B, int NP, int W, T* __restrict__ x) {
     const long long total = (long long)B * (NP + 1) * W;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const int c = (int)(e % W);
@@ -991,7 +911,7 @@ __global__ __launch_bounds__(256) void vit_tokens_f16_kernel(const _Float16* __r
         const int s = (int)(t % (NP + 1));
         const long long b = t / (NP + 1);
         const float base = s == 0 ? (float)cls[c] : (float)patch_out[(b * NP + s - 1) * W + c];
-        x[e] = (_Float16)(base + (float)pos[(long long)s * W + c]);
+        x[e] = (T)(base + (float)pos[(long long)s * W + c]);
     }
 }
 
@@ -1009,102 +929,9 @@ __global__ __launch_bounds__(256) void text_tokens_f16_kernel(const int* __restr
 }
 
 // out[i] = x[index[i]]  (rows of width W; the class token of every image / the end-of-text token of every caption)
-__global__ __launch_bounds__(256) void gather_rows_f16_kernel(const _Float16* __restrict__ x, const long long* __restrict__ index,
-                                                              long long n, int W, _Float16* __restrict__ out) {
-    const long long total = n * W;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const int c = (int)(e % W);
-        const long long i = e / W;
-        out[e] = x[index[i] * W + c];
-    }
-}
-
-// ---- the fp32 residual stream of the DINOv2 tower (dinov2_hip.HipDino) ---------------------------------------------------
-// layernorm_f16_kernel's sibling on an fp32 row with fp32 gamma / beta: one wave per row, lane l holds columns 8l .. 8l+7
-// and 512 + 8l .. (two 16-byte loads each), two passes over registers.  OutT = _Float16 feeds the next GEMM, float is the
-// tower's feature row.
-template <typename OutT>
-__global__ __launch_bounds__(256) void layernorm_f32_kernel(const float* __restrict__ x, long long ldx, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, OutT* __restrict__ out, long long ldo,
-                                                            int rows, int C, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* xr = x + (long long)row * ldx;
-    float v[2][8];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int c = 512 * k + 8 * lane;
-        float4_t lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
-        if (c < C) {
-            lo = *reinterpret_cast<const float4_t*>(xr + c);
-            hi = *reinterpret_cast<const float4_t*>(xr + c + 4);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { v[k][e] = lo[e]; v[k][4 + e] = hi[e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[k][e];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    const float mean = s / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (512 * k + 8 * lane < C) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float d = v[k][e] - mean; q += d * d; }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
-    const float rstd = 1.0f / sqrtf(q / (float)C + eps);
-    OutT* o = out + (long long)row * ldo;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int c = 512 * k + 8 * lane;
-        if (c < C) {
-            float y[8];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float4_t g = *reinterpret_cast<const float4_t*>(gamma + c + 4 * h);
-                const float4_t bb = *reinterpret_cast<const float4_t*>(beta + c + 4 * h);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) y[4 * h + e] = (v[k][4 * h + e] - mean) * rstd * g[e] + bb[e];
-            }
-            if constexpr (sizeof(OutT) == 2) {
-                half8_t r;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) r[e] = (_Float16)y[e];
-                *reinterpret_cast<half8_t*>(o + c) = r;
-            } else {
-                *reinterpret_cast<float4_t*>(o + c) = float4_t{y[0], y[1], y[2], y[3]};
-                *reinterpret_cast<float4_t*>(o + c + 4) = float4_t{y[4], y[5], y[6], y[7]};
-            }
-        }
-    }
-}
-
-// x[b][0] = cls + pos[0];  x[b][1 + p] = float(patch_out[b * NP + p]) + pos[1 + p]: fp16 rows of the patch GEMM, fp32 class
-// row and position table, fp32 tokens; one fp32 add per element
-__global__ __launch_bounds__(256) void vit_tokens_f32_kernel(const _Float16* __restrict__ patch_out, const float* __restrict__ cls,
-                                                             const float* __restrict__ pos, int B, int NP, int W,
-                                                             float* __restrict__ x) {
-    const long long total = (long long)B * (NP + 1) * W;
-    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
-        const int c = (int)(e % W);
-        const long long t = e / W;
-        const int s = (int)(t % (NP + 1));
-        const long long b = t / (NP + 1);
-        const float base = s == 0 ? cls[c] : (float)patch_out[(b * NP + s - 1) * W + c];
-        x[e] = base + pos[(long long)s * W + c];
-    }
-}
-
-// out[i] = x[index[i]]  (fp32 rows of width W: the class token of every image)
-__global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float* __restrict__ x, const long long* __restrict__ index,
-                                                              long long n, int W, float* __restrict__ out) {
+template <typename T>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ x, const long long* __restrict__ index, long long n,
+                                                          int W, T* __restrict__ out) {
     const long long total = n * W;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
         const int c = (int)(e % W);
@@ -1166,27 +993,78 @@ int gemm_launch(const GemmArgs& p, void* stream) {
     return TISE_OK;
 }
 
-// tise_gemm_f16 (act 0 .. 1, as it always was) and tise_gemm_f16_act (act 0 .. 2): one check, one launch
-int gemm_f16_entry(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* res_dev,
-                   int64_t ldr, void* out_dev, int64_t ldo, int m, int n, int k, int act, int max_act, void* stream) {
-    // the kernels move a / w rows by 16-byte LDS-DMA, res / out in 16-byte pieces and bias in 8-byte pieces: strides
-    // below the row length and misaligned pointers are refused here, before anything reaches the device
-    if (!a_dev || !w_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || k % GM_BK != 0 || n % 8 != 0 || lda % 8 != 0 || ldw % 8 != 0 ||
-        ldo % 8 != 0 || (res_dev && ldr % 8 != 0) || act < 0 || act > max_act || lda < k || ldw < k || ldo < n ||
-        (res_dev && ldr < n) ||
-        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev) | reinterpret_cast<uintptr_t>(out_dev) |
-          reinterpret_cast<uintptr_t>(res_dev)) & 15) != 0 ||
+// What every GEMM entry point asks of a / w / bias and the shape, and their half of the arguments: the kernels move a / w
+// rows by 16-byte LDS-DMA and bias in 8-byte pieces, so strides below the row length and misaligned pointers are refused
+// (false) before anything reaches the device.
+bool gemm_operands(GemmArgs& p, const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, int m, int n, int k) {
+    if (!a_dev || !w_dev || m < 0 || n <= 0 || k <= 0 || k % GM_BK != 0 || n % 8 != 0 || lda % 8 != 0 || ldw % 8 != 0 || lda < k ||
+        ldw < k || ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev)) & 15) != 0 ||
         (reinterpret_cast<uintptr_t>(bias_dev) & 7) != 0)
-        return TISE_ERR_INVALID_ARG;
-    if (m == 0) return TISE_OK;
-    GemmArgs p = {};
+        return false;
     p.a = reinterpret_cast<const _Float16*>(a_dev); p.lda = lda;
     p.w = reinterpret_cast<const _Float16*>(w_dev); p.ldw = ldw;
     p.bias = reinterpret_cast<const _Float16*>(bias_dev);
+    p.M = m; p.N = n; p.K = k;
+    return true;
+}
+
+// tise_gemm_f16 (act 0 .. 1, as it always was) and tise_gemm_f16_act (act 0 .. 2): one check, one launch
+int gemm_f16_entry(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* res_dev,
+                   int64_t ldr, void* out_dev, int64_t ldo, int m, int n, int k, int act, int max_act, void* stream) {
+    // res / out move in 16-byte pieces of eight halves
+    GemmArgs p = {};
+    if (!gemm_operands(p, a_dev, lda, w_dev, ldw, bias_dev, m, n, k) || !out_dev || ldo % 8 != 0 || (res_dev && ldr % 8 != 0) ||
+        act < 0 || act > max_act || ldo < n || (res_dev && ldr < n) ||
+        ((reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(res_dev)) & 15) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (m == 0) return TISE_OK;
     p.res = reinterpret_cast<const _Float16*>(res_dev); p.ldr = ldr;
     p.out = reinterpret_cast<_Float16*>(out_dev); p.ldo = ldo;
-    p.M = m; p.N = n; p.K = k; p.act = act;
+    p.act = act;
     return gemm_launch<EPI_F16>(p, stream);
+}
+
+// tise_layernorm_f16 and both outputs of tise_layernorm_f32: x, gamma, beta and out move as 16-byte pieces of eight halves
+// or four floats
+template <typename InT, typename OutT>
+int layernorm_launch(const void* x_dev, int64_t ldx, const void* gamma_dev, const void* beta_dev, void* out_dev, int64_t ldo,
+                     int64_t rows, int C, float eps, void* stream) {
+    constexpr int64_t xmul = 16 / sizeof(InT), omul = 16 / sizeof(OutT);
+    if (!x_dev || !gamma_dev || !beta_dev || !out_dev || rows < 0 || C <= 0 || C > 1024 || C % 8 != 0 || ldx % xmul != 0 ||
+        ldo % omul != 0 || ldx < C || ldo < C ||
+        ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(gamma_dev) |
+          reinterpret_cast<uintptr_t>(beta_dev)) & 15) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (rows == 0) return TISE_OK;
+    if ((rows + 3) / 4 > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((layernorm_kernel<InT, OutT>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const InT*>(x_dev), ldx, reinterpret_cast<const InT*>(gamma_dev),
+                       reinterpret_cast<const InT*>(beta_dev), reinterpret_cast<OutT*>(out_dev), ldo, (int)rows, C, eps);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+template <typename T>
+int vit_tokens_launch(const void* patch_out_dev, const void* class_dev, const void* pos_emb_dev, int batch, int n_patches, int width,
+                      void* x_dev, void* stream) {
+    if (!patch_out_dev || !class_dev || !pos_emb_dev || !x_dev || batch < 0 || n_patches <= 0 || width <= 0) return TISE_ERR_INVALID_ARG;
+    if (batch == 0) return TISE_OK;
+    hipLaunchKernelGGL(vit_tokens_kernel<T>, dim3(grid1d((long long)batch * (n_patches + 1) * width)), dim3(256), 0,
+                       (hipStream_t)stream, reinterpret_cast<const _Float16*>(patch_out_dev), reinterpret_cast<const T*>(class_dev),
+                       reinterpret_cast<const T*>(pos_emb_dev), batch, n_patches, width, reinterpret_cast<T*>(x_dev));
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+template <typename T>
+int gather_rows_launch(const void* x_dev, const int64_t* index_dev, int64_t n, int width, void* out_dev, void* stream) {
+    if (!x_dev || !index_dev || !out_dev || n < 0 || width <= 0) return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(grid1d(n * width)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const T*>(x_dev), reinterpret_cast<const long long*>(index_dev), (long long)n, width,
+                       reinterpret_cast<T*>(out_dev));
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
 }
 
 }  // namespace
@@ -1205,90 +1083,45 @@ int tise_gemm_f16_act(const void* a_dev, int64_t lda, const void* w_dev, int64_t
 
 int tise_gemm_f16_res32(const void* a_dev, int64_t lda, const void* w_dev, int64_t ldw, const void* bias_dev, const void* scale_dev,
                         const void* res32_dev, int64_t ldr, void* out32_dev, int64_t ldo, int m, int n, int k, void* stream) {
-    // a / w / bias as tise_gemm_f16; res32 / out32 move in 16-byte pieces of four floats (rows 16-byte aligned: strides % 4),
-    // scale in 16-byte pieces.  out32 == res32 (same stride) is the tower's in-place update; any other overlap is the caller's.
-    if (!a_dev || !w_dev || !res32_dev || !out32_dev || m < 0 || n <= 0 || k <= 0 || k % GM_BK != 0 || n % 8 != 0 || lda % 8 != 0 ||
-        ldw % 8 != 0 || ldr % 4 != 0 || ldo % 4 != 0 || lda < k || ldw < k || ldr < n || ldo < n ||
-        ((reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(w_dev) | reinterpret_cast<uintptr_t>(res32_dev) |
-          reinterpret_cast<uintptr_t>(out32_dev) | reinterpret_cast<uintptr_t>(scale_dev)) & 15) != 0 ||
-        (reinterpret_cast<uintptr_t>(bias_dev) & 7) != 0)
+    // res32 / out32 move in 16-byte pieces of four floats (rows 16-byte aligned: strides % 4), scale in 16-byte pieces.
+    // out32 == res32 (same stride) is the tower's in-place update; any other overlap is the caller's.
+    GemmArgs p = {};
+    if (!gemm_operands(p, a_dev, lda, w_dev, ldw, bias_dev, m, n, k) || !res32_dev || !out32_dev || ldr % 4 != 0 || ldo % 4 != 0 ||
+        ldr < n || ldo < n ||
+        ((reinterpret_cast<uintptr_t>(res32_dev) | reinterpret_cast<uintptr_t>(out32_dev) | reinterpret_cast<uintptr_t>(scale_dev)) & 15) != 0)
         return TISE_ERR_INVALID_ARG;
     if (m == 0) return TISE_OK;
-    GemmArgs p = {};
-    p.a = reinterpret_cast<const _Float16*>(a_dev); p.lda = lda;
-    p.w = reinterpret_cast<const _Float16*>(w_dev); p.ldw = ldw;
-    p.bias = reinterpret_cast<const _Float16*>(bias_dev);
     p.scale = reinterpret_cast<const float*>(scale_dev);
     p.res32 = reinterpret_cast<const float*>(res32_dev); p.ldr32 = ldr;
     p.out32 = reinterpret_cast<float*>(out32_dev); p.ldo32 = ldo;
-    p.M = m; p.N = n; p.K = k; p.act = 0;
     return gemm_launch<EPI_RES32>(p, stream);
 }
 
 int tise_layernorm_f32(const void* x_dev, int64_t ldx, const void* gamma_dev, const void* beta_dev, void* out_dev, int64_t ldo,
                        int64_t rows, int C, float eps, int out_f32, void* stream) {
-    // x, gamma, beta (and an fp32 out) move as 16-byte pieces of four floats, an fp16 out as 16-byte pieces of eight halves
-    const int64_t omul = out_f32 ? 4 : 8;
-    if (!x_dev || !gamma_dev || !beta_dev || !out_dev || rows < 0 || C <= 0 || C > 1024 || C % 8 != 0 || ldx % 4 != 0 || ldo % omul != 0 ||
-        ldx < C || ldo < C || (out_f32 != 0 && out_f32 != 1) ||
-        ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(gamma_dev) |
-          reinterpret_cast<uintptr_t>(beta_dev)) & 15) != 0)
-        return TISE_ERR_INVALID_ARG;
-    if (rows == 0) return TISE_OK;
-    if ((rows + 3) / 4 > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    const float* x = reinterpret_cast<const float*>(x_dev);
-    const float* g = reinterpret_cast<const float*>(gamma_dev);
-    const float* b = reinterpret_cast<const float*>(beta_dev);
-    if (out_f32) hipLaunchKernelGGL(layernorm_f32_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, g, b,
-                                    reinterpret_cast<float*>(out_dev), ldo, (int)rows, C, eps);
-    else hipLaunchKernelGGL(layernorm_f32_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, g, b,
-                            reinterpret_cast<_Float16*>(out_dev), ldo, (int)rows, C, eps);
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    if (out_f32 != 0 && out_f32 != 1) return TISE_ERR_INVALID_ARG;
+    return out_f32 ? layernorm_launch<float, float>(x_dev, ldx, gamma_dev, beta_dev, out_dev, ldo, rows, C, eps, stream)
+                   : layernorm_launch<float, _Float16>(x_dev, ldx, gamma_dev, beta_dev, out_dev, ldo, rows, C, eps, stream);
 }
 
 int tise_vit_tokens_f32(const void* patch_out_dev, const void* class_tok_dev, const void* pos_emb_dev, int batch, int n_patches,
                         int width, void* x_dev, void* stream) {
-    if (!patch_out_dev || !class_tok_dev || !pos_emb_dev || !x_dev || batch < 0 || n_patches <= 0 || width <= 0 ||
-        (reinterpret_cast<uintptr_t>(patch_out_dev) & 1) != 0 ||
+    if ((reinterpret_cast<uintptr_t>(patch_out_dev) & 1) != 0 ||
         ((reinterpret_cast<uintptr_t>(class_tok_dev) | reinterpret_cast<uintptr_t>(pos_emb_dev) | reinterpret_cast<uintptr_t>(x_dev)) & 3) != 0)
         return TISE_ERR_INVALID_ARG;
-    if (batch == 0) return TISE_OK;
-    hipLaunchKernelGGL(vit_tokens_f32_kernel, dim3(grid1d((long long)batch * (n_patches + 1) * width)), dim3(256), 0,
-                       (hipStream_t)stream, reinterpret_cast<const _Float16*>(patch_out_dev), reinterpret_cast<const float*>(class_tok_dev),
-                       reinterpret_cast<const float*>(pos_emb_dev), batch, n_patches, width, reinterpret_cast<float*>(x_dev));
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    return vit_tokens_launch<float>(patch_out_dev, class_tok_dev, pos_emb_dev, batch, n_patches, width, x_dev, stream);
 }
 
 int tise_gather_rows_f32(const void* x_dev, const int64_t* index_dev, int64_t n, int width, void* out_dev, void* stream) {
-    if (!x_dev || !index_dev || !out_dev || n < 0 || width <= 0 ||
-        ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 3) != 0 ||
+    if (((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 3) != 0 ||
         (reinterpret_cast<uintptr_t>(index_dev) & 7) != 0)
         return TISE_ERR_INVALID_ARG;
-    if (n == 0) return TISE_OK;
-    hipLaunchKernelGGL(gather_rows_f32_kernel, dim3(grid1d(n * width)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float*>(x_dev), reinterpret_cast<const long long*>(index_dev), (long long)n, width,
-                       reinterpret_cast<float*>(out_dev));
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    return gather_rows_launch<float>(x_dev, index_dev, n, width, out_dev, stream);
 }
 
 int tise_layernorm_f16(const void* x_dev, int64_t ldx, const void* gamma_dev, const void* beta_dev, void* out_dev, int64_t ldo,
                        int64_t rows, int C, float eps, void* stream) {
-    if (!x_dev || !gamma_dev || !beta_dev || !out_dev || rows < 0 || C <= 0 || C > 1024 || C % 8 != 0 || ldx % 8 != 0 || ldo % 8 != 0 ||
-        ldx < C || ldo < C ||
-        ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(gamma_dev) |
-          reinterpret_cast<uintptr_t>(beta_dev)) & 15) != 0)
-        return TISE_ERR_INVALID_ARG;
-    if (rows == 0) return TISE_OK;
-    if ((rows + 3) / 4 > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(layernorm_f16_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const _Float16*>(x_dev), ldx, reinterpret_cast<const _Float16*>(gamma_dev),
-                       reinterpret_cast<const _Float16*>(beta_dev), reinterpret_cast<_Float16*>(out_dev), ldo, (int)rows, C, eps);
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    return layernorm_launch<_Float16, _Float16>(x_dev, ldx, gamma_dev, beta_dev, out_dev, ldo, rows, C, eps, stream);
 }
 
 int tise_attention_f16(const void* qkv_dev, int batch, int seq, int heads, int head_dim, int causal, void* out_dev, void* stream) {
@@ -1350,13 +1183,7 @@ int tise_patchify_pad_f16(const void* img_dev, int batch, int res, int patch, in
 
 int tise_vit_tokens_f16(const void* patch_out_dev, const void* class_emb_dev, const void* pos_emb_dev, int batch, int n_patches,
                         int width, void* x_dev, void* stream) {
-    if (!patch_out_dev || !class_emb_dev || !pos_emb_dev || !x_dev || batch < 0 || n_patches <= 0 || width <= 0) return TISE_ERR_INVALID_ARG;
-    if (batch == 0) return TISE_OK;
-    hipLaunchKernelGGL(vit_tokens_f16_kernel, dim3(grid1d((long long)batch * (n_patches + 1) * width)), dim3(256), 0,
-                       (hipStream_t)stream, reinterpret_cast<const _Float16*>(patch_out_dev), reinterpret_cast<const _Float16*>(class_emb_dev),
-                       reinterpret_cast<const _Float16*>(pos_emb_dev), batch, n_patches, width, reinterpret_cast<_Float16*>(x_dev));
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    return vit_tokens_launch<_Float16>(patch_out_dev, class_emb_dev, pos_emb_dev, batch, n_patches, width, x_dev, stream);
 }
 
 int tise_text_tokens_f16(const int32_t* tokens_dev, const void* table_dev, const void* pos_emb_dev, int64_t rows, int seq, int width,
@@ -1371,13 +1198,7 @@ int tise_text_tokens_f16(const int32_t* tokens_dev, const void* table_dev, const
 }
 
 int tise_gather_rows_f16(const void* x_dev, const int64_t* index_dev, int64_t n, int width, void* out_dev, void* stream) {
-    if (!x_dev || !index_dev || !out_dev || n < 0 || width <= 0) return TISE_ERR_INVALID_ARG;
-    if (n == 0) return TISE_OK;
-    hipLaunchKernelGGL(gather_rows_f16_kernel, dim3(grid1d(n * width)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const _Float16*>(x_dev), reinterpret_cast<const long long*>(index_dev), (long long)n, width,
-                       reinterpret_cast<_Float16*>(out_dev));
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    return gather_rows_launch<_Float16>(x_dev, index_dev, n, width, out_dev, stream);
 }
 
 }  // extern "C"
