@@ -542,7 +542,9 @@ int tise_cosine_top1(const void* img_emb_dev, const void* txt_emb_dev, const int
  *   tise_attention_long_f16  the same layout and result for ANY seq >= 1, non-causal: keys stream in tiles of
  *                        tise_attention_long_key_tile() under an online softmax with the exact running maximum; a workgroup
  *                        of 4 waves serves 128 consecutive queries of one (sequence, head) and stages each K / V tile once
- *                        in LDS (the image tower of ViT-L/14@336: 577 tokens); head_dim == 64, qkv / out 16-byte aligned
+ *                        in LDS (the image tower of ViT-L/14@336: 577 tokens); head_dim == 64, or 80 (open_clip ViT-H/14: five
+ *                        K-steps of 16, the fp32 scale nearest 1 / sqrt(80), a third output tile whose columns >= 80 are never
+ *                        stored), any other head_dim is refused; qkv / out 16-byte aligned (then so is every head's q, k and v)
  *   tise_patchify_pad_f16  tise_patchify_f16's matrix for any patch >= 1 with res % patch == 0, rows padded to kpad columns
  *                        (kpad >= 3*patch*patch, kpad % 64 == 0: tise_gemm_f16's K-step), the padding written as +0;
  *                        image 2-byte, out 16-byte aligned
@@ -598,6 +600,21 @@ int tise_layernorm_f32(const void* x_dev, int64_t ldx, const void* gamma_dev, co
 int tise_vit_tokens_f32(const void* patch_out_dev, const void* class_tok_dev, const void* pos_emb_dev, int batch, int n_patches,
                         int width, void* x_dev, void* stream);
 int tise_gather_rows_f32(const void* x_dev, const int64_t* index_dev, int64_t n, int width, void* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * CLIPScore on an open_clip ViT-H/14 tower (tise_toolbox_amd/clip_score.py, openclip_model.py): head width 80 is
+ * tise_attention_long_f16 above, exact GELU is tise_gemm_f16_act; the two entries the tower and the score add:
+ *   tise_layernorm_wide_f16  tise_layernorm_f16 -- the same parameters, two-pass fp32 statistics and rsqrtf -- for rows of up to
+ *                        2048 columns (C % 8 == 0; ViT-H/14: 1280): four 16-byte groups per lane instead of two.
+ *                        tise_layernorm_f16 / _f32 keep refusing C > 1024.
+ *   tise_paired_cosine   out_cos[i] = (a_i . b_i) / sqrt((a_i . a_i)(b_i . b_i)) of row i of two contiguous (n, d) tables, fp16
+ *                        (is_f16 1) or fp32 (0): fp64 products and sums in a fixed order (lane-strided partial sums, then a
+ *                        butterfly), one wave per row, no atomics -- two launches give the same bits.  A zero row gives NaN.
+ *                        n >= 0, d >= 1; tables aligned to their element, out_cos (n doubles) to 8 bytes.
+ * ------------------------------------------------------------------------------------------ */
+int tise_layernorm_wide_f16(const void* x_dev, int64_t ldx, const void* gamma_dev, const void* beta_dev, void* out_dev, int64_t ldo,
+                            int64_t rows, int C, float eps, void* stream);
+int tise_paired_cosine(const void* img_dev, const void* txt_dev, int64_t n, int d, int is_f16, double* out_cos_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a5, convolution) Implicit-GEMM convolution on fp16 MFMA with 3-term split-precision operands.

@@ -51,12 +51,21 @@ def build_towers(weights_path, dev, arch=None, seed=0):
     Default: the hand-written kernels of csrc/clip_ops.hip (clip_hip.HipTowers: 1.4x / 2.4x the library-kernel module
     on the image / text tower, profiles/r02x_clip_towers.txt); TISE_CLIP=torch runs the module itself on PyTorch-ROCm
     library kernels (what north_star prescribes for the forward passes; same parameters, same results to fp16 rounding).
-    ``arch``: a tower of clip_model.CONFIGS (None: ViT-B/32, what RP-COCO and PA use); ``seed``: of the stand-in parameters."""
-    model = clip_model.build_clip(weights_path, seed, arch)
+    ``arch``: a tower of clip_model.CONFIGS (None: ViT-B/32, what RP-COCO and PA use) or of openclip_model.CONFIGS (ViT-H-14: the
+    same two routes -- HipTowers at head width 80 with the exact GELU, or the module in fp16 -- except that a tower wider than
+    HipTowers' 1024 columns, ViT-H-14 itself, takes the MODULE by default: openclip_model.default_route); ``seed``: of the stand-in
+    parameters."""
+    from . import openclip_model
+    route = "hip"
+    if openclip_model.is_config(arch):
+        model = openclip_model.build_openclip(weights_path, seed, arch)
+        route = openclip_model.default_route(openclip_model.get_config(arch))
+    else:
+        model = clip_model.build_clip(weights_path, seed, arch)
     scale = float(model.logit_scale.detach().exp())            # clip's convert_weights leaves logit_scale in fp32
     model = model.to(dev).half()
     tdist.broadcast_module_(model)
-    if os.environ.get("TISE_CLIP", "hip") == "torch":
+    if os.environ.get("TISE_CLIP", route) == "torch":
         return model, scale
     from . import clip_hip
     return clip_hip.HipTowers(model, dev), scale

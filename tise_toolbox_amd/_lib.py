@@ -79,6 +79,8 @@ SIGNATURES = {
     "tise_layernorm_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_int, c_void_p]),
     "tise_vit_tokens_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tise_gather_rows_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "tise_layernorm_wide_f16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p]),
+    "tise_paired_cosine": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "tise_stats_create": (c_int, [c_int, POINTER(c_void_p)]),
     "tise_stats_destroy": (c_int, [c_void_p]),
     "tise_stats_reset": (c_int, [c_void_p, c_void_p]),

@@ -1,4 +1,7 @@
-"""The CLIP towers (ViT-B/32; ViT-L/14@336 for CMMD) on the hand-written kernels of csrc/clip_ops.hip.
+"""The CLIP towers (ViT-B/32; ViT-L/14@336 for CMMD) on the hand-written kernels of csrc/clip_ops.hip;
+also towers of openclip_model.py's kind: head width 80 on the long-sequence attention and the exact GELU are read off the module.
+A tower wider than 1024 columns (open_clip's ViT-H/14 itself: 1280) is refused when HipTowers is built -- the LayerNorm entry point
+the towers launch holds 1024 -- and runs on the library route (RP_coco.build_towers).
 
 ``HipTowers(model)`` takes a ``clip_model.CLIP`` (real OpenAI parameters or the seeded stand-ins), keeps fp16 copies
 of its parameters in the layouts the kernels read, and offers ``encode_image`` / ``encode_text`` with the signatures
@@ -44,55 +47,98 @@ def layernorm(x, gamma, beta, eps=1e-5, out=None):
     assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
     if out is None:
         out = torch.empty_like(x)
+    if x.shape[1] > LAYERNORM_MAX_C:
+        raise ValueError(f"the towers' LayerNorm kernel holds rows of up to {LAYERNORM_MAX_C} columns (got {x.shape[1]})")
     _lib.call("tise_layernorm_f16", _p(x), x.stride(0), _p(gamma), _p(beta), _p(out), out.stride(0), x.shape[0], x.shape[1],
               ctypes.c_float(eps), _stream())
     return out
 
 
+LAYERNORM_MAX_C = 1024           # tise_layernorm_f16 holds a row as 2 x 8 values per lane
+ATTN_LONG_HEAD_DIMS = (64, 80)   # tise_attention_long_f16's instances; tise_attention_f16 (short / causal) is 64 only
+GEMM_K_STEP = 64                 # tise_gemm_f16 steps K by 64 columns
 ATTN_LONG_KEY_TILE = 64          # keys per LDS tile of tise_attention_long_f16 (= tise_attention_long_key_tile(), csrc/clip_ops.hip)
 ATTN_SHORT_MAX_SEQ = 96          # tise_attention_f16 keeps a (sequence, head)'s scores in registers up to here
 
 
-def attention(qkv, batch, seq, heads, causal):
-    """qkv (batch*seq, 3*heads*64) fp16 contiguous -> (batch*seq, heads*64).  seq <= 96: tise_attention_f16 (one wave per
-    (sequence, head)); longer sequences: tise_attention_long_f16 (streamed keys, online softmax), non-causal only."""
+def attention(qkv, batch, seq, heads, causal, head_dim=64):
+    """qkv (batch*seq, 3*heads*head_dim) fp16 contiguous -> (batch*seq, heads*head_dim).  seq <= 96: tise_attention_f16 (one wave
+    per (sequence, head); head_dim 64 only); longer sequences: tise_attention_long_f16 (streamed keys, online softmax),
+    non-causal only, head_dim 64 or 80."""
     if seq > ATTN_SHORT_MAX_SEQ:
         if causal:
             raise ValueError(f"causal attention runs up to {ATTN_SHORT_MAX_SEQ} tokens (got {seq}): the long-sequence kernel has no mask")
-        return attention_long(qkv, batch, seq, heads)
-    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.shape == (batch * seq, 3 * heads * 64)
-    out = torch.empty((batch * seq, heads * 64), dtype=torch.float16, device=qkv.device)
-    _lib.call("tise_attention_f16", _p(qkv), batch, seq, heads, 64, 1 if causal else 0, _p(out), _stream())
+        return attention_long(qkv, batch, seq, heads, head_dim)
+    if head_dim != 64:
+        raise ValueError(f"the short / causal attention kernel runs at head width 64 only (got {head_dim}, {seq} tokens"
+                         f"{', causal' if causal else ''})")
+    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.shape == (batch * seq, 3 * heads * head_dim)
+    out = torch.empty((batch * seq, heads * head_dim), dtype=torch.float16, device=qkv.device)
+    _lib.call("tise_attention_f16", _p(qkv), batch, seq, heads, head_dim, 1 if causal else 0, _p(out), _stream())
     return out
 
 
-def attention_long(qkv, batch, seq, heads):
-    """attention(..., causal=False) on tise_attention_long_f16 whatever the length (any seq >= 1)."""
-    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.shape == (batch * seq, 3 * heads * 64)
-    out = torch.empty((batch * seq, heads * 64), dtype=torch.float16, device=qkv.device)
-    _lib.call("tise_attention_long_f16", _p(qkv), batch, seq, heads, 64, _p(out), _stream())
+def attention_long(qkv, batch, seq, heads, head_dim=64):
+    """attention(..., causal=False) on tise_attention_long_f16 whatever the length (any seq >= 1), at head width 64 or 80."""
+    if head_dim not in ATTN_LONG_HEAD_DIMS:
+        raise ValueError(f"the long-sequence attention kernel runs at head widths {ATTN_LONG_HEAD_DIMS} (got {head_dim})")
+    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.shape == (batch * seq, 3 * heads * head_dim)
+    out = torch.empty((batch * seq, heads * head_dim), dtype=torch.float16, device=qkv.device)
+    _lib.call("tise_attention_long_f16", _p(qkv), batch, seq, heads, head_dim, _p(out), _stream())
     return out
+
+
+def mlp_act(module):
+    """The GEMM epilogue's activation code of a block's MLP activation module: 1 QuickGELU, 2 exact (erf) GELU."""
+    from . import clip_model
+    if isinstance(module, clip_model.QuickGELU):
+        return 1
+    if isinstance(module, torch.nn.GELU) and getattr(module, "approximate", "none") == "none":
+        return 2
+    raise ValueError(f"no GEMM epilogue for the MLP activation {module!r}: QuickGELU or the exact nn.GELU")
+
+
+def _k_padded(cols):
+    return (cols + GEMM_K_STEP - 1) // GEMM_K_STEP * GEMM_K_STEP
+
+
+def _pad_cols(t, kp):
+    """A GEMM operand (rows, K) with zero columns up to kp = _k_padded(K), as the patch matrix of patch 14 has them: a width that
+    is no multiple of the K-step (a tower of 2 heads of 80: 160) still runs, on exact zeros.  kp == K: the tensor itself."""
+    return t if t.shape[1] == kp else torch.nn.functional.pad(t, (0, kp - t.shape[1])).contiguous()
+
+
+def _layernorm_k(x, ln, kp):
+    """layernorm(x, *ln) as the next GEMM's operand: (rows, kp) with zeros behind the C columns (kp == C: layernorm's own output)."""
+    if x.shape[1] == kp:
+        return layernorm(x, *ln)
+    buf = torch.zeros((x.shape[0], kp), dtype=torch.float16, device=x.device)
+    layernorm(x, *ln, out=buf[:, :x.shape[1]])
+    return buf
 
 
 class _Block:
     def __init__(self, blk, dev):
         h = lambda t: t.detach().to(dev, torch.float16).contiguous()
+        self.kp = kp = _k_padded(blk.attn.in_proj_weight.shape[1])
         self.ln1 = (h(blk.ln_1.weight), h(blk.ln_1.bias), blk.ln_1.eps)
         self.ln2 = (h(blk.ln_2.weight), h(blk.ln_2.bias), blk.ln_2.eps)
-        self.w_in, self.b_in = h(blk.attn.in_proj_weight), h(blk.attn.in_proj_bias)
-        self.w_out, self.b_out = h(blk.attn.out_proj.weight), h(blk.attn.out_proj.bias)
-        self.w_fc, self.b_fc = h(blk.mlp.c_fc.weight), h(blk.mlp.c_fc.bias)
+        self.w_in, self.b_in = _pad_cols(h(blk.attn.in_proj_weight), kp), h(blk.attn.in_proj_bias)
+        self.w_out, self.b_out = _pad_cols(h(blk.attn.out_proj.weight), kp), h(blk.attn.out_proj.bias)
+        self.w_fc, self.b_fc = _pad_cols(h(blk.mlp.c_fc.weight), kp), h(blk.mlp.c_fc.bias)
         self.w_pr, self.b_pr = h(blk.mlp.c_proj.weight), h(blk.mlp.c_proj.bias)
         self.heads = blk.attn.heads
+        self.head_dim = blk.attn.in_proj_weight.shape[1] // self.heads
+        self.act = mlp_act(blk.mlp.gelu)
 
     def __call__(self, x, batch, seq, causal):
         """x (batch*seq, width) -> x + attn(ln_1(x)); then + mlp(ln_2(.))   (clip model.py ResidualAttentionBlock)."""
-        y = layernorm(x, *self.ln1)
+        y = _layernorm_k(x, self.ln1, self.kp)
         qkv = gemm(y, self.w_in, self.b_in)
-        o = attention(qkv, batch, seq, self.heads, causal)
-        x = gemm(o, self.w_out, self.b_out, residual=x)
-        y = layernorm(x, *self.ln2)
-        f = gemm(y, self.w_fc, self.b_fc, act=1)                    # QuickGELU in the epilogue
+        o = attention(qkv, batch, seq, self.heads, causal, self.head_dim)
+        x = gemm(_pad_cols(o, self.kp), self.w_out, self.b_out, residual=x)
+        y = _layernorm_k(x, self.ln2, self.kp)
+        f = gemm(y, self.w_fc, self.b_fc, act=self.act)             # QuickGELU (1) or exact GELU (2) in the epilogue
         return gemm(f, self.w_pr, self.b_pr, residual=x)
 
 
@@ -120,15 +166,27 @@ class HipTowers:
         self.cls, self.pos_v = h(v.class_embedding), h(v.positional_embedding)
         self.ln_pre = (h(v.ln_pre.weight), h(v.ln_pre.bias), v.ln_pre.eps)
         self.ln_post = (h(v.ln_post.weight), h(v.ln_post.bias), v.ln_post.eps)
-        self.proj_v = h(v.proj.t())                                  # (out_dim, width): features @ proj
+        self.proj_v = _pad_cols(h(v.proj.t()), _k_padded(self.width_v))      # (out_dim, width): features @ proj
         self.blocks_v = [_Block(b, dev) for b in v.transformer.resblocks]
         self.table = h(model.token_embedding.weight)
         self.pos_t = h(model.positional_embedding)
         self.ln_final = (h(model.ln_final.weight), h(model.ln_final.bias), model.ln_final.eps)
-        self.proj_t = h(model.text_projection.t())
+        self.proj_t = _pad_cols(h(model.text_projection.t()), _k_padded(self.table.shape[1]))
         self.blocks_t = [_Block(b, dev) for b in model.transformer.resblocks]
         self.width_t = self.table.shape[1]
         self.logit_scale = model.logit_scale
+        # a head width the kernels of a tower's sequences do not have is an error here, before anything is launched: the text
+        # tower (causal) and an image tower of up to 96 tokens run on the short kernel, head width 64 only
+        for name, width in (("image", self.width_v), ("text", self.width_t)):
+            if width > LAYERNORM_MAX_C:
+                raise ValueError(f"the {name} tower is {width} columns wide: HipTowers' LayerNorm kernel holds rows of up to "
+                                 f"{LAYERNORM_MAX_C}; this tower runs on the library route (TISE_CLIP=torch)")
+        seq_v = self.pos_v.shape[0]
+        for name, blocks, long_seq in (("image", self.blocks_v, seq_v > ATTN_SHORT_MAX_SEQ), ("text", self.blocks_t, False)):
+            for blk in blocks:
+                if blk.head_dim != 64 and not (long_seq and blk.head_dim in ATTN_LONG_HEAD_DIMS):
+                    raise ValueError(f"the {name} tower has head width {blk.head_dim}: the "
+                                     f"{'long-sequence' if long_seq else 'short / causal'} attention kernel does not run it")
 
     @torch.no_grad()
     def encode_image(self, image):
@@ -153,7 +211,7 @@ class HipTowers:
         idx = torch.arange(b, device=self.device, dtype=torch.int64) * seq          # the class token of every image
         c = torch.empty((b, self.width_v), dtype=torch.float16, device=self.device)
         _lib.call("tise_gather_rows_f16", _p(xs), _p(idx), b, self.width_v, _p(c), _stream())
-        return gemm(layernorm(c, *self.ln_post), self.proj_v)
+        return gemm(_layernorm_k(c, self.ln_post, self.proj_v.shape[1]), self.proj_v)
 
     @torch.no_grad()
     def encode_text(self, text):
@@ -169,7 +227,7 @@ class HipTowers:
         idx = (torch.arange(b, device=self.device, dtype=torch.int64) * seq + text.argmax(-1).to(torch.int64)).contiguous()
         e = torch.empty((b, self.width_t), dtype=torch.float16, device=self.device)
         _lib.call("tise_gather_rows_f16", _p(x), _p(idx), b, self.width_t, _p(e), _stream())
-        return gemm(layernorm(e, *self.ln_final), self.proj_t)
+        return gemm(_layernorm_k(e, self.ln_final, self.proj_t.shape[1]), self.proj_t)
 
     def parameters(self):                                            # so that callers can ask for the dtype
         yield self.table

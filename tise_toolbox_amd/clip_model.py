@@ -82,12 +82,21 @@ class Attention(nn.Module):
         return self.out_proj(o.transpose(1, 2).reshape(b, s, w))
 
 
+def make_act(act):
+    """The MLP activation of a tower: "quick_gelu" (every OpenAI tower) or "gelu" (exact erf GELU: openclip_model's towers)."""
+    if act == "quick_gelu":
+        return QuickGELU()
+    if act == "gelu":
+        return nn.GELU()
+    raise ValueError(f"unknown MLP activation {act!r}: 'quick_gelu' or 'gelu'")
+
+
 class Block(nn.Module):
-    def __init__(self, width, heads):
+    def __init__(self, width, heads, act="quick_gelu"):
         super().__init__()
         self.attn = Attention(width, heads)
         self.ln_1 = nn.LayerNorm(width)
-        self.mlp = nn.Sequential(OrderedDict([("c_fc", nn.Linear(width, 4 * width)), ("gelu", QuickGELU()),
+        self.mlp = nn.Sequential(OrderedDict([("c_fc", nn.Linear(width, 4 * width)), ("gelu", make_act(act)),
                                               ("c_proj", nn.Linear(4 * width, width))]))
         self.ln_2 = nn.LayerNorm(width)
 
@@ -97,9 +106,9 @@ class Block(nn.Module):
 
 
 class Transformer(nn.Module):
-    def __init__(self, width, layers, heads):
+    def __init__(self, width, layers, heads, act="quick_gelu"):
         super().__init__()
-        self.resblocks = nn.ModuleList([Block(width, heads) for _ in range(layers)])
+        self.resblocks = nn.ModuleList([Block(width, heads, act) for _ in range(layers)])
 
     def forward(self, x, causal=False):
         for blk in self.resblocks:
@@ -108,14 +117,14 @@ class Transformer(nn.Module):
 
 
 class VisionTransformer(nn.Module):
-    def __init__(self, resolution=224, patch=32, width=768, layers=12, heads=12, out_dim=512):
+    def __init__(self, resolution=224, patch=32, width=768, layers=12, heads=12, out_dim=512, act="quick_gelu"):
         super().__init__()
         self.conv1 = nn.Conv2d(3, width, patch, patch, bias=False)
         scale = width ** -0.5
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
         self.positional_embedding = nn.Parameter(scale * torch.randn((resolution // patch) ** 2 + 1, width))
         self.ln_pre = nn.LayerNorm(width)
-        self.transformer = Transformer(width, layers, heads)
+        self.transformer = Transformer(width, layers, heads, act)
         self.ln_post = nn.LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, out_dim))
 
@@ -132,16 +141,18 @@ class CLIP(nn.Module):
         """``config``: a name of ``CONFIGS`` or a configuration dict (then the other arguments are not read); None: ViT-B/32
         with the text tower of the arguments, as before the configurations existed."""
         super().__init__()
+        act = "quick_gelu"
         if config is not None:
             cfg = get_config(config)
+            act = cfg.get("act", act)                          # only openclip_model's configurations carry one
             embed_dim, text_width, text_layers, text_heads = cfg["embed_dim"], cfg["text_width"], cfg["text_layers"], cfg["text_heads"]
-            self.visual = VisionTransformer(cfg["resolution"], cfg["patch"], cfg["width"], cfg["layers"], cfg["heads"], embed_dim)
+            self.visual = VisionTransformer(cfg["resolution"], cfg["patch"], cfg["width"], cfg["layers"], cfg["heads"], embed_dim, act)
         else:
             self.visual = VisionTransformer(out_dim=embed_dim)
         # what callers preprocess to and allocate for (clip_hip.HipTowers and RP_coco.encode_paths read both)
         self.resolution = self.visual.conv1.kernel_size[0] * int(round((self.visual.positional_embedding.shape[0] - 1) ** 0.5))
         self.out_dim = embed_dim
-        self.transformer = Transformer(text_width, text_layers, text_heads)
+        self.transformer = Transformer(text_width, text_layers, text_heads, act)
         self.token_embedding = nn.Embedding(VOCAB_SIZE, text_width)
         self.positional_embedding = nn.Parameter(torch.empty(CONTEXT_LENGTH, text_width))
         self.ln_final = nn.LayerNorm(text_width)

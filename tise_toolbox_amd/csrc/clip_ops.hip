@@ -16,7 +16,8 @@
 //                        cores with operands loaded straight into the MFMA layout, fp32 softmax in registers.
 //   attention_long_f16_kernel  any S (ViT-L/14@336: 577 tokens), non-causal: 4 waves x 32 queries of one (sequence, head)
 //                        share each 64-key K / V tile in LDS; the same two products, online softmax with the exact running
-//                        maximum.
+//                        maximum.  A template over the head width: 64, or the 80 of open_clip ViT-H/14.
+//   paired_cosine_kernel one wave per row pair, fp64 in a fixed order: CLIPScore's cosine (clip_score.py).
 //   vit_tokens_kernel / text_tokens_f16_kernel / patchify_f16_kernel / patchify_pad_f16_kernel (any patch size, rows
 //   padded with zeros to the GEMM's K-step) / gather_rows_kernel: token assembly.
 // The DINOv2 tower of FD-DINOv2 (dinov2_hip.HipDino) keeps its residual stream in fp32 -- what torch.autocast(fp16) computes:
@@ -527,7 +528,9 @@ template <> struct Row8<float> {
 // version moved 2 bytes per lane and instruction and ran at 2 TB/s.
 // InT = _Float16 (x, gamma, beta and out in fp16): the CLIP towers, rsqrtf.  InT = float: the fp32 residual stream of the
 // DINOv2 tower (dinov2_hip.HipDino), 1 / sqrtf; OutT = _Float16 feeds the next GEMM, float is the tower's feature row.
-template <typename InT, typename OutT>
+// NG = 16-byte groups per lane: 2 (C <= 1024) everywhere but tise_layernorm_wide_f16, whose NG = 4 holds a row of up to 2048
+// columns (open_clip ViT-H/14: 1280) -- the same loops, 32 sequential adds per lane instead of 16; groups beyond C add +0.
+template <typename InT, typename OutT, int NG>
 __global__ __launch_bounds__(256) void layernorm_kernel(const InT* __restrict__ x, long long ldx, const InT* __restrict__ gamma,
                                                         const InT* __restrict__ beta, OutT* __restrict__ out, long long ldo,
                                                         int rows, int C, float eps) {
@@ -535,10 +538,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const InT* __restrict__ 
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const InT* xr = x + (long long)row * ldx;
-    float v[2][8];
+    float v[NG][8];
     float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < NG; ++k) {
         const int c = 512 * k + 8 * lane;
         Row8<InT> r;
         if (c < C) r.load(xr + c);
@@ -550,7 +553,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const InT* __restrict__ 
     const float mean = s / (float)C;
     float q = 0.f;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < NG; ++k) {
         if (512 * k + 8 * lane < C) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) { const float d = v[k][e] - mean; q += d * d; }
@@ -561,7 +564,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const InT* __restrict__ 
     const float rstd = sizeof(InT) == 2 ? rsqrtf(q / (float)C + eps) : 1.0f / sqrtf(q / (float)C + eps);
     OutT* o = out + (long long)row * ldo;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < NG; ++k) {
         const int c = 512 * k + 8 * lane;
         if (c < C) {
             Row8<InT> g, bb;
@@ -722,60 +725,104 @@ __global__ __launch_bounds__(256) void attention_f16_kernel(const _Float16* __re
 //   read as NaN would be NaN).  Padding queries i >= S compute on q = 0 and store nothing.  EVERY wave -- also one whose 32
 //   queries all lie beyond S -- runs every staging step and every barrier: there is no early return and no break.
 #define ATTN_LONG_KT 64
+// D = head width: 64 (every OpenAI tower) or 80 (open_clip ViT-H/14: width 1280, 16 heads).  The D = 64 instance is the kernel
+// as it was -- the same MFMA order, `* 0.125f`, the same online-softmax steps, the same LDS image.  What D = 80 changes:
+//   K Q^T      five K-steps of 16 (80 = 5 x 16: no padding on that side); the scores are multiplied in fp32 by the float nearest
+//              1 / sqrt(80).
+//   V^T P^T    three 32-row output tiles; V^T rows 80 .. 95 are written as ZEROS once, before the first barrier, in both stages
+//              (the staging never touches them again), and output columns >= 80 are never stored.
+//   K in LDS   [key][80 d] rows of 160 bytes = ten 16-byte chunks; logical chunk c of row r sits at chunk c ^ ((r >> 4) & 1).
+//              Why that is conflict-free: a fragment read is one ds_read_b128 in which lane l reads row r = l & 31, chunk
+//              2 ks + (l >> 5); the instruction is served in four groups of 16 lanes, rows {0-3, 12-15, 20-27} and
+//              {4-11, 16-19, 28-31} of each half-wave, one logical chunk per group, and a group is conflict-free when its 16
+//              rows fall into 16 distinct 16-byte slots of the 256-byte bank row.  The slot of (r, c) is (10 r + c') mod 16 and
+//              10 r mod 16 = 2 (5 r mod 8) takes the eight EVEN values, by r mod 8; both row sets hold every residue mod 8
+//              exactly twice, as {r, r + 24} or {r, r + 8}: two rows that differ in bit 4.  c' = c ^ bit 4 moves one row of each
+//              pair to the neighbouring odd slot (c ^ 1 stays inside 0 .. 9): 8 even + 8 odd slots, 16 distinct.  (The XOR
+//              with (r >> 1) & 7 of the 128-byte rows needs eight chunks per row.)
+//   staging    item q = tid + 256 n: K chunk q % 10 of row q / 10, n = 0 .. 2 (640 chunks, the third pass half idle); V chunk
+//              q % 10 of the key PAIR q / 10, n = 0 .. 1 (320 pairs of chunks).  At D = 64 the same map is row tid >> 3 (+ 32),
+//              chunk tid & 7, as before.  Two stages, one barrier per tile, no early return.
+template <int D>
 __global__ __launch_bounds__(256) void attention_long_f16_kernel(const _Float16* __restrict__ qkv, int S, int H, int QB,
                                                                  _Float16* __restrict__ out) {
+    static_assert(D == 64 || D == 80, "the head widths that have an LDS layout");
     constexpr int KT = ATTN_LONG_KT, NJ = KT / 32;
+    constexpr int NKS = D / 16, NDT = (D + 31) / 32, CH = D / 8; // K-steps of K Q^T; 32-row tiles of V^T P^T; 16-byte chunks per row
+    constexpr int KP = 2 * D;                                   // K pitch in bytes
     constexpr int VP = KT + 4;                                  // V^T pitch in halves: 8-byte aligned rows, 34 banks apart
-    constexpr int K_BYTES = KT * 128, V_BYTES = 64 * VP * 2, STAGE = K_BYTES + V_BYTES;
+    constexpr int K_BYTES = KT * KP, V_BYTES = 32 * NDT * VP * 2, STAGE = K_BYTES + V_BYTES;
+    constexpr int K_ITEMS = KT * CH, V_ITEMS = KT / 2 * CH;     // staging items of a tile and the passes of 256 threads over them
+    constexpr int NKP = (K_ITEMS + 255) / 256, NVP = (V_ITEMS + 255) / 256;
+    constexpr float SCALE = D == 64 ? 0.125f : 0.111803398874989485f;       // 1 / sqrt(D): exact, or the float nearest 1 / sqrt(80)
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qb = (int)(blockIdx.x % (unsigned)QB), bh = (int)(blockIdx.x / (unsigned)QB);
     const int b = bh / H, h = bh - b * H;
-    const int E = H * 64;
+    const int E = H * D;
     const long long ld = 3LL * E;
-    const _Float16* qbase = qkv + (long long)b * S * ld + h * 64;
+    const _Float16* qbase = qkv + (long long)b * S * ld + h * D;
     const _Float16* kb = qbase + E;
     const _Float16* vb = qbase + 2 * E;
     const int r = lane & 31, hh = lane >> 5;
     const int i = qb * 128 + wave * 32 + r;                    // this lane's query
     const half8_t z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-    half8_t qf[4];
+    half8_t qf[NKS];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = i < S ? *reinterpret_cast<const half8_t*>(qbase + (long long)i * ld + 16 * ks + 8 * hh) : z8;
-    // staging: thread -> 16-byte chunk sc of K rows sr, sr + 32 and of V rows 2 vp, 2 vp + 1
-    const int sc = tid & 7, sr = tid >> 3, vp = tid >> 3;
-    half8_t gk[2], gv[2];
+    for (int ks = 0; ks < NKS; ++ks) qf[ks] = i < S ? *reinterpret_cast<const half8_t*>(qbase + (long long)i * ld + 16 * ks + 8 * hh) : z8;
+    // staging: pass n of a thread -> 16-byte chunk kc[n] of K row kr[n]; chunk vc[n] of V rows 2 vq[n], 2 vq[n] + 1
+    int kr[NKP], kc[NKP], vq[NVP], vc[NVP];
+#pragma unroll
+    for (int n = 0; n < NKP; ++n) { kr[n] = (tid + 256 * n) / CH; kc[n] = (tid + 256 * n) % CH; }
+#pragma unroll
+    for (int n = 0; n < NVP; ++n) { vq[n] = (tid + 256 * n) / CH; vc[n] = (tid + 256 * n) % CH; }
+    // a pass beyond the items (D = 80: the upper half of the last one) fetches and writes nothing
+    const auto k_on = [&](int n) { return K_ITEMS % 256 == 0 || tid + 256 * n < K_ITEMS; };
+    const auto v_on = [&](int n) { return V_ITEMS % 256 == 0 || tid + 256 * n < V_ITEMS; };
+    // chunk c of K row `row` in LDS (the comment above)
+    const auto k_swz = [](int c, int row) { return D == 64 ? c ^ ((row >> 1) & 7) : c ^ ((row >> 4) & 1); };
+    half8_t gk[NKP], gv[NVP][2];
 #define AL_FETCH(J0)                                                                                       \
     {                                                                                                     \
-        _Pragma("unroll") for (int n = 0; n < 2; ++n) {                                                    \
-            const int jk = (J0) + sr + 32 * n, jv = (J0) + 2 * vp + n;                                     \
-            gk[n] = jk < S ? *reinterpret_cast<const half8_t*>(kb + (long long)jk * ld + 8 * sc) : z8;      \
-            gv[n] = jv < S ? *reinterpret_cast<const half8_t*>(vb + (long long)jv * ld + 8 * sc) : z8;      \
+        _Pragma("unroll") for (int n = 0; n < NKP; ++n) {                                                  \
+            const int jk = (J0) + kr[n];                                                                   \
+            gk[n] = (k_on(n) && jk < S) ? *reinterpret_cast<const half8_t*>(kb + (long long)jk * ld + 8 * kc[n]) : z8; \
         }                                                                                                  \
+        _Pragma("unroll") for (int n = 0; n < NVP; ++n)                                                    \
+            _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                \
+                const int jv = (J0) + 2 * vq[n] + u;                                                       \
+                gv[n][u] = (v_on(n) && jv < S) ? *reinterpret_cast<const half8_t*>(vb + (long long)jv * ld + 8 * vc[n]) : z8; \
+            }                                                                                              \
     }
 #define AL_WRITE(SOFF)                                                                                     \
     {                                                                                                     \
-        _Pragma("unroll") for (int n = 0; n < 2; ++n) {                                                    \
-            const int row = sr + 32 * n;                                                                   \
-            *reinterpret_cast<half8_t*>(lds + (SOFF) + row * 128 + ((sc ^ ((row >> 1) & 7)) << 4)) = gk[n]; \
-        }                                                                                                  \
+        _Pragma("unroll") for (int n = 0; n < NKP; ++n)                                                    \
+            if (k_on(n)) *reinterpret_cast<half8_t*>(lds + (SOFF) + kr[n] * KP + (k_swz(kc[n], kr[n]) << 4)) = gk[n]; \
         _Float16* vt_ = reinterpret_cast<_Float16*>(lds + (SOFF) + K_BYTES);                               \
-        _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                    \
-            half2_t pr = {gv[0][e], gv[1][e]};                                                             \
-            *reinterpret_cast<half2_t*>(vt_ + (8 * sc + e) * VP + 2 * vp) = pr;                             \
-        }                                                                                                  \
+        _Pragma("unroll") for (int n = 0; n < NVP; ++n)                                                    \
+            if (v_on(n)) {                                                                                 \
+                _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                            \
+                    half2_t pr = {gv[n][0][e], gv[n][1][e]};                                               \
+                    *reinterpret_cast<half2_t*>(vt_ + (8 * vc[n] + e) * VP + 2 * vq[n]) = pr;               \
+                }                                                                                          \
+            }                                                                                              \
     }
-    float16_t oc[2];
+    float16_t oc[NDT];
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+    for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
         for (int e = 0; e < 16; ++e) oc[dt][e] = 0.f;
     float m = -INFINITY, l = 0.f;
     const int T = (S + KT - 1) / KT;                            // the same for every wave of the workgroup
+    if constexpr (32 * NDT > D) {                               // V^T rows D .. 32 NDT - 1 of both stages: zeros, written once
+        constexpr int ZW = (32 * NDT - D) * VP / 2;             // dwords; the rows are contiguous
+        for (int w = tid; w < 2 * ZW; w += 256)
+            *reinterpret_cast<unsigned*>(lds + (w / ZW) * STAGE + K_BYTES + D * VP * 2 + (w % ZW) * 4) = 0u;
+    }
     AL_FETCH(0)
     AL_WRITE(0)
     __syncthreads();
-    const int ksw = (r >> 1) & 7;
+    const int ksw = D == 64 ? (r >> 1) & 7 : (r >> 4) & 1;
 #pragma unroll 1
     for (int t = 0; t < T; ++t) {
         const int soff = (t & 1) * STAGE;
@@ -789,8 +836,8 @@ __global__ __launch_bounds__(256) void attention_long_f16_kernel(const _Float16*
 #pragma unroll
             for (int e = 0; e < 16; ++e) s[jt][e] = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const half8_t kf = *reinterpret_cast<const half8_t*>(kl + (32 * jt + r) * 128 + (((2 * ks + hh) ^ ksw) << 4));
+            for (int ks = 0; ks < NKS; ++ks) {
+                const half8_t kf = *reinterpret_cast<const half8_t*>(kl + (32 * jt + r) * KP + (((2 * ks + hh) ^ ksw) << 4));
                 s[jt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[jt], 0, 0, 0);
             }
         }
@@ -801,7 +848,7 @@ __global__ __launch_bounds__(256) void attention_long_f16_kernel(const _Float16*
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int j = j0 + 32 * jt + 8 * (e >> 2) + 4 * hh + (e & 3);
-                const float v = j < S ? s[jt][e] * 0.125f : -INFINITY;
+                const float v = j < S ? s[jt][e] * SCALE : -INFINITY;
                 s[jt][e] = v;
                 tm = fmaxf(tm, v);
             }
@@ -820,7 +867,7 @@ __global__ __launch_bounds__(256) void attention_long_f16_kernel(const _Float16*
             }
         l = l * alpha + psum;
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
+        for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int e = 0; e < 16; ++e) oc[dt][e] *= alpha;
 #pragma unroll
@@ -831,7 +878,7 @@ __global__ __launch_bounds__(256) void attention_long_f16_kernel(const _Float16*
 #pragma unroll
                 for (int e = 0; e < 8; ++e) pf[e] = (_Float16)s[jt][8 * q + e];
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
+                for (int dt = 0; dt < NDT; ++dt) {
                     const _Float16* vr = vt + (32 * dt + r) * VP + 32 * jt + 16 * q + 4 * hh;
                     const half4_t lo4 = *reinterpret_cast<const half4_t*>(vr);
                     const half4_t hi4 = *reinterpret_cast<const half4_t*>(vr + 8);
@@ -849,11 +896,12 @@ __global__ __launch_bounds__(256) void attention_long_f16_kernel(const _Float16*
     l += __shfl_xor(l, 32, 64);
     const float inv = 1.0f / l;                                 // l >= 1: the key of the maximum contributes exp(0)
     if (i < S) {
-        _Float16* orow = out + ((long long)b * S + i) * E + h * 64;
+        _Float16* orow = out + ((long long)b * S + i) * E + h * D;
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
+        for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
+                if (32 * dt + 8 * g >= D) continue;             // D = 80: rows 80 .. 95 of the third tile are padding, never stored
                 half4_t o4;
 #pragma unroll
                 for (int k2 = 0; k2 < 4; ++k2) o4[k2] = (_Float16)(oc[dt][4 * g + k2] * inv);
@@ -940,6 +988,34 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ 
     }
 }
 
+// CLIPScore's paired cosine: out[i] = (a_i . b_i) / sqrt((a_i . a_i)(b_i . b_i)) of row i of two (n, d) tables, ONE WAVE per row.
+// Every product and sum is fp64 (a product of two fp16 or fp32 values is exact there) in a fixed order: lane l adds the
+// elements l, l + 64, ... in turn, then a butterfly (xor 32 .. 1) leaves the same total in every lane.  No atomics: two launches
+// give the same bits.  A zero row is 0 / sqrt(0) = NaN, as numpy's 0 / 0.  Not a hot path (n * d reads once).
+template <typename T>
+__global__ __launch_bounds__(256) void paired_cosine_kernel(const T* __restrict__ a, const T* __restrict__ b, long long n, int d,
+                                                            double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const T* ar = a + row * d;
+    const T* br = b + row * d;
+    double ab = 0.0, aa = 0.0, bb = 0.0;
+    for (int c = lane; c < d; c += 64) {
+        const double x = (double)ar[c], y = (double)br[c];
+        ab += x * y;
+        aa += x * x;
+        bb += y * y;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ab += __shfl_xor(ab, off, 64);
+        aa += __shfl_xor(aa, off, 64);
+        bb += __shfl_xor(bb, off, 64);
+    }
+    if (lane == 0) out[row] = ab / sqrt(aa * bb);
+}
+
 inline int grid1d(long long total) {
     long long b = (total + 255) / 256;
     return (int)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
@@ -1024,20 +1100,20 @@ int gemm_f16_entry(const void* a_dev, int64_t lda, const void* w_dev, int64_t ld
     return gemm_launch<EPI_F16>(p, stream);
 }
 
-// tise_layernorm_f16 and both outputs of tise_layernorm_f32: x, gamma, beta and out move as 16-byte pieces of eight halves
-// or four floats
-template <typename InT, typename OutT>
+// tise_layernorm_f16, tise_layernorm_wide_f16 (NG = 4) and both outputs of tise_layernorm_f32: x, gamma, beta and out move as
+// 16-byte pieces of eight halves or four floats; C <= 512 NG
+template <typename InT, typename OutT, int NG = 2>
 int layernorm_launch(const void* x_dev, int64_t ldx, const void* gamma_dev, const void* beta_dev, void* out_dev, int64_t ldo,
                      int64_t rows, int C, float eps, void* stream) {
     constexpr int64_t xmul = 16 / sizeof(InT), omul = 16 / sizeof(OutT);
-    if (!x_dev || !gamma_dev || !beta_dev || !out_dev || rows < 0 || C <= 0 || C > 1024 || C % 8 != 0 || ldx % xmul != 0 ||
+    if (!x_dev || !gamma_dev || !beta_dev || !out_dev || rows < 0 || C <= 0 || C > 512 * NG || C % 8 != 0 || ldx % xmul != 0 ||
         ldo % omul != 0 || ldx < C || ldo < C ||
         ((reinterpret_cast<uintptr_t>(x_dev) | reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(gamma_dev) |
           reinterpret_cast<uintptr_t>(beta_dev)) & 15) != 0)
         return TISE_ERR_INVALID_ARG;
     if (rows == 0) return TISE_OK;
     if ((rows + 3) / 4 > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((layernorm_kernel<InT, OutT>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((layernorm_kernel<InT, OutT, NG>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const InT*>(x_dev), ldx, reinterpret_cast<const InT*>(gamma_dev),
                        reinterpret_cast<const InT*>(beta_dev), reinterpret_cast<OutT*>(out_dev), ldo, (int)rows, C, eps);
     TISE_LAUNCH_CHECK();
@@ -1124,6 +1200,30 @@ int tise_layernorm_f16(const void* x_dev, int64_t ldx, const void* gamma_dev, co
     return layernorm_launch<_Float16, _Float16>(x_dev, ldx, gamma_dev, beta_dev, out_dev, ldo, rows, C, eps, stream);
 }
 
+int tise_layernorm_wide_f16(const void* x_dev, int64_t ldx, const void* gamma_dev, const void* beta_dev, void* out_dev, int64_t ldo,
+                            int64_t rows, int C, float eps, void* stream) {
+    return layernorm_launch<_Float16, _Float16, 4>(x_dev, ldx, gamma_dev, beta_dev, out_dev, ldo, rows, C, eps, stream);
+}
+
+int tise_paired_cosine(const void* img_dev, const void* txt_dev, int64_t n, int d, int is_f16, double* out_cos_dev, void* stream) {
+    const uintptr_t mask = is_f16 ? 1 : 3;
+    if (!img_dev || !txt_dev || !out_cos_dev || n < 0 || d <= 0 || (is_f16 != 0 && is_f16 != 1) ||
+        ((reinterpret_cast<uintptr_t>(img_dev) | reinterpret_cast<uintptr_t>(txt_dev)) & mask) != 0 ||
+        (reinterpret_cast<uintptr_t>(out_cos_dev) & 7) != 0)
+        return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    if ((n + 3) / 4 > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    if (is_f16)
+        hipLaunchKernelGGL(paired_cosine_kernel<_Float16>, grid, block, 0, (hipStream_t)stream, reinterpret_cast<const _Float16*>(img_dev),
+                           reinterpret_cast<const _Float16*>(txt_dev), (long long)n, d, out_cos_dev);
+    else
+        hipLaunchKernelGGL(paired_cosine_kernel<float>, grid, block, 0, (hipStream_t)stream, reinterpret_cast<const float*>(img_dev),
+                           reinterpret_cast<const float*>(txt_dev), (long long)n, d, out_cos_dev);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
 int tise_attention_f16(const void* qkv_dev, int batch, int seq, int heads, int head_dim, int causal, void* out_dev, void* stream) {
     if (!qkv_dev || !out_dev || batch < 0 || seq <= 0 || seq > 96 || heads <= 0 || head_dim != 64 ||
         ((reinterpret_cast<uintptr_t>(qkv_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15) != 0)    // 16-byte q / k / v loads
@@ -1144,15 +1244,19 @@ int tise_attention_f16(const void* qkv_dev, int batch, int seq, int heads, int h
 int tise_attention_long_key_tile(void) { return ATTN_LONG_KT; }
 
 int tise_attention_long_f16(const void* qkv_dev, int batch, int seq, int heads, int head_dim, void* out_dev, void* stream) {
-    if (!qkv_dev || !out_dev || batch < 0 || seq <= 0 || heads <= 0 || head_dim != 64 ||
-        ((reinterpret_cast<uintptr_t>(qkv_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15) != 0)    // 16-byte q / k / v loads
+    // 16-byte q / k / v loads: the q, k and v base of every head is 16-byte aligned when qkv is (a head is 128 or 160 bytes)
+    if (!qkv_dev || !out_dev || batch < 0 || seq <= 0 || heads <= 0 || (head_dim != 64 && head_dim != 80) ||
+        ((reinterpret_cast<uintptr_t>(qkv_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15) != 0)
         return TISE_ERR_INVALID_ARG;
     if (batch == 0) return TISE_OK;
     const long long qblocks = ((long long)seq + 127) / 128;
     const long long bh = (long long)batch * heads;
     if (qblocks * bh > 0x7fffffffLL) return TISE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(attention_long_f16_kernel, dim3((unsigned)(qblocks * bh)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const _Float16*>(qkv_dev), seq, heads, (int)qblocks, reinterpret_cast<_Float16*>(out_dev));
+    const dim3 grid((unsigned)(qblocks * bh)), block(256);
+    const _Float16* q = reinterpret_cast<const _Float16*>(qkv_dev);
+    _Float16* o = reinterpret_cast<_Float16*>(out_dev);
+    if (head_dim == 64) hipLaunchKernelGGL(attention_long_f16_kernel<64>, grid, block, 0, (hipStream_t)stream, q, seq, heads, (int)qblocks, o);
+    else hipLaunchKernelGGL(attention_long_f16_kernel<80>, grid, block, 0, (hipStream_t)stream, q, seq, heads, (int)qblocks, o);
     TISE_LAUNCH_CHECK();
     return TISE_OK;
 }

@@ -959,3 +959,22 @@ def cosine_top1(img_emb, txt_emb, txt_index=None, normalize=True, logit_scale=10
               ctypes.c_int64(n), int(c), int(d), 0 if img_emb.dtype == torch.float32 else 1, 1 if normalize else 0,
               ctypes.c_float(logit_scale), _ptr(top1), _ptr(p0) if p0 is not None else None, _stream())
     return top1, p0
+
+
+def paired_cosine(img_emb, txt_emb):
+    """cos(img_emb[i], txt_emb[i]) for every row of two (n, d) device tables, fp16 or fp32 alike -> (n,) float64 on the device
+    (csrc/clip_ops.hip, tise_paired_cosine: fp64 products and sums in a fixed order, one wave per row, no atomics -- two calls
+    give the same bits, and no n x n product is formed).  A zero row gives NaN, as numpy's 0 / 0."""
+    _require_cuda(img_emb, txt_emb)
+    if img_emb.dim() != 2 or img_emb.shape != txt_emb.shape:
+        raise ValueError(f"paired rows need two (n, d) tables of one shape (got {tuple(img_emb.shape)} and {tuple(txt_emb.shape)})")
+    if img_emb.dtype != txt_emb.dtype or img_emb.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"both tables fp16 or both fp32 (got {img_emb.dtype} and {txt_emb.dtype})")
+    img_emb, txt_emb = img_emb.contiguous(), txt_emb.contiguous()
+    n, d = img_emb.shape
+    out = torch.empty(n, dtype=torch.float64, device=img_emb.device)
+    if n == 0:                                                              # an empty shard: nothing to launch (and no pointer to pass)
+        return out
+    _lib.call("tise_paired_cosine", _ptr(img_emb), _ptr(txt_emb), ctypes.c_int64(n), int(d),
+              1 if img_emb.dtype == torch.float16 else 0, _ptr(out), _stream())
+    return out
