@@ -328,6 +328,38 @@ int tise_prdc_counts(const float* r_dev, int64_t rows_r, int64_t ld_r, const dou
                      int32_t* prec_dev, void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Nearest row of another set, with its index (csrc/knn.hip): the primitive of authenticity (AuthPct; Alaa et al. 2022, as the
+ * `dgm-eval` package of Stein et al. 2023 states it) and of "which training image is this sample closest to".  No counterpart in
+ * the reference; dgm-eval writes the whole n x m fp32 torch.cdist matrix.  For every query row i, over the base rows j, with the
+ * d2 of the block above (the same bits for the same pair as in tise_knn_radius2 and tise_prdc_counts):
+ *     d2[i]  = min_j d2(Q_i, B_j)          idx[i] = the SMALLEST j that attains it
+ * exclude_diagonal = 1 skips the pair j == i by row number (the within-set pass; it requires rows_q == rows_b, and q_dev may be
+ * b_dev): d2 then has the bits of tise_knn_radius2 at k = 1.  The grid is that block's, (query row tiles of 64) x (S column
+ * splits) with the same col_splits rule; a workgroup writes one (d2, index) candidate per (row, split) and a merge launch takes
+ * the minimum of the S candidates.  The ONLY combination anywhere is the lexicographic minimum of (d2, index),
+ * v < best || (v == best && j < bestj), which is order-independent: the result is bitwise reproducible and does not depend on
+ * col_splits.  No floating-point atomics, no n x m matrix.
+ *   q_dev, b_dev          fp32 feature matrices, rows of ld floats, d columns used (ld >= d, ld % 4 == 0, 16-byte aligned base)
+ *   rows_q, rows_b        1 .. 2^24 each
+ *   d2_dev, idx_dev       rows_q doubles (8-byte aligned) and rows_q int32 (out)
+ *   ws_dev                device scratch, 8-byte aligned, ws_bytes >= tise_nn_workspace_bytes(rows_q, rows_b, col_splits)
+ *                         = 8 * (rows_q + rows_b) + (8 + 4) * rows_q * S: the norms of both sides, then one double and one int32
+ *                         candidate per query row and split, S = min(col_splits or ceil(1024 / query row tiles), base row tiles)
+ * Non-finite feature rows (the rule of the block above, extended): a base row that holds a NaN or an infinity is nobody's
+ * nearest row -- d2 of every pair with it is NaN and both comparisons of the rule are false -- so every query row gets the bits
+ * of the same call without that base row (its index shifted accordingly).  A query row that holds one gets d2 = NaN, idx = -1.
+ * A query row with no candidate at all -- every base row non-finite, or rows_b == 1 under exclude_diagonal -- gets d2 = +inf,
+ * idx = -1.
+ * Rejected before any HIP call (TISE_ERR_INVALID_ARG): a NULL pointer, rows_q < 1 or rows_b < 1, d <= 0, ld < d, ld % 4 != 0, a
+ * feature base that is not 16-byte aligned, col_splits outside 0 .. 1024, exclude_diagonal outside {0, 1} or set while rows_q !=
+ * rows_b, a misaligned output, a workspace too small or misaligned.  TISE_ERR_UNSUPPORTED: more than 2^24 rows on either side.
+ * ------------------------------------------------------------------------------------------ */
+int tise_nn_workspace_bytes(int64_t rows_q, int64_t rows_b, int col_splits, size_t* bytes);
+int tise_nn_argmin(const float* q_dev, int64_t rows_q, int64_t ld_q, const float* b_dev, int64_t rows_b, int64_t ld_b, int d,
+                   int exclude_diagonal, int col_splits, double* d2_dev, int32_t* idx_dev, void* ws_dev, size_t ws_bytes,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a6) Frechet distance.
  * Replaces calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps)
  *                                           image_realism/FID/fid_score.py:121-171

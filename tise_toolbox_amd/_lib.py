@@ -101,6 +101,9 @@ SIGNATURES = {
     "tise_knn_radius2": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "tise_prdc_counts": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tise_nn_workspace_bytes": (c_int, [c_int64, c_int64, c_int, POINTER(c_size_t)]),
+    "tise_nn_argmin": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
     "tise_frechet_create": (c_int, [c_int, POINTER(c_void_p)]),
     "tise_frechet_destroy": (c_int, [c_void_p]),
     "tise_frechet_distance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),

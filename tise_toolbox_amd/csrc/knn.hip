@@ -23,6 +23,11 @@
 //   prdc_counts_kernel     cross pass R x F; compares on the accumulator registers, row-side results accumulate in registers over
 //                          the walk and leave through integer LDS / global atomics, the column-side flag through atomicOr.
 //                          bound: fp64 MFMA, as above
+//   nn_argmin_kernel       cross pass Q x B (or a set against itself without the diagonal): the nearest base row of every query
+//                          row WITH ITS INDEX (authenticity.py).  The lexicographic minimum of (d2, index) stays in the registers
+//                          of the thread that owns the accumulator rows over the whole walk; the 32 threads that share a row meet
+//                          once per workgroup in the slab buffer; one candidate per (row, split).  bound: fp64 MFMA, as above
+//   nn_merge_kernel        one thread per row: the minimum of its S candidates.  bound: latency
 //
 // Reproducible by construction: the only cross-workgroup combination is integer add / or (order-independent) and a minimum
 // selection over candidates (order-independent); there are no floating-point atomics.
@@ -187,6 +192,106 @@ __global__ __launch_bounds__(256, 2) void prdc_counts_kernel(const float* __rest
     }
 }
 
+// ---- nearest row of another set, with its index ------------------------------------------------------------------------------
+// The only combination, in a thread, in a workgroup and across the splits: the lexicographic minimum of (d2, index).  It is
+// order-independent, so the result does not depend on the walk, on the lane map or on col_splits.  A NaN d2 (a non-finite row
+// on either side) fails both comparisons and is never a candidate.
+#define NN_NONE 0x7fffffff   // the index of "no candidate": it sorts after every real index, and d2 = +inf with it
+#define NN_TP 33             // pitch of the end-of-walk staging: 64 rows x 32 threads that share a row
+
+static_assert(64 * NN_TP * (sizeof(double) + sizeof(int)) <= GT_ROWS_LDS_FLOATS * sizeof(float), "the staged candidates must fit the slab buffer");
+
+__device__ __forceinline__ void nn_take(double& best, int& bestj, double v, int j) {
+    if (v < best || (v == best && j < bestj)) {
+        best = v;
+        bestj = j;
+    }
+}
+
+// Q x B pass.  Every thread keeps one (d2, index) for each of its eight accumulator rows over the whole walk -- the first
+// minimum is taken on the accumulator registers, nothing is staged per tile -- and the 32 threads that share a row meet once,
+// after the walk, in the slab buffer.  bound: fp64 MFMA, as knn_radius2_kernel, without its per-tile scan
+__global__ __launch_bounds__(256, 2) void nn_argmin_kernel(const float* __restrict__ Q, int64_t ldq, int n, const float* __restrict__ B,
+                                                           int64_t ldb, int m, int d, int exclude_diagonal,
+                                                           const double* __restrict__ norm_q, const double* __restrict__ norm_b,
+                                                           double* __restrict__ cand_d2, int* __restrict__ cand_idx) {
+    __shared__ __attribute__((aligned(16))) float lds[GT_ROWS_LDS_FLOATS];
+    const int tm = blockIdx.x, s = blockIdx.y, S = gridDim.y;
+    const int T = (m + 63) >> 6;
+    const int t0 = (int)((int64_t)s * T / S), t1 = (int)((int64_t)(s + 1) * T / S);
+    const int tid = threadIdx.x;
+    const GtAccLanes at;
+    GtRowFetch fa, fb;
+    fa.bind(Q, ldq, nullptr, 0, tm * 64, n, tid);
+    double na[2][4], best[2][4];
+    int bestj[2][4];
+    gt_rows_load(na, norm_q, tm * 64, n, at);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            best[a][r] = __builtin_inf();
+            bestj[a][r] = NN_NONE;
+        }
+    for (int tn = t0; tn < t1; ++tn) {
+        fb.bind(B, ldb, nullptr, 0, tn * 64, m, tid);
+        double4_t acc[2][2];
+        gt_acc_zero(acc);
+        gemm_tile_64x64_rows_f32(fa, fb, d, acc, lds);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int col = tn * 64 + at.col(b);
+            const bool col_on = col < m;
+            const double nb = norm_b[col_on ? col : m - 1];
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = tm * 64 + at.row(a, r);
+                    const double v = rows_d2(na[a][r], nb, acc[a][b][r]);
+                    if (col_on && !(exclude_diagonal && row == col)) nn_take(best[a][r], bestj[a][r], v, col);
+                }
+        }
+    }
+    // the walk's last barrier lies behind every wave: the slab buffer is free.  Slot = this thread's place among the 32 that hold
+    // the same rows (2 wave columns x 16 lanes)
+    double* sd = reinterpret_cast<double*>(lds);
+    int* sj = reinterpret_cast<int*>(sd + 64 * NN_TP);
+    const int slot = ((tid >> 6) & 1) * 16 + (tid & 15);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            sd[at.row(a, r) * NN_TP + slot] = best[a][r];
+            sj[at.row(a, r) * NN_TP + slot] = bestj[a][r];
+        }
+    __syncthreads();
+    const int row = tm * 64 + tid;
+    if (tid < 64 && row < n) {
+        double v = __builtin_inf();
+        int j = NN_NONE;
+#pragma unroll 8
+        for (int c = 0; c < 32; ++c) nn_take(v, j, sd[tid * NN_TP + c], sj[tid * NN_TP + c]);
+        cand_d2[(int64_t)row * S + s] = v;
+        cand_idx[(int64_t)row * S + s] = j;
+    }
+}
+
+// one thread per query row: the minimum over its S candidates.  A query row with a non-finite value (norm NaN; no pair with it
+// was a candidate) gets (NaN, -1); a row without any candidate (+inf, -1).  bound: latency
+__global__ __launch_bounds__(256) void nn_merge_kernel(const double* __restrict__ cand_d2, const int* __restrict__ cand_idx,
+                                                       const double* __restrict__ norm_q, int n, int S, double* __restrict__ d2,
+                                                       int* __restrict__ idx) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    double v = __builtin_inf();
+    int j = NN_NONE;
+    for (int i = 0; i < S; ++i) nn_take(v, j, cand_d2[(int64_t)row * S + i], cand_idx[(int64_t)row * S + i]);
+    const double nq = norm_q[row];
+    d2[row] = nq == nq ? v : nq;
+    idx[row] = (nq == nq && j != NN_NONE) ? j : -1;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 // column splits of a (rows x cols) pass: the caller's value, or enough to put about four workgroups on each of 256 compute
 // units when there are few row tiles; never more than there are column tiles.  A function of the sizes alone (no device query),
@@ -265,6 +370,45 @@ int tise_prdc_counts(const float* r_dev, int64_t rows_r, int64_t ld_r, const dou
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)knn_splits(rows_r, rows_f, col_splits));
     hipLaunchKernelGGL(prdc_counts_kernel, grid, dim3(256), 0, st, r_dev, ld_r, n, r2_r_dev, f_dev, ld_f, m, r2_f_dev, d, norm_r,
                        norm_f, cnt_dev, rec_dev, prec_dev);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
+
+int tise_nn_workspace_bytes(int64_t rows_q, int64_t rows_b, int col_splits, size_t* bytes) {
+    if (!bytes || rows_q < 1 || rows_b < 1 || col_splits < 0 || col_splits > KNN_MAX_SPLITS) return TISE_ERR_INVALID_ARG;
+    if (rows_q > KNN_MAX_ROWS || rows_b > KNN_MAX_ROWS) return TISE_ERR_UNSUPPORTED;
+    const size_t S = (size_t)knn_splits(rows_q, rows_b, col_splits);
+    *bytes = sizeof(double) * (size_t)(rows_q + rows_b) + (sizeof(double) + sizeof(int32_t)) * (size_t)rows_q * S;
+    return TISE_OK;
+}
+
+int tise_nn_argmin(const float* q_dev, int64_t rows_q, int64_t ld_q, const float* b_dev, int64_t rows_b, int64_t ld_b, int d,
+                   int exclude_diagonal, int col_splits, double* d2_dev, int32_t* idx_dev, void* ws_dev, size_t ws_bytes,
+                   void* stream) {
+    if (col_splits < 0 || col_splits > KNN_MAX_SPLITS || (exclude_diagonal != 0 && exclude_diagonal != 1)) return TISE_ERR_INVALID_ARG;
+    int rc = knn_side_check(q_dev, rows_q, ld_q, d, 1);
+    if (rc != TISE_OK) return rc;
+    rc = knn_side_check(b_dev, rows_b, ld_b, d, 1);
+    if (rc != TISE_OK) return rc;
+    if (exclude_diagonal && rows_q != rows_b) return TISE_ERR_INVALID_ARG;
+    if (!d2_dev || !idx_dev || (reinterpret_cast<uintptr_t>(d2_dev) & 7) || (reinterpret_cast<uintptr_t>(idx_dev) & 3)) return TISE_ERR_INVALID_ARG;
+    size_t need = 0;
+    rc = tise_nn_workspace_bytes(rows_q, rows_b, col_splits, &need);
+    if (rc != TISE_OK) return rc;
+    if (!ws_dev || (reinterpret_cast<uintptr_t>(ws_dev) & 7) || ws_bytes < need) return TISE_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int S = knn_splits(rows_q, rows_b, col_splits), n = (int)rows_q, m = (int)rows_b;
+    double* norm_q = reinterpret_cast<double*>(ws_dev);
+    double* norm_b = norm_q + rows_q;
+    double* cand_d2 = norm_b + rows_b;
+    int* cand_idx = reinterpret_cast<int*>(cand_d2 + (size_t)rows_q * S);
+    rc = rows_norm2(q_dev, ld_q, nullptr, 0, rows_q, b_dev, ld_b, nullptr, 0, rows_b, d, norm_q, st);   // norm_b = norm_q + rows_q
+    if (rc != TISE_OK) return rc;
+    hipLaunchKernelGGL(nn_argmin_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)S), dim3(256), 0, st, q_dev, ld_q, n, b_dev, ld_b,
+                       m, d, exclude_diagonal, norm_q, norm_b, cand_d2, cand_idx);
+    TISE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nn_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cand_d2, cand_idx, norm_q, n, S, d2_dev,
+                       idx_dev);
     TISE_LAUNCH_CHECK();
     return TISE_OK;
 }

@@ -649,8 +649,9 @@ class GaussianMMD(_GroupedMMD):
 
 
 class KnnManifold(_RowsTileUser):
-    """k-nearest-neighbour radii and the precision / recall / density / coverage counts on resident fp32 rows (tise_knn_radius2
-    and tise_prdc_counts in include/tise_hip.h; csrc/knn.hip).  Owns the workspace; bitwise reproducible."""
+    """k-nearest-neighbour radii, the precision / recall / density / coverage counts and the nearest row of another set on
+    resident fp32 rows (tise_knn_radius2, tise_prdc_counts and tise_nn_argmin in include/tise_hip.h; csrc/knn.hip).  Owns the
+    workspace; bitwise reproducible."""
 
     def radius2(self, X, k, col_splits=0):
         """X (n, d) fp32 CUDA tensor (row stride may exceed d), n >= k + 1, 1 <= k <= 16 -> (n,) fp64 CUDA tensor: the squared
@@ -690,6 +691,28 @@ class KnnManifold(_RowsTileUser):
             _lib.call("tise_prdc_counts", _ptr(R), R.shape[0], R.stride(0), _ptr(r2R), _ptr(F), F.shape[0], F.stride(0), _ptr(r2F),
                       int(R.shape[1]), int(col_splits), _ptr(cnt), _ptr(rec), _ptr(prec), _ptr(ws), ws.numel(), _stream())
         return cnt, rec != 0, prec != 0
+
+    def nearest(self, Q, B, exclude_diagonal=False, col_splits=0):
+        """Q (n, d), B (m, d) fp32 CUDA tensors (row stride may exceed d) -> (d2 (n,) fp64, idx (n,) int32) CUDA tensors
+        (tise_nn_argmin): the squared distance from every row of Q to its nearest row of B and that row's number, the smallest
+        one on a tie.  ``exclude_diagonal``: the within-set pass -- row i skips base row i; needs n == m, and d2 then has the bits
+        of ``radius2(k = 1)``.  The result does not depend on ``col_splits``.  A non-finite base row is nobody's nearest row; a
+        non-finite query row gets (NaN, -1); a query row without any candidate (+inf, -1)."""
+        Q, B = _rows_side(Q, "Q"), _rows_side(B, "B")
+        if Q.shape[1] != B.shape[1] or Q.shape[1] < 1 or not Q.shape[0] or not B.shape[0]:
+            raise ValueError("Q and B need rows and the same, positive number of columns")
+        if exclude_diagonal and Q.shape[0] != B.shape[0]:
+            raise ValueError(f"exclude_diagonal is the within-set pass: the row counts must agree (got {Q.shape[0]} and {B.shape[0]})")
+        col_splits = int(col_splits)
+        d2 = torch.empty(Q.shape[0], dtype=torch.float64, device=self.device)
+        idx = torch.empty(Q.shape[0], dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            nbytes = ctypes.c_size_t()
+            _lib.call("tise_nn_workspace_bytes", Q.shape[0], B.shape[0], col_splits, ctypes.byref(nbytes))
+            ws = self._workspace(nbytes.value)
+            _lib.call("tise_nn_argmin", _ptr(Q), Q.shape[0], Q.stride(0), _ptr(B), B.shape[0], B.stride(0), int(Q.shape[1]),
+                      1 if exclude_diagonal else 0, col_splits, _ptr(d2), _ptr(idx), _ptr(ws), ws.numel(), _stream())
+        return d2, idx
 
 
 def _wrap_device_doubles(ptr, n, device, owner=None):

@@ -11,6 +11,10 @@ neighbour metrics in that space:
     KD-DINOv2   (--kd)   kid.kid_from_features: 100 subsets of at most 1000 rows, the polynomial kernel (k(x, y) = (x.y / d + 1)^3)
                 -- dgm-eval's KD; printed as mean +- std over the subsets
     --prdc      the four numbers of prdc.prdc_from_features(ref, gen, nearest_k = 5)
+    --authpct   (needs --train) authenticity.authpct_from_features(train, gen): the share of generated samples that are not copies
+                of a training image; --nearest-train OUT.csv lists every sample's nearest training row
+    --vendi     vendi.vendi_from_features of the generated and of the reference rows (linear kernel, q = 1)
+    --fd-infinity   fd_infinity.fd_infinity_from_features(ref, gen): FD extrapolated to infinitely many samples (seeded subsets)
 
 THE TOWER is dinov2_hip.HipDino (csrc/clip_ops.hip): fp16 matrix-core operands, fp32 accumulation, an fp32 residual stream and
 fp32 features -- the arithmetic of torch.autocast(fp16); dgm-eval runs the tower in fp32.  ``--arch`` chooses vits14 / vitb14 /
@@ -33,6 +37,7 @@ import torch
 from . import _lib, dist as tdist, weights as tweights
 
 ARCH = "vitl14"
+NEAREST_TRAIN_COLUMNS = ("gen_row", "train_row", "d2", "authentic", "gen_file", "train_file")
 
 
 def arch_info(arch=ARCH):
@@ -103,17 +108,41 @@ def _side(path, tower, dev, batch_size, num_workers, feed, arch):
     return (feats,) + statistics(feats)
 
 
+def write_nearest_train_csv(path, near, gen_path, train_path):
+    """One line per generated row under a header line: gen_row,train_row,d2,authentic,gen_file,train_file.  A file column is
+    filled from img_data.get_filenames (the walk order the rows were embedded in) when that side is a directory, else empty."""
+    import csv
+    from . import img_data
+    gen_files = img_data.get_filenames(gen_path) if os.path.isdir(gen_path) else None
+    train_files = img_data.get_filenames(train_path) if os.path.isdir(train_path) else None
+    if gen_files is not None and len(gen_files) != len(near["idx"]):
+        raise RuntimeError(f"{gen_path}: {len(gen_files)} files now, {len(near['idx'])} rows were embedded")
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(NEAREST_TRAIN_COLUMNS)
+        for g, (t, d2, a) in enumerate(zip(near["idx"].tolist(), near["d2_gen"].tolist(), near["authentic"].tolist())):
+            w.writerow([g, t, repr(d2), int(a), gen_files[g] if gen_files is not None else "",
+                        train_files[t] if train_files is not None else ""])
+
+
 def calculate_fd_dinov2_given_paths(paths, batch_size=50, weights=None, seed=0, num_workers=0, feed="ring", arch=ARCH, kd=False,
-                                    prdc_k=None, save_features=""):
+                                    prdc_k=None, save_features="", train=None, authpct=False, nearest_train="", vendi=False,
+                                    fd_infinity=False, fd_infinity_seed=0):
     """-> dict(fd=float, kd=(mean, std) | None, prdc=OrderedDict | None) of two paths, each a directory or a feature file.
     ``weights=None``: seeded stand-in parameters (the CLI only allows that behind --synthetic-weights).  ``save_features``: the
-    FIRST path's rows (the reference set) are written there with their mu, sigma and the network tag."""
+    FIRST path's rows (the reference set) are written there with their mu, sigma and the network tag.
+    The memorization and diversity numbers add keys only when asked for: ``authpct`` (float; needs ``train``, the training set's
+    directory or feature file) and, with ``nearest_train`` (a CSV path, written by rank 0), the per-sample table; ``vendi`` and
+    ``vendi_reference`` (floats: the second and the first path's); ``fd_infinity`` (the dict of fd_infinity_from_features)."""
     from . import dinov2_hip, fid_score
     arch_info(arch)                                                        # an unknown arch: say so before anything is read
-    for p in paths:
+    if (authpct or nearest_train) and not train:
+        raise ValueError("authpct / nearest_train need the training set: train=PATH (a directory or a feature file)")
+    every = list(paths) + ([train] if train else [])
+    for p in every:
         if not os.path.exists(p):
             raise RuntimeError("Invalid path: %s" % p)
-    for p in paths:                                                        # refusals that need no GPU come first
+    for p in every:                                                        # refusals that need no GPU come first
         if p.endswith(".npz"):
             check_feature_file(p, arch)
     if not torch.cuda.is_available():
@@ -137,6 +166,21 @@ def calculate_fd_dinov2_given_paths(paths, batch_size=50, weights=None, seed=0, 
     if prdc_k is not None:
         from . import prdc
         out["prdc"] = prdc.prdc_from_features(f1, f2, nearest_k=int(prdc_k))
+    # every rank holds the same rows in the same order and evaluates these itself, as the k-NN metrics above
+    if authpct or nearest_train:
+        from . import authenticity
+        ft = _side(train, tower, dev, batch_size, num_workers, feed, arch)[0]
+        near = authenticity.nearest_train(ft, f2)
+        if authpct:
+            out["authpct"] = authenticity.authpct_from_counts(near["authentic"].sum(), len(near["authentic"]))
+        if nearest_train and tdist.is_main():
+            write_nearest_train_csv(nearest_train, near, paths[1], train)
+    if vendi:
+        from . import vendi as tvendi
+        out["vendi"], out["vendi_reference"] = tvendi.vendi_from_features(f2), tvendi.vendi_from_features(f1)
+    if fd_infinity:
+        from . import fd_infinity as tfdinf
+        out["fd_infinity"] = tfdinf.fd_infinity_from_features(f1, f2, seed=int(fd_infinity_seed))
     return out
 
 
@@ -146,6 +190,12 @@ def result_lines(res, arch, tag=""):
         lines.append(f"KD-DINOv2 ({arch}): {res['kd'][0]} +- {res['kd'][1]}{tag}")
     if res["prdc"] is not None:
         lines += [f"{name.capitalize()}-DINOv2 ({arch}): {res['prdc'][name]}{tag}" for name in ("precision", "recall", "density", "coverage")]
+    if "authpct" in res:
+        lines.append(f"AuthPct-DINOv2 ({arch}): {res['authpct']}{tag}")
+    if "vendi" in res:
+        lines += [f"Vendi-DINOv2 ({arch}): {res['vendi']}{tag}", f"Vendi-DINOv2 reference ({arch}): {res['vendi_reference']}{tag}"]
+    if "fd_infinity" in res:
+        lines.append(f"FD-infinity-DINOv2 ({arch}): {res['fd_infinity']['fd_infinity']}{tag}")
     return lines
 
 
@@ -158,6 +208,13 @@ def parse_args(argv=None):
     parser.add_argument("--kd", action="store_true", help="also report the kernel distance (KID's estimator in DINOv2 space)")
     parser.add_argument("--prdc", action="store_true", help="also report precision, recall, density and coverage in DINOv2 space")
     parser.add_argument("--prdc-k", type=int, default=5, help="nearest neighbours of --prdc (default 5)")
+    parser.add_argument("--train", default="", type=str, help="the generator's training images: a directory, or a feature file of --save-features (same --arch)")
+    parser.add_argument("--authpct", action="store_true", help="also report AuthPct: the share of --path2 samples that are not nearer to a --train row than that row's own nearest training neighbour")
+    parser.add_argument("--nearest-train", default="", type=str, metavar="OUT.csv",
+                        help="write every --path2 row's nearest --train row, its squared distance and the authentic flag to this CSV")
+    parser.add_argument("--vendi", action="store_true", help="also report the Vendi score (linear kernel, q = 1) of --path2, and of --path1 for comparison")
+    parser.add_argument("--fd-infinity", action="store_true", help="also report FD-infinity: FD extrapolated to infinitely many --path2 samples")
+    parser.add_argument("--fd-infinity-seed", type=int, default=0, help="seed of the --fd-infinity subsets (default 0)")
     parser.add_argument("--weights", default=None, type=str, help="DINOv2 state_dict (.pth) of the chosen tower; default: $TORCH_HOME/hub/checkpoints/dinov2_<arch>_pretrain.pth")
     parser.add_argument("--synthetic-weights", action="store_true",
                         help="seeded stand-in tower (plumbing / throughput only; results are tagged)")
@@ -174,12 +231,14 @@ def parse_args(argv=None):
         parser.error("--synthetic-weights and --weights are mutually exclusive")
     if args.prdc and not 1 <= args.prdc_k <= 16:
         parser.error("--prdc-k must lie in 1 .. 16")
+    if (args.authpct or args.nearest_train) and not args.train:
+        parser.error("--authpct and --nearest-train need the training set: --train PATH")
     return args
 
 
 def main(argv=None):
     args = parse_args(argv)
-    for p in (args.path1, args.path2):                                     # a file of another network: refused before the GPU is asked for
+    for p in (args.path1, args.path2, args.train):                         # a file of another network: refused before the GPU is asked for
         if p.endswith(".npz") and os.path.exists(p):
             check_feature_file(p, args.arch)
     if not torch.cuda.is_available():
@@ -189,7 +248,8 @@ def main(argv=None):
     torch.cuda.set_device(dev)
     wpath, tag = tweights.resolve(args.weights, args.synthetic_weights, arch_info(args.arch)[2], f"DINOv2 {args.arch}")
     res = calculate_fd_dinov2_given_paths([args.path1, args.path2], args.batch_size, wpath, args.seed, args.num_workers, args.png_feed,
-                                          args.arch, args.kd, args.prdc_k if args.prdc else None, args.save_features)
+                                          args.arch, args.kd, args.prdc_k if args.prdc else None, args.save_features, args.train or None,
+                                          args.authpct, args.nearest_train, args.vendi, args.fd_infinity, args.fd_infinity_seed)
     lines = result_lines(res, args.arch, tag)
     if tdist.is_main():
         if args.saved_file:
