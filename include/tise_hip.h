@@ -198,6 +198,36 @@ int tise_resize_tf1_f32(const uint8_t* src_dev, int n, int h, int w, float* dst_
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * (a3p) torch's float bilinear interpolation (F.interpolate(x, size, mode="bilinear", align_corners=False): half-pixel centres,
+ * no antialiasing) on ToTensor's byte / 255, + input affine, fused: the input route of pytorch-fid (csrc/resize_torch.hip).
+ * What the CPU build of torch computes, bit for bit (tests/_torch_resize_ref.py).  Per axis, all in float32:
+ * scale = (float)in / (float)out, s = max(fmaf(scale, (float)o + 0.5f, -0.5f), 0), i0 = min((int)s, in - 1),
+ * i1 = min(i0 + 1, in - 1), l1 = s - (float)i0, l0 = 1 - l1.  Per value, p(byte) = (float)byte / 255.0f:
+ * top = fmaf(wx0, p(a), wx1 * p(b)), bot = fmaf(wx0, p(c), wx1 * p(d)), v = fmaf(hy0, top, hy1 * bot), out = v * mul - sub
+ * (a separate multiply and subtract).
+ *
+ *   src_dev   n images, HWC uint8, contiguous (n, h, w, 3), any alignment
+ *   dst_dev   fp32 (n, oh, ow, 3), what tise_stem_conv3x3s2_split reads; any 4-byte alignment (16-byte: wider stores, same bits)
+ * A non-positive size, n < 0, a null pointer, a non-finite mul or sub: TISE_ERR_INVALID_ARG.  oh * ow >= 2^31:
+ * TISE_ERR_UNSUPPORTED.  n == 0: TISE_OK, no launch.  One launch for any n (grid-stride).
+ * ------------------------------------------------------------------------------------------ */
+int tise_resize_torch_f32(const uint8_t* src_dev, int n, int h, int w, float* dst_dev, int oh, int ow, float mul, float sub,
+                          void* stream);
+
+/* One image of a ragged batch: an (h, w, 3) uint8 image in device memory, contiguous, any alignment. */
+typedef struct tise_torch_image {
+    const uint8_t* src;
+    int32_t h, w;
+} tise_torch_image_t;
+
+/* The same for n images of DIFFERENT sizes into one fp32 batch (n, oh, ow, 3), ONE launch for any n: image by image exactly the
+ * bits tise_resize_torch_f32 writes.  table_dev: n entries in DEVICE memory, read by the kernel (the caller copies them there,
+ * on ``stream`` or before); an entry with a null pointer or a non-positive size is skipped and its output left unwritten.
+ * Refusals as above (the table's contents cannot be checked on the host: the caller checks the sizes). */
+int tise_resize_ragged_torch_f32(const tise_torch_image_t* table_dev, int64_t n, float* dst_dev, int oh, int ow, float mul,
+                                 float sub, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a7) Streaming activation statistics: n, s = sum_i x_i, S = sum_i x_i x_i^T in fp64 from
  * fp32 feature rows that never leave the device.
  * Replaces pred_arr[start:end] = pred.cpu()...  + np.mean(act, 0) + np.cov(act, rowvar=False)

@@ -58,6 +58,8 @@ SIGNATURES = {
                                         c_float, c_float, c_float, c_float, c_void_p, c_int64, c_void_p, POINTER(c_int64),
                                         c_void_p]),
     "tise_resize_tf1_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
+    "tise_resize_torch_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
+    "tise_resize_ragged_torch_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
     "tise_split_tap_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "tise_cosine_top1": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                   c_void_p, c_void_p]),

@@ -387,6 +387,60 @@ def resize_tf1_f32(src_u8, out_hw=(299, 299), sub=128, mul=2.0 ** -7, channels_l
     return out if channels_last else out.contiguous()
 
 
+def resize_torch_f32(src_u8, out_hw=(299, 299), mul=2.0, sub=1.0, channels_last=True):
+    """(N,H,W,3) uint8 CUDA tensor -> (N,3,oh,ow) fp32 network input of pytorch-fid's route (tise_resize_torch_f32): ToTensor's
+    byte / 255, torch's float32 bilinear interpolation (align_corners=False, no antialiasing; the bits of torch's CPU kernel,
+    tests/_torch_resize_ref.py is the definition), then ``v * mul - sub``.  The kernel writes NHWC: with ``channels_last`` the
+    result is its NCHW view (torch.channels_last memory format, what the trunk's stem reads); otherwise a contiguous NCHW copy."""
+    _require_cuda(src_u8)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3:
+        raise ValueError("src_u8 must be (N,H,W,3) uint8")
+    oh, ow = (int(v) for v in out_hw)
+    src_u8 = src_u8.contiguous()
+    n, h, w, _ = src_u8.shape
+    if h <= 0 or w <= 0 or oh <= 0 or ow <= 0:
+        raise ValueError(f"resize_torch_f32: sizes must be positive (got {h} x {w} -> {oh} x {ow})")
+    store = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=src_u8.device)
+    if n:
+        _lib.call("tise_resize_torch_f32", _ptr(src_u8), n, h, w, _ptr(store), oh, ow, float(mul), float(sub), _stream())
+    out = store.permute(0, 3, 1, 2)
+    return out if channels_last else out.contiguous()
+
+
+_TORCH_IMAGE = np.dtype([("src", "<u8"), ("h", "<i4"), ("w", "<i4")])       # tise_torch_image_t (include/tise_hip.h)
+
+
+def resize_ragged_torch_f32(crops, out_hw=(299, 299), mul=2.0, sub=1.0, channels_last=True):
+    """List of (H_i,W_i,3) uint8 CUDA tensors of any sizes -> the (B,3,oh,ow) fp32 batch ``resize_torch_f32`` gives image by
+    image, bit for bit, in ONE launch (tise_resize_ragged_torch_f32).  The (pointer, h, w) table is built in page-locked memory
+    and copied on the current stream, in front of the launch; a wrong dtype or shape raises before anything is enqueued."""
+    if len(crops) == 0:
+        raise ValueError("empty batch")
+    oh, ow = (int(v) for v in out_hw)
+    if oh <= 0 or ow <= 0:
+        raise ValueError(f"resize_ragged_torch_f32: sizes must be positive (got -> {oh} x {ow})")
+    dev = crops[0].device
+    srcs = []
+    for i, c in enumerate(crops):
+        _require_cuda(c)
+        if c.dim() == 4 and c.shape[0] == 1:
+            c = c[0]
+        if c.dtype != torch.uint8 or c.dim() != 3 or c.shape[2] != 3 or c.shape[0] <= 0 or c.shape[1] <= 0:
+            raise ValueError(f"crop {i} must be (H,W,3) uint8")
+        srcs.append(c.contiguous())
+    n = len(srcs)
+    table = np.empty(n, dtype=_TORCH_IMAGE)
+    table["src"] = np.fromiter((c.data_ptr() for c in srcs), dtype=np.uint64, count=n)
+    table["h"] = np.fromiter((c.shape[0] for c in srcs), dtype=np.int32, count=n)
+    table["w"] = np.fromiter((c.shape[1] for c in srcs), dtype=np.int32, count=n)
+    # (torch's caching host allocator keeps the page-locked block until the copy that reads it has run)
+    table_dev = torch.from_numpy(table.view(np.uint8)).pin_memory().to(dev, non_blocking=True)
+    store = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=dev)
+    _lib.call("tise_resize_ragged_torch_f32", _ptr(table_dev), n, _ptr(store), oh, ow, float(mul), float(sub), _stream())
+    out = store.permute(0, 3, 1, 2)
+    return out if channels_last else out.contiguous()
+
+
 def split_tap_rows(t, c0, nc, ld):
     """Channels [c0, c0 + nc) of a split tensor (N,H,W,2C) (conv_split.py) as fp32 rows (N, ld) (tise_split_tap_rows): row i
     holds ``conv_split.merge(t)[i, :, :, c0:c0+nc]`` flattened in h, w, c order -- the same bits -- and zeros from column

@@ -63,7 +63,9 @@ def run_with_exact_fallback(fn, what="the evaluation"):
 
 
 RESIZES = ("reference", "clean")          # the resizes behind fid_score's modes (--mode tise / clean)
-SUITE_RESIZES = ("tf1",)                   # ... and the one only the ADM suite (adm_eval.py) uses
+SUITE_RESIZES = ("tf1",)                   # ... the ADM suite's (adm_eval.py; fid_score --mode torch-fidelity takes it too)
+TORCH_RESIZES = ("torch",)                 # ... and pytorch-fid's (fid_score --mode pytorch-fid)
+FLOAT_RESIZES = ("clean", "tf1", "torch")  # the routes that hand the fp32 stem a float network input
 
 
 class RealismEngine:
@@ -76,18 +78,21 @@ class RealismEngine:
         every channel resized as a float32 image with Pillow's bicubic filter, not quantised, clipped to [0, 255] and mapped
         (x - 128) / 128 (csrc/resize_f32.hip), for the Inception-2015 network only (whose input map that is); "tf1" -- the
         ADM evaluator's: TensorFlow 1's legacy float32 ResizeBilinear, then (x - 128) * 2^-7 (csrc/resize_tf1.hip), for the
-        same network only.
+        same network only; "torch" -- pytorch-fid's: byte / 255, torch's float32 bilinear interpolation (align_corners=False, no
+        antialiasing), then 2 x - 1 (csrc/resize_torch.hip), for the same network only.
         ``spatial``: the split-precision trunk also hands out the first 7 channels of Mixed_6d's 1x1 branch (17 x 17 x 7, the
         ADM evaluator's sFID features) as rows of 2048 fp32 (25 zero columns): begin() creates ``stats_spatial``, the steps
         feed it, ``statistics_spatial()`` finalises it.  Needs dims 2048 and the split trunk; runs eagerly (no hipGraph)."""
         require_gpu()
-        if resize not in RESIZES + SUITE_RESIZES:
-            raise ValueError(f"unknown resize {resize!r} (choose from {', '.join(RESIZES + SUITE_RESIZES)})")
+        if resize not in RESIZES + SUITE_RESIZES + TORCH_RESIZES:
+            raise ValueError(f"unknown resize {resize!r} (choose from {', '.join(RESIZES + SUITE_RESIZES + TORCH_RESIZES)})")
         net = getattr(model, "network", "torchvision") if model is not None else network
         if resize == "clean" and net != "inception-2015":
             raise ValueError(f"resize='clean' is clean-fid's route and runs on network 'inception-2015' only (got {net!r})")
         if resize == "tf1" and net != "inception-2015":
             raise ValueError(f"resize='tf1' is the ADM evaluator's route and runs on network 'inception-2015' only (got {net!r})")
+        if resize == "torch" and net != "inception-2015":
+            raise ValueError(f"resize='torch' is pytorch-fid's route and runs on network 'inception-2015' only (got {net!r})")
         self.spatial = bool(spatial)
         self.resize = resize
         if device_index is None:
@@ -163,11 +168,18 @@ class RealismEngine:
         from .inception import INCEPTION_2015_INPUT_SUB
         return device.resize_tf1_f32(u8, (299, 299), INCEPTION_2015_INPUT_SUB, 2.0 ** -7, channels_last=self.channels_last)
 
+    def _torch_input(self, u8, ragged=False):
+        """pytorch-fid's network input: (N,3,299,299) fp32, channels_last as the engine's trunk reads it."""
+        fn = device.resize_ragged_torch_f32 if ragged else device.resize_torch_f32
+        return fn(u8, (299, 299), 2.0, 1.0, channels_last=self.channels_last)
+
     def _features_from_u8_eager(self, batch_u8):
         if self.resize == "clean":
             return self._trunk(self._clean_input(batch_u8), prenormalized=True)
         if self.resize == "tf1":
             return self._trunk(self._tf1_input(batch_u8), prenormalized=True)
+        if self.resize == "torch":
+            return self._trunk(self._torch_input(batch_u8), prenormalized=True)
         if self._u8_stem:
             # all-HIP trunk: the resize kernel writes the Pillow-exact uint8 image only and the stem convolution
             # applies the input table (134 MB instead of 536 MB of network input per 500 images; same features)
@@ -237,6 +249,8 @@ class RealismEngine:
         crops = [(c[0] if c.dim() == 4 else c).to(self.device, non_blocking=True) for c in crops]
         if self.resize == "clean":
             return self._trunk(self._clean_input(crops, ragged=True), prenormalized=True)
+        if self.resize == "torch":
+            return self._trunk(self._torch_input(crops, ragged=True), prenormalized=True)
         if self.resize == "tf1":
             raise ValueError("resize='tf1' takes batches of equal-sized images (features_from_u8), not ragged crop lists")
         u8 = device.resize_ragged_u8(crops, (299, 299))
@@ -291,7 +305,7 @@ class RealismEngine:
         images = int(images)
         if images <= getattr(self, "_reserved_images", 0) or not isinstance(self.fused, SplitTrunk) or os.environ.get("TISE_RESERVE", "1") == "0":
             return 0
-        nbytes = images * (self.ACT_BYTES_PER_IMAGE + (self.CLEAN_INPUT_BYTES_PER_IMAGE if self.resize in ("clean", "tf1") else 0))
+        nbytes = images * (self.ACT_BYTES_PER_IMAGE + (self.CLEAN_INPUT_BYTES_PER_IMAGE if self.resize in FLOAT_RESIZES else 0))
         free, _total = torch.cuda.mem_get_info(self.device)
         have = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)      # cached, free blocks
         if nbytes <= have or nbytes > 0.6 * free:

@@ -24,7 +24,9 @@ Deviations from the reference, all deliberate (SURVEY.md notes N3-N5):
     ``--num-classes`` (80 for the O-FID fine-tune, O-FID/inception.py:58-64), ``--per-class`` (extension, BASELINE
     configs[4]: one FID per object class, crops grouped by the ``{class}`` token of ``{stem}_{class}_{k}.png``,
     object_fidelity/crop_object.py:45), ``--mode clean`` (extension: clean-fid's FID -- Inception-2015, every channel resized
-    as a float32 image with Pillow's bicubic filter and not quantised, every image used; MODES below).
+    as a float32 image with Pillow's bicubic filter and not quantised, every image used; MODES below), ``--mode pytorch-fid``
+    and ``--mode torch-fidelity`` (extensions: those packages' input routes on Inception-2015, every image used),
+    ``--untagged-stats MODE`` (whose statistics a {mu, sigma} file without a mode tag holds).
 """
 import contextlib
 import os
@@ -73,19 +75,44 @@ FID_NETWORKS = tuple(n for n in NETWORKS if n != "slim")
 # channel resized as a float32 image with Pillow's antialiased bicubic filter and NOT quantised, clipped to [0, 255], mapped
 # (x - 128) / 128 (csrc/resize_f32.hip), every image used.  The file set is this module's os.walk either way (clean-fid globs and
 # sorts: the same FID, other KID subsets).
-MODES = ("tise", "clean")
+# pytorch-fid: pytorch-fid's (Seitzer 2020) -- network inception-2015, byte / 255, torch's float32 bilinear interpolation
+# (align_corners=False, no antialiasing), 2 x - 1 (csrc/resize_torch.hip), every image used.  torch-fidelity: torch-fidelity's
+# (Obukhov et al. 2020; torchmetrics' FrechetInceptionDistance runs its extractor) -- network inception-2015, TensorFlow 1's legacy
+# bilinear resize of the bytes as floats, (x - 128) * 2^-7 (csrc/resize_tf1.hip, the ADM suite's kernel), every image used; one
+# image size per directory (that kernel has no ragged launch).
+MODES = ("tise", "clean", "pytorch-fid", "torch-fidelity")
 CLEAN_TAG = " [mode clean]"
+MODE_RESIZE = {"tise": "reference", "clean": "clean", "pytorch-fid": "torch", "torch-fidelity": "tf1"}       # engine.RealismEngine(resize=...)
+MODE_OWNER = {"clean": "clean-fid's", "pytorch-fid": "pytorch-fid's", "torch-fidelity": "torch-fidelity's"}
+PACKAGE_MODES = ("pytorch-fid", "torch-fidelity")       # whose own packages write {mu, sigma} files without a tag: --untagged-stats
+
+
+def mode_tag(mode):
+    """What result lines carry behind the value: nothing under the default mode."""
+    return "" if mode == "tise" else f" [mode {mode}]"
 
 
 def resolve_mode(mode, network):
-    """-> the network ``mode`` runs on; ``network`` None: the mode's own (tise: torchvision, clean: inception-2015)."""
+    """-> the network ``mode`` runs on; ``network`` None: the mode's own (tise: torchvision, every other mode: inception-2015)."""
     if mode not in MODES:
         raise ValueError(f"unknown mode {mode!r} (choose from {', '.join(MODES)})")
-    if mode == "clean":
+    if mode != "tise":
         if network not in (None, "inception-2015"):
-            raise ValueError(f"--mode clean is clean-fid's FID and runs on --network inception-2015 only (got --network {network})")
+            raise ValueError(f"--mode {mode} is {MODE_OWNER[mode]} FID and runs on --network inception-2015 only (got --network {network})")
         return "inception-2015"
     return "torchvision" if network is None else network
+
+
+_UNTAGGED_STATS = None              # --untagged-stats MODE of this process (main sets it; set_untagged_stats for Python callers)
+
+
+def set_untagged_stats(mode):
+    """A statistics .npz WITHOUT a ``mode`` array is taken as ``mode``'s from now on (None: as the default mode's, the rule
+    of every earlier version).  A tagged file is never overridden."""
+    global _UNTAGGED_STATS
+    if mode is not None and mode not in MODES:
+        raise ValueError(f"unknown mode {mode!r} (choose from {', '.join(MODES)})")
+    _UNTAGGED_STATS = mode
 
 
 def _fid_network(value):
@@ -125,7 +152,15 @@ def _build_parser():
     parser.add_argument("--mode", type=str, default="tise", choices=list(MODES),
                         help="tise: the reference's FID (Pillow's 8-bit bilinear resize, the last N mod batch-size files dropped); "
                              "clean: clean-fid's FID -- --network inception-2015, every channel resized as a float32 image with "
-                             "Pillow's bicubic filter and not quantised, every image used; --save-stats tags the .npz with mode=clean")
+                             "Pillow's bicubic filter and not quantised, every image used; "
+                             "pytorch-fid: pytorch-fid's FID -- --network inception-2015, byte / 255, torch's float32 bilinear "
+                             "interpolation (no antialiasing), 2 x - 1, every image used; "
+                             "torch-fidelity: torch-fidelity's (and torchmetrics') FID -- --network inception-2015, TensorFlow 1's "
+                             "legacy bilinear resize, (x - 128) / 128, every image used, one image size per directory.  --save-stats "
+                             "tags the .npz with the mode; --kid keeps this project's subsets under every mode")
+    parser.add_argument("--untagged-stats", type=str, default=None, choices=list(MODES), metavar="MODE",
+                        help="take a statistics .npz WITHOUT a mode tag (the {mu, sigma} files pytorch-fid itself writes, for "
+                             "instance) as MODE's; unset: such a file is the default mode's.  A tagged file is never overridden")
     parser.add_argument("--synthetic-weights", action="store_true",
                         help="seeded stand-in parameters (plumbing / throughput only; results are tagged)")
     parser.add_argument("--seed", type=int, default=0, help="seed of the --synthetic-weights parameters")
@@ -182,7 +217,7 @@ def _engine_for(model, dims):
     eng = getattr(model, "_tise_engine", None)
     if eng is None:
         eng = RealismEngine(dims=dims, model=model, fold_bn=isinstance(model, InceptionV3),
-                            resize="clean" if getattr(model, "fid_mode", "tise") == "clean" else "reference")
+                            resize=MODE_RESIZE[getattr(model, "fid_mode", "tise")])
         try:
             model._tise_engine = eng
         except Exception:
@@ -193,8 +228,12 @@ def _engine_for(model, dims):
 def _forward_batch(engine, model, batch):
     """One batch -> (B, dims) fp32 features on the device, for either input convention."""
     if isinstance(batch, (list, tuple)):                 # ragged uint8 crops: resize each into one batch, ONE trunk pass
+        if engine.resize == "tf1":                       # --mode torch-fidelity: a feed's list of equal-sized images is a dense batch
+            return engine.features_from_u8(_one_size(engine, batch).to(engine.device, non_blocking=True))[0]
         return engine.features_from_u8_list(batch)[0]
     if batch.dtype == torch.uint8:                       # (B,H,W,3) decoded images: fused device resize
+        if engine.resize == "tf1":
+            _one_size(engine, batch)
         return engine.features_from_u8(batch.to(engine.device, non_blocking=True))[0]
     if isinstance(model, InceptionV3):
         return engine.features_from_float(batch)[0]
@@ -204,6 +243,23 @@ def _forward_batch(engine, model, batch):
         if pred.shape[2] != 1 or pred.shape[3] != 1:     # fid_score.py:110-111
             pred = torch.nn.functional.adaptive_avg_pool2d(pred, output_size=(1, 1))
         return pred.reshape(pred.shape[0], -1).float().contiguous()
+
+
+def _one_size(engine, images):
+    """--mode torch-fidelity: a loader's batch -- (B,H,W,3), or a list of (H,W,3) images -- as one (B,H,W,3) batch of THE image
+    size of the directory in work (``engine._one_size``, reset per directory by _compute_statistics_of_path); an image of
+    another size is refused with the reason."""
+    items = [images] if isinstance(images, torch.Tensor) else [(c[0] if c.dim() == 4 else c) for c in images]
+    for c in items:
+        hw = (int(c.shape[-3]), int(c.shape[-2]))
+        seen = getattr(engine, "_one_size", None)
+        if seen is None:
+            engine._one_size = seen = hw
+        if hw != seen:
+            raise RuntimeError(f"--mode torch-fidelity: the images of this directory differ in size ({seen[0]} x {seen[1]} and "
+                               f"{hw[0]} x {hw[1]}), and the TF1 resize of this mode has no ragged launch: one image size per "
+                               "directory (resize or crop the images first, as torch-fidelity's own loader requires)")
+    return images if isinstance(images, torch.Tensor) else torch.stack(items)
 
 
 def _first(images, n):
@@ -393,22 +449,27 @@ def _compute_statistics_of_path(path, model, batch_size, dims, cuda, num_workers
         f = np.load(path, allow_pickle=True)              # :201-203
         m, s = f["mu"][:], f["sigma"][:]
         tag = str(f["network"]) if "network" in f.files else None
-        mode_tag = str(f["mode"]) if "mode" in f.files else "tise"
+        untagged = "mode" not in f.files
+        file_mode = str(f["mode"]) if not untagged else (_UNTAGGED_STATS or "tise")
         f.close()
+        if untagged and _UNTAGGED_STATS is not None and tdist.is_main():
+            print(f"[tise] {path}: no mode tag in this statistics file; taken as statistics of mode {_UNTAGGED_STATS} (--untagged-stats)",
+                  file=sys.stderr, flush=True)
         check_stats_network(path, tag, getattr(model, "network", "torchvision"))
-        check_stats_mode(path, mode_tag, getattr(model, "fid_mode", "tise"))
+        check_stats_mode(path, file_mode, getattr(model, "fid_mode", "tise"), untagged)
         if keep_features:
             return m, s, kid_features_of_npz(path)
         return m, s
     files = img_data.get_filenames(path)                  # os.walk order (img_data.py:27-35)
     rank, world, _ = tdist.env_world()
     engine = _engine_for(model, dims)
+    engine._one_size = None                               # --mode torch-fidelity: the image size of THIS directory (_one_size)
 
-    if getattr(model, "fid_mode", "tise") == "clean":
+    if getattr(model, "fid_mode", "tise") != "tise":
         # every image is used: contiguous index ranges of the walk per rank (as cmmd.py), a short last loader batch; the PNG
         # ring forms whole batches of ITS batch size, so it runs on batches of one image (as the IS* feed, inception_score.py)
         if u8_cache:
-            raise RuntimeError("--u8-cache holds whole loader batches only (the reference's drop-last rule); --mode clean uses every image")
+            raise RuntimeError(f"--u8-cache holds whole loader batches only (the reference's drop-last rule); --mode {model.fid_mode} uses every image")
         lo, hi = tdist.shard_range(len(files), rank, world)
         shard = files[lo:hi]
 
@@ -479,15 +540,19 @@ def check_stats_network(path, tag, network):
 
 
 def stats_mode_tag(mode):
-    """``mode`` for --mode clean only: the default mode's files stay exactly what they were."""
+    """``mode`` for every mode but the default one, whose files stay exactly what they were."""
     return {} if mode == "tise" else {"mode": np.asarray(mode)}
 
 
-def check_stats_mode(path, tag, mode):
+def check_stats_mode(path, tag, mode, untagged=False):
     """Statistics of one mode (another resize, another set of images) do not compare with features of the other.  ``tag``: the
-    file's ``mode`` array, "tise" for a file without one."""
+    file's ``mode`` array; for a file without one (``untagged``) what --untagged-stats says, else "tise"."""
     if tag != mode:
-        raise RuntimeError(f"{path}: statistics of mode {tag!r}, this run uses --mode {mode}")
+        hint = ""
+        if untagged and mode in PACKAGE_MODES:
+            hint = (f" (the file carries no mode tag and reads as the default mode's; if {MODE_OWNER[mode]} own package wrote it, "
+                    f"pass --untagged-stats {mode})")
+        raise RuntimeError(f"{path}: statistics of mode {tag!r}, this run uses --mode {mode}{hint}")
 
 
 def save_stats_npz(path, mu, sigma, network="torchvision", features=None, mode="tise"):
@@ -534,8 +599,8 @@ def _own_model(dims, weights, num_classes, seed, network="torchvision", mode="ti
 def calculate_fid_given_paths(paths, batch_size, cuda, dims, weights=None, num_classes=None, seed=0,
                               save_stats="", num_workers=8, u8_cache=False, network=None, mode="tise"):
     """Calculates the FID of two paths (fid_score.py:223-238).  ``weights=None`` = seeded stand-in parameters (the
-    CLI only allows that behind --synthetic-weights).  ``mode``: MODES ("clean": clean-fid's FID; ``network`` None = the
-    mode's own network, resolve_mode)."""
+    CLI only allows that behind --synthetic-weights).  ``mode``: MODES ("clean": clean-fid's FID, "pytorch-fid": pytorch-fid's,
+    "torch-fidelity": torch-fidelity's; ``network`` None = the mode's own network, resolve_mode)."""
     return _fid_kid_given_paths(paths, batch_size, cuda, dims, weights, num_classes, seed, save_stats, num_workers, u8_cache,
                                 network, None, mode=mode)[0]
 
@@ -683,6 +748,7 @@ def _class_statistics(path, model, batch_size, dims, num_workers, owner=None, ke
     rank, world, _ = tdist.env_world()
     lo, hi = tdist.shard_range(len(files), rank, world)
     engine = _engine_for(model, dims)
+    engine._one_size = None                               # --mode torch-fidelity: the image size of THIS directory (_one_size)
     accs = {c: device.StatsAccumulator(dims, engine.device) for c in names}
     # The pool3 rows of the directory stay on the device (8 KB per crop); once the walk is complete they are sorted by class
     # and folded into the 80 accumulators by ONE grouped launch (device.stats_update_grouped): every class's S is
@@ -891,8 +957,9 @@ def main(argv=None):
         args.network = resolve_mode(args.mode, args.network if args.network_given else None)
     except ValueError as e:
         parser.error(str(e))
-    if args.mode == "clean" and args.u8_cache:
-        parser.error("--mode clean --u8-cache is not available: the cache holds whole loader batches only, --mode clean uses every image")
+    if args.mode != "tise" and args.u8_cache:
+        parser.error(f"--mode {args.mode} --u8-cache is not available: the cache holds whole loader batches only, --mode {args.mode} uses every image")
+    set_untagged_stats(args.untagged_stats)
     if args.num_classes is None:
         args.num_classes = NETWORK_CLASSES[args.network]
     _timing(f"imports done (this module's imports {_T_IMPORT1 - _T_IMPORT0:.2f} s)")
@@ -912,8 +979,7 @@ def main(argv=None):
         os.environ["TISE_CONV"] = "miopen" if args.conv == "exact" else "split"
     kind = tweights.inception_kind(args.network, args.label == "O-FID" and args.num_classes == 80)
     wpath, tag = tweights.resolve(args.weights, args.synthetic_weights, kind)
-    if args.mode == "clean":
-        tag = CLEAN_TAG + tag                                          # result lines name the mode
+    tag = mode_tag(args.mode) + tag                                    # result lines name the mode (nothing under the default one)
     if args.path1 is None:                                             # statistics-only
         if tdist.is_main():
             print([args.path2])
