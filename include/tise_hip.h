@@ -390,6 +390,72 @@ int tise_nn_argmin(const float* q_dev, int64_t rows_q, int64_t ld_q, const float
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PSNR, SSIM and MS-SSIM of image PAIRS (csrc/ssim.hip; tise_toolbox_amd/paired.py).  No counterpart in the reference.  Images
+ * are 8-bit RGB, HWC, L = 255; every quantity is formed per channel and the caller averages the three channels.
+ *   PSNR     SSE = sum (x - y)^2 over the h w 3 bytes (an exact integer; tise_pair_sse_u8), MSE = SSE / (3 h w),
+ *            PSNR = 10 log10(255^2 / MSE) -- the caller's fp64.
+ *   SSIM     Wang, Bovik, Sheikh & Simoncelli 2004: window g[i] ~ exp(-(i - 5)^2 / (2 1.5^2)), i = 0..10, normalised to sum 1,
+ *            applied as g g^T at the (h - 10)(w - 10) VALID positions (no padding): mx, my, E[xx], E[yy], E[xy];
+ *            sxx = E[xx] - mx mx, syy = E[yy] - my my, sxy = E[xy] - mx my (biased, weighted); C1 = (0.01 255)^2,
+ *            C2 = (0.03 255)^2; cs = (2 sxy + C2) / (sxx + syy + C2), l = (2 mx my + C1) / (mx mx + my my + C1), ssim = l cs.
+ *            tise_ssim_pairs gives, per pair and channel, the mean of the ssim map and the mean of the cs map.
+ *   MS-SSIM  Wang, Simoncelli & Bovik 2003: five scales, between scales the 2 x 2 mean with stride 2, a last odd row or column
+ *            DROPPED (tise_pool2x2_pairs); the caller forms prod_s max(m_s, 0)^w_s from the cs means of scales 1..4 and the
+ *            ssim mean of scale 5.  A level holds multiples of 4^-s that are <= 255: exact in fp32.
+ * All arithmetic after the byte or float load is fp64, in a fixed order: the five moments go through one function (with x == y
+ * E[xx], E[yy] and E[xy] are bit-equal, as are mx and my), l and cs are formed without contraction, so an IDENTICAL pair gives
+ * exactly 1.0 for both means.  Map means: fixed-order sums inside a workgroup, one partial per (pair, tile) in the workspace, a
+ * second fixed-order pass; no floating-point atomics.  A pair's result depends on its own size and values only -- not on max_h,
+ * max_w, the other pairs of the launch or the run.  The uint8 and the fp32 form of the same values give the same bits.
+ *
+ * RAGGED launches: every entry point takes a table of n records in DEVICE memory (the caller copies it there, on ``stream`` or
+ * before), one record per pair, and is one launch (tise_ssim_pairs: two) for any n.  max_h, max_w: the largest h and w of the
+ * table, which size the grid and the workspace.  The table's contents cannot be checked on the host: the caller checks them.  A
+ * record with a null pointer, a side below the entry point's minimum or above max_h / max_w is SKIPPED: nothing of it is read,
+ * tise_ssim_pairs writes NaN for it, tise_pair_sse_u8 writes 0, tise_pool2x2_pairs writes nothing.
+ * LIMITS: 1 <= h, w <= TISE_SSIM_MAX_SIDE, n <= TISE_SSIM_MAX_PAIRS pairs per launch, n * tiles(max_h) * tiles(max_w) <= 2^22
+ * with tiles(s) = ceil((s - 10) / TISE_SSIM_TILE); uint8 images at any address, fp32 levels 4-byte aligned, both contiguous.
+ * ------------------------------------------------------------------------------------------ */
+#define TISE_SSIM_TAPS 11
+#define TISE_SSIM_TILE 64            /* output rows and output pixels per row of one workgroup's tile */
+#define TISE_SSIM_MAX_SIDE 16384
+#define TISE_SSIM_MAX_PAIRS 65535
+
+/* One pair of a ragged launch: two (h, w, 3) images in device memory, contiguous, uint8 or fp32 as the call's is_f32 says (the
+ * output table of tise_pool2x2_pairs: the two fp32 destinations and THEIR size).  24 bytes, 8-byte aligned. */
+typedef struct tise_pair {
+    const void* x;
+    const void* y;
+    int32_t h, w;
+} tise_pair_t;
+
+/* out_dev[i] = sum over the h w 3 bytes of (x - y)^2 of pair i (uint64, 8-byte aligned; zeroed by the call, then exact integer
+ * atomics).  uint8 images; minimum side 1.
+ * TISE_ERR_INVALID_ARG: a NULL or misaligned table or output, n < 0, max_h or max_w < 1.  TISE_ERR_UNSUPPORTED: max_h or max_w
+ * above TISE_SSIM_MAX_SIDE, n above TISE_SSIM_MAX_PAIRS.  n == 0: TISE_OK, no HIP call. */
+int tise_pair_sse_u8(const tise_pair_t* table_dev, int64_t n, int max_h, int max_w, uint64_t* out_dev, void* stream);
+
+/* bytes = 48 * n * tiles(max_h) * tiles(max_w): six doubles ({ssim, cs} x {R, G, B}) per pair and tile of the largest pair.
+ * TISE_ERR_INVALID_ARG: NULL bytes, n < 0, max_h or max_w < 11.  TISE_ERR_UNSUPPORTED: the limits above. */
+int tise_ssim_workspace_bytes(int64_t n, int max_h, int max_w, size_t* bytes);
+
+/* out_dev: (n, 3, 2) doubles, [pair][channel] = {mean of the ssim map, mean of the cs map}.  is_f32 = 0: uint8 images (scale
+ * 1); 1: fp32 images (the pyramid levels).  Minimum side 11.  ws_dev: 8-byte aligned scratch of at least
+ * tise_ssim_workspace_bytes(n, max_h, max_w).
+ * TISE_ERR_INVALID_ARG: a NULL or misaligned (8 bytes) table, output or workspace, n < 0, max_h or max_w < 11, is_f32 outside
+ * {0, 1}, a workspace too small.  TISE_ERR_UNSUPPORTED: the limits above.  n == 0: TISE_OK, no HIP call. */
+int tise_ssim_pairs(const tise_pair_t* table_dev, int64_t n, int max_h, int max_w, int is_f32, double* out_dev, void* ws_dev,
+                    size_t ws_bytes, void* stream);
+
+/* Both images of every pair -> fp32 (h / 2, w / 2, 3), value (a + b + c + d) * 0.25 of each whole 2 x 2 block (exact).
+ * out_table_dev[i]: the two destinations of pair i and their size, which must be (h / 2, w / 2) of table_dev[i] (otherwise the
+ * pair is skipped); it can be the input table of the next level's calls.  Minimum side 2.
+ * TISE_ERR_INVALID_ARG: a NULL or misaligned table, n < 0, max_h or max_w < 2, is_f32 outside {0, 1}.  TISE_ERR_UNSUPPORTED: the
+ * limits above.  n == 0: TISE_OK, no HIP call. */
+int tise_pool2x2_pairs(const tise_pair_t* table_dev, const tise_pair_t* out_table_dev, int64_t n, int max_h, int max_w, int is_f32,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a6) Frechet distance.
  * Replaces calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps)
  *                                           image_realism/FID/fid_score.py:121-171

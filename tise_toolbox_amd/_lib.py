@@ -106,6 +106,10 @@ SIGNATURES = {
     "tise_nn_workspace_bytes": (c_int, [c_int64, c_int64, c_int, POINTER(c_size_t)]),
     "tise_nn_argmin": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
+    "tise_pair_sse_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "tise_ssim_workspace_bytes": (c_int, [c_int64, c_int, c_int, POINTER(c_size_t)]),
+    "tise_ssim_pairs": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tise_pool2x2_pairs": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "tise_frechet_create": (c_int, [c_int, POINTER(c_void_p)]),
     "tise_frechet_destroy": (c_int, [c_void_p]),
     "tise_frechet_distance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),

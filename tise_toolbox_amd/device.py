@@ -1055,3 +1055,154 @@ def paired_cosine(img_emb, txt_emb):
     _lib.call("tise_paired_cosine", _ptr(img_emb), _ptr(txt_emb), ctypes.c_int64(n), int(d),
               1 if img_emb.dtype == torch.float16 else 0, _ptr(out), _stream())
     return out
+
+
+_PAIR = np.dtype([("x", "<u8"), ("y", "<u8"), ("h", "<i4"), ("w", "<i4")])       # tise_pair_t (include/tise_hip.h)
+SSIM_TAPS, SSIM_TILE, SSIM_MAX_SIDE, SSIM_MAX_PAIRS = 11, 64, 16384, 65535       # TISE_SSIM_* of the header
+
+
+def _pair_images(xs, ys, what, min_side, dtypes):
+    """Two (N,H,W,3) tensors or two lists of (H,W,3) tensors -> (x side, y side, dtype): a side stays ONE contiguous (N,H,W,3)
+    tensor (no per-image work on the host) or becomes a list of contiguous images.  One dtype of ``dtypes`` for all, pair by
+    pair one size, every side within min_side .. SSIM_MAX_SIDE, at most SSIM_MAX_PAIRS pairs.  A wrong dtype, shape or size
+    raises before anything is enqueued."""
+    if isinstance(xs, torch.Tensor) != isinstance(ys, torch.Tensor):
+        raise ValueError(f"{what}: both sides a (N,H,W,3) tensor or both a list of (H,W,3) tensors")
+    stacked = isinstance(xs, torch.Tensor)
+    if stacked:
+        if xs.dim() != 4 or xs.shape != ys.shape or xs.shape[3] != 3:
+            raise ValueError(f"{what}: two (N,H,W,3) tensors of one shape (got {tuple(xs.shape)} and {tuple(ys.shape)})")
+        pairs = [(xs, ys)]
+    else:
+        if len(xs) != len(ys):
+            raise ValueError(f"{what}: {len(xs)} images on side one, {len(ys)} on side two")
+        pairs = list(zip(xs, ys))
+    if len(xs) == 0:
+        raise ValueError("empty batch")
+    if len(xs) > SSIM_MAX_PAIRS:
+        raise ValueError(f"{what}: at most {SSIM_MAX_PAIRS} pairs per launch (got {len(xs)})")
+    dtype = pairs[0][0].dtype
+    if dtype not in dtypes:
+        raise ValueError(f"{what}: images must be {' or '.join(str(d) for d in dtypes)} (got {dtype})")
+    outx, outy = [], []
+    for i, (a, b) in enumerate(pairs):
+        _require_cuda(a, b)
+        for t in (a, b):
+            if t.dtype != dtype or t.dim() != (4 if stacked else 3) or t.shape[-1] != 3:
+                raise ValueError(f"{what}: image {i} must be (H,W,3) {dtype} (got {tuple(t.shape)} {t.dtype})")
+        if a.shape != b.shape:
+            raise ValueError(f"{what}: pair {i} has two sizes ({a.shape[0]} x {a.shape[1]} and {b.shape[0]} x {b.shape[1]})")
+        h, w = a.shape[-3], a.shape[-2]
+        if min(h, w) < min_side:
+            raise ValueError(f"{what}: pair {i} is {h} x {w}; the smaller side must be at least {min_side}")
+        if max(h, w) > SSIM_MAX_SIDE:
+            raise ValueError(f"{what}: pair {i} is {h} x {w}; a side may be at most {SSIM_MAX_SIDE}")
+        outx.append(a.contiguous())
+        outy.append(b.contiguous())
+    return (outx[0], outy[0], dtype) if stacked else (outx, outy, dtype)
+
+
+def _pair_geometry(side):
+    """(pointers uint64, h int32, w int32) of the images of a side: a contiguous (N,H,W,3) tensor or a list of images."""
+    if isinstance(side, torch.Tensor):
+        n, h, w = side.shape[:3]
+        step = h * w * 3 * side.element_size()
+        return (np.uint64(side.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(step), np.full(n, h, dtype=np.int32),
+                np.full(n, w, dtype=np.int32))
+    n = len(side)
+    return (np.fromiter((t.data_ptr() for t in side), dtype=np.uint64, count=n),
+            np.fromiter((t.shape[0] for t in side), dtype=np.int32, count=n),
+            np.fromiter((t.shape[1] for t in side), dtype=np.int32, count=n))
+
+
+def _pair_table(xs, ys, dev):
+    """The tise_pair_t table of the pairs on ``dev`` (built in page-locked memory, copied on the current stream in front of the
+    launch that reads it) and the largest h and w."""
+    px, hs, ws = _pair_geometry(xs)
+    table = np.empty(len(px), dtype=_PAIR)
+    table["x"], table["y"], table["h"], table["w"] = px, _pair_geometry(ys)[0], hs, ws
+    # (torch's caching host allocator keeps the page-locked block until the copy that reads it has run)
+    return torch.from_numpy(table.view(np.uint8)).pin_memory().to(dev, non_blocking=True), int(hs.max()), int(ws.max())
+
+
+def _side_device(side):
+    return side.device if isinstance(side, torch.Tensor) else side[0].device
+
+
+def pair_sse_u8(xs, ys, out=None):
+    """Two (N,H,W,3) uint8 CUDA tensors, or two lists of (H_i,W_i,3) uint8 CUDA tensors (pair by pair one size) -> (N,) int64 on
+    the device: the sum over a pair's bytes of (x - y)^2, exact (tise_pair_sse_u8; one launch for the list).  ``out``: N int64 to
+    write into."""
+    xs, ys, _ = _pair_images(xs, ys, "pair_sse_u8", 1, (torch.uint8,))
+    n, dev = len(xs), _side_device(xs)
+    table, mh, mw = _pair_table(xs, ys, dev)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.shape != (n,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"pair_sse_u8: out must be {n} contiguous int64 on {dev}")
+    _lib.call("tise_pair_sse_u8", _ptr(table), ctypes.c_int64(n), mh, mw, _ptr(out), _stream())
+    return out
+
+
+def ssim_workspace_bytes(n, max_h, max_w):
+    nb = ctypes.c_size_t(0)
+    _lib.call("tise_ssim_workspace_bytes", ctypes.c_int64(n), int(max_h), int(max_w), ctypes.byref(nb))
+    return nb.value
+
+
+def ssim_pairs(xs, ys, out=None, workspace=None):
+    """Two (N,H,W,3) CUDA tensors or two lists of (H_i,W_i,3) CUDA tensors, all uint8 (scale 1) or all float32 (a pyramid level),
+    pair by pair one size, every side >= 11 -> (N,3,2) float64 on the device: per pair and channel the mean of the SSIM map and
+    the mean of its contrast-structure (cs) map over the valid positions of the 11 x 11 Gaussian window (tise_ssim_pairs: fp64 in
+    a fixed order, an identical pair gives exactly 1.0; one launch for the list).  ``out`` / ``workspace``: buffers to use
+    ((N,3,2) float64; uint8 of at least ssim_workspace_bytes(N, max h, max w))."""
+    xs, ys, dtype = _pair_images(xs, ys, "ssim_pairs", SSIM_TAPS, (torch.uint8, torch.float32))
+    n, dev = len(xs), _side_device(xs)
+    table, mh, mw = _pair_table(xs, ys, dev)
+    need = ssim_workspace_bytes(n, mh, mw)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or workspace.device != dev:
+        raise ValueError(f"ssim_pairs: workspace must be at least {need} contiguous uint8 on {dev}")
+    if out is None:
+        out = torch.empty((n, 3, 2), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.shape != (n, 3, 2) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"ssim_pairs: out must be ({n},3,2) contiguous float64 on {dev}")
+    _lib.call("tise_ssim_pairs", _ptr(table), ctypes.c_int64(n), mh, mw, 1 if dtype == torch.float32 else 0, _ptr(out),
+              _ptr(workspace), ctypes.c_size_t(workspace.numel()), _stream())
+    return out
+
+
+def pool2x2_sizes(xs):
+    """Floats of the pooled level of every image of a list (or of a (N,H,W,3) tensor): (h // 2) * (w // 2) * 3."""
+    return [(t.shape[0] // 2) * (t.shape[1] // 2) * 3 for t in xs]
+
+
+def pool2x2_pairs(xs, ys, out=None):
+    """Two (N,H,W,3) CUDA tensors or two lists of (H_i,W_i,3) CUDA tensors, uint8 or float32, every side >= 2 -> the next
+    pyramid level of both sides as float32: the mean of every whole 2 x 2 block, (h // 2, w // 2, 3), a last odd row or column
+    dropped; exact (tise_pool2x2_pairs, one launch for the list).  Tensors in, two (N,H//2,W//2,3) tensors out; lists in, two
+    lists out -- views of ONE float32 store, side one's levels first (``out``: that store, 2 * sum(pool2x2_sizes(xs)) floats)."""
+    xs, ys, dtype = _pair_images(xs, ys, "pool2x2_pairs", 2, (torch.uint8, torch.float32))
+    n, dev = len(xs), _side_device(xs)
+    _, hs, ws = _pair_geometry(xs)
+    sizes = (hs // 2).astype(np.int64) * (ws // 2) * 3
+    total = int(sizes.sum())
+    if out is None:
+        out = torch.empty(2 * total, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.shape != (2 * total,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"pool2x2_pairs: out must be {2 * total} contiguous float32 on {dev}")
+    if isinstance(xs, torch.Tensor):
+        shape = (n, int(hs[0]) // 2, int(ws[0]) // 2, 3)
+        ox, oy = out[:total].view(shape), out[total:].view(shape)
+    else:
+        ox, oy, at = [], [], 0
+        for h, w, sz in zip(hs.tolist(), ws.tolist(), sizes.tolist()):
+            ox.append(out[at:at + sz].view(h // 2, w // 2, 3))
+            oy.append(out[total + at:total + at + sz].view(h // 2, w // 2, 3))
+            at += sz
+    table, mh, mw = _pair_table(xs, ys, dev)
+    out_table, _, _ = _pair_table(ox, oy, dev)
+    _lib.call("tise_pool2x2_pairs", _ptr(table), _ptr(out_table), ctypes.c_int64(n), mh, mw, 1 if dtype == torch.float32 else 0,
+              _stream())
+    return ox, oy

@@ -40,6 +40,7 @@ FID = Site(("jpeg", "crop", "ring", "dataloader"), True, crop_on_request=True, r
 FID_ALL = FID._replace(drop_last=False)                           # fid_score --mode clean: the FID site, every image used
 CROPS = Site(("crop", "dataloader"), False)                       # fid_score --per-class, O-IS
 IS = Site(("jpeg", "ring", "dataloader"), False)
+PAIRED = Site(("jpeg", "ring", "dataloader"), False)              # paired.py, side one of the pairs: every image used, the kinds of IS
 CLIP = Site(("ring", "dataloader"), False, ragged_raises=False)   # RP_coco, PA
 
 Last = namedtuple("Last", "kind loader")
