@@ -251,7 +251,7 @@ def test_grid_limit_of_65535_images(cuda_device):
     assert torch.isnan(dst).all()                                # nothing ran
 
 
-RAGGED_CHUNK = 4096        # images per launch of tise_resize_ragged_f32 (csrc/resize_f32.hip)
+RAGGED_CHUNK = 4096        # images per launch of tise_resize_ragged_f32 (csrc/resize_plan.h)
 
 # Nine base images per output size, of RAGGED's kinds.  -> (5, 7): (2000, 64) and (64, 2000) are refused there (no tile fits
 # LDS), so the streamed kind is (800, 64) (641 staged rows: 123 KB streamed, 177 KB with float32 rows) and the many-tap kind

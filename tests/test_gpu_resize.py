@@ -4,7 +4,7 @@ The kernel is integer arithmetic, so every comparison is ``assert_array_equal``.
 ``Image.resize``; the oracle (oracle/resize_oracle.py) must agree with it in the same test; the expected float outputs are
 the 3x256 table applied to that uint8 image, exactly.  ``_check_all_products`` compares the four products of a call (float
 channels-last, float planar, the uint8 next to a float output, uint8 only) with one expected image, every destination inside
-a larger buffer of canary bytes that must be intact afterwards.  The kernel's host tables (precompute_coeffs in resize.hip)
+a larger buffer of canary bytes that must be intact afterwards.  The kernel's host tables (precompute_coeffs in resize_plan.h)
 have no export: they are covered here by outputs (tests/test_resize_host.py, point 3 of its docstring).
 
 Every GPU step is an ordinary launch with valid arguments or a host-side refusal that returns before any launch.

@@ -5,7 +5,7 @@
    of ``Image.resize``'s vertical-pass-first rule (h > 100 w and the height shrinks).
 2. The precondition of the kernel's 24-bit multiplies (``__mul24`` -> v_mad_i32_i24), swept through the oracle's
    coefficient tables: every coefficient fits the signed 24-bit operand and the accumulator fits ``int``.
-3. The kernel's own host tables (``precompute_coeffs`` in csrc/resize.hip) are host C++ that only a launch reaches and
+3. The kernel's own host tables (``precompute_coeffs`` in csrc/resize_plan.h, rounded in csrc/resize.hip) are host C++ that only a launch reaches and
    there is deliberately no export for them: they are covered by OUTPUTS in tests/test_gpu_resize.py -- every output byte
    depends on every coefficient of its two windows, and those tests compare every byte with Pillow at every table shape
    (up-scale, down-scale, identity, both filters, 1-pixel axes).  What this module adds is that the oracle those tests

@@ -9,6 +9,11 @@
                         one resize launch per crop (restated below: RealismEngine.features_from_u8_list as it was)
            dataloader   today's --crop-feed dataloader: the DataLoader, but one resize launch per device batch
   kernels  one pass of the native feed and nothing else, for a ``rocprofv3 --kernel-trace --stats`` run (--kernels-only)
+  launch   the two ragged resize launches alone (--launch-only; no files): tise_resize_ragged_u8 and tise_resize_ragged_f32 on
+           the first ``--crops`` (1 000) sizes of the directory below as resident device crops -> 299 x 299, table in page-locked
+           memory; per round the calls are enqueued back to back between two device events until they fill a tenth of a second;
+           median and spread (max - min) of the rounds, ms per launch, and the host's time to enqueue one call (the device
+           figure is the kernel's as long as that is the smaller one)
 
 The synthetic crop directory (seeded, documented here because the result depends on it): ``--files`` (6 000) PNGs named
 ``im_{i}_{class}_{i}.png`` over 80 class tokens; height and width drawn independently and uniformly from 16..256 with
@@ -17,6 +22,7 @@ feeds: compresses like a photograph, not like noise), rolled by a random offset;
 (RGBA); written by Pillow's PNG writer at its default compression (adaptive row filters).
 
     python tools/crop_feed_probe.py --root /tmp/crop_probe [--files 6000] [--pairs 3] [--host-only | --kernels-only]
+    python tools/crop_feed_probe.py --launch-only [--crops 1000] [--rounds 7]
 """
 import argparse
 import ctypes
@@ -43,6 +49,12 @@ def synthetic(n, h, w, seed):
     return out
 
 
+def crop_draws(n):
+    """(h, w, roll) of the directory's first n files."""
+    rng = np.random.default_rng(1)
+    return [(int(rng.integers(16, 257)), int(rng.integers(16, 257)), int(rng.integers(0, 256))) for _ in range(n)]
+
+
 def make_set(root, n):
     from PIL import Image
     d = os.path.join(root, "crops")
@@ -50,10 +62,8 @@ def make_set(root, n):
         return d
     os.makedirs(d, exist_ok=True)
     pool = synthetic(16, 256, 256, seed=5)
-    rng = np.random.default_rng(1)
-    for i in range(n):
-        h, w = int(rng.integers(16, 257)), int(rng.integers(16, 257))
-        img = np.roll(pool[i % 16], int(rng.integers(0, 256)), axis=1)[:h, :w]
+    for i, (h, w, roll) in enumerate(crop_draws(n)):
+        img = np.roll(pool[i % 16], roll, axis=1)[:h, :w]
         if i % 5 == 0:
             img = np.concatenate([img, np.full((h, w, 1), 255, np.uint8)], axis=2)
         Image.fromarray(img).save(os.path.join(d, f"im_{i:06d}_class{i % 80:02d}_{i}.png"))
@@ -139,15 +149,81 @@ def kernels_only(d, batch_size):
         torch.cuda.synchronize()
 
 
+def launch_probe(n, rounds, out_hw=(299, 299)):
+    import torch
+    from tise_toolbox_amd import _lib
+    dev = torch.device("cuda", 0)
+    oh, ow = out_hw
+    pool = synthetic(16, 256, 256, seed=5)
+    crops = [torch.from_numpy(np.ascontiguousarray(np.roll(pool[i % 16], roll, axis=1)[:h, :w])).to(dev)
+             for i, (h, w, roll) in enumerate(crop_draws(n))]
+    ptrs = np.fromiter((c.data_ptr() for c in crops), dtype=np.uint64, count=n)
+    hs = np.fromiter((c.shape[0] for c in crops), dtype=np.int32, count=n)
+    ws = np.fromiter((c.shape[1] for c in crops), dtype=np.int32, count=n)
+    orders = np.zeros(n, dtype=np.int32)
+    need = n * (64 + 4 * oh) + 16 * (n // 4096 + 1)
+    ws_dev = torch.empty(need, dtype=torch.uint8, device=dev)
+    pinned = torch.empty(need, dtype=torch.uint8).pin_memory()
+    u8 = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
+    f32 = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lib, bad = _lib.load(), ctypes.c_int64(-1)
+    args = (ctypes.c_void_p(ws_dev.data_ptr()), need, ctypes.c_void_p(pinned.data_ptr()), ctypes.byref(bad), stream)
+    calls = {
+        "ragged u8": lambda: lib.tise_resize_ragged_u8(ptrs.ctypes.data, hs.ctypes.data, ws.ctypes.data, n, ctypes.c_void_p(u8.data_ptr()),
+                                                        oh, ow, 0, *args),
+        "ragged f32": lambda: lib.tise_resize_ragged_f32(ptrs.ctypes.data, hs.ctypes.data, ws.ctypes.data, orders.ctypes.data, n,
+                                                          ctypes.c_void_p(f32.data_ptr()), oh, ow, 1, 1, 0.0, 255.0, 128.0, 128.0, *args),
+    }
+    print(f"{n} resident crops, sides 16..256 ({int(hs.astype(np.int64) @ ws) * 3 / 1e6:.1f} MB) -> {oh} x {ow}, {rounds} rounds, alternating", flush=True)
+    reps, dev_ms, host_ms = {}, {k: [] for k in calls}, {k: [] for k in calls}
+    for k, f in calls.items():                                                 # warm-up: plans, code objects; then size a round
+        for _ in range(3):
+            assert f() == _lib.TISE_OK, (k, bad.value)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(5):
+            f()
+        b.record()
+        b.synchronize()
+        reps[k] = max(5, int(100.0 / (a.elapsed_time(b) / 5)) + 1)
+    for _ in range(rounds):
+        for k, f in calls.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            t0 = time.perf_counter()
+            for _ in range(reps[k]):
+                f()
+            t1 = time.perf_counter()
+            b.record()
+            b.synchronize()
+            dev_ms[k].append(a.elapsed_time(b) / reps[k])
+            host_ms[k].append((t1 - t0) / reps[k] * 1e3)
+    for k in calls:
+        d = dev_ms[k]
+        print(f"  {k:10s} median {statistics.median(d):7.4f} ms per launch  spread {max(d) - min(d):6.4f}  min {min(d):7.4f}  max {max(d):7.4f}"
+              f"  ({reps[k]} launches per round; host enqueue {statistics.median(host_ms[k]):.4f} ms per call)", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--root", required=True)
+    ap.add_argument("--root")
+    ap.add_argument("--launch-only", action="store_true")
+    ap.add_argument("--crops", type=int, default=1000)
+    ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--files", type=int, default=6000)
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--batch-size", type=int, default=50)
     ap.add_argument("--host-only", action="store_true")
     ap.add_argument("--kernels-only", action="store_true")
     args = ap.parse_args()
+    if args.launch_only:
+        launch_probe(args.crops, args.rounds)
+        return
+    if not args.root:
+        ap.error("--root is required without --launch-only")
     d = make_set(args.root, args.files)
     if args.kernels_only:
         kernels_only(d, args.batch_size)
