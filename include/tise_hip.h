@@ -456,6 +456,51 @@ int tise_pool2x2_pairs(const tise_pair_t* table_dev, const tise_pair_t* out_tabl
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LPIPS (VGG-16) of image PAIRS (csrc/lpips.hip; tise_toolbox_amd/lpips_hip.py).  No counterpart in the reference; restated from
+ * Zhang, Isola, Efros, Shechtman & Wang 2018 (the `lpips` package v0.1, net = vgg):
+ *   input    8-bit RGB; x = b / 127.5 - 1, then (x - shift_c) / scale_c, shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448,
+ *            0.450): a 3 x 256 fp32 table the caller forms.
+ *   network  torchvision VGG-16 `features`: thirteen 3 x 3 / stride 1 / padding 1 convolutions with ReLU (tise_conv_split_f16),
+ *            MaxPool2d(2, 2) (floor) after blocks 1..4; taps relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 (64, 128, 256, 512, 512
+ *            channels).
+ *   head     per tap and pixel n(a) = sqrt(sum_c a_c^2) + 1e-10, d = sum_c w_c (a_c / n(a) - b_c / n(b))^2; the tap's value is the
+ *            mean of d over the pixels; LPIPS is the sum over the five taps.
+ * The three kernels here are what stands around the convolutions.  All take n PAIRS as 2n images: 0..n-1 side one, n..2n-1 side
+ * two.  LIMITS: 1 <= h, w <= TISE_LPIPS_MAX_SIDE, n <= TISE_LPIPS_MAX_PAIRS.
+ * ------------------------------------------------------------------------------------------ */
+#define TISE_LPIPS_MAX_SIDE 16384
+#define TISE_LPIPS_MAX_PAIRS 32767
+#define TISE_LPIPS_WG_PIXELS 256     /* pixels of one pair that one workgroup of the head sums */
+#define TISE_LPIPS_MAX_CHANNELS 512  /* of a tap: one 8-channel chunk per lane of a wave */
+
+/* table_dev: n records {x, y, h, w} of uint8 (h, w, 3) images at any address, ALL of the size (h, w) given here (a record of
+ * another size or with a NULL image is written as zeros).  lut_dev: 3 x 256 fp32 (4-byte aligned).  out_dev: split tensor
+ * (2n, h, w, 32), 16-byte aligned: channels 0..2 = lut[c][byte] in split form, channels 3..31 zero in both halves.
+ * TISE_ERR_INVALID_ARG: a NULL or misaligned pointer, n < 0, h or w < 1.  TISE_ERR_UNSUPPORTED: the limits above.  n == 0: TISE_OK,
+ * no HIP call. */
+int tise_lpips_input_split(const tise_pair_t* table_dev, int64_t n, int h, int w, const float* lut_dev, void* out_dev, void* stream);
+
+/* 2 x 2 / stride 2 max-pool (floor: a last odd row or column is dropped) of a channel slice of a split tensor into a channel slice
+ * of another; arguments and value arithmetic as tise_maxpool3s2_split_nhwc (the maximum of the exact fp32 values hi + lo 2^-11,
+ * split again).  C % 8 == 0, h, w >= 2, both tensors 16-byte aligned. */
+int tise_maxpool2s2_split_nhwc(const void* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, void* out_dev, int64_t out_ld,
+                               int out_off, void* stream);
+
+/* bytes = 8 * n * ceil(h w / TISE_LPIPS_WG_PIXELS): one double per pair and workgroup.
+ * TISE_ERR_INVALID_ARG: NULL bytes, n < 0, h or w < 1.  TISE_ERR_UNSUPPORTED: the limits above. */
+int tise_lpips_workspace_bytes(int64_t n, int h, int w, size_t* bytes);
+
+/* One tap.  feat_dev: split tensor (2n, h, w, C), 16 <= C <= TISE_LPIPS_MAX_CHANNELS, C % 16 == 0, 16-byte aligned; w_dev: C fp32;
+ * out_dev[i] += mean over the pixels of d (pair i; n doubles, 8-byte aligned: the caller zeroes them before the first tap);
+ * ws_dev: 8-byte aligned scratch of at least tise_lpips_workspace_bytes(n, h, w).  hi + lo 2^-11 is formed exactly, everything
+ * after it is fp64 in a fixed order, no floating-point atomics: two calls give the same bits, a pair's bits depend on its own
+ * features only, an identical pair adds exactly 0.0, a pixel that is zero on both sides contributes exactly 0.
+ * TISE_ERR_INVALID_ARG: a NULL or misaligned pointer, n < 0, h or w < 1, C < 16 or C % 16, a workspace too small.
+ * TISE_ERR_UNSUPPORTED: the limits above, C > TISE_LPIPS_MAX_CHANNELS.  n == 0: TISE_OK, no HIP call. */
+int tise_lpips_layer(const void* feat_dev, int64_t n, int h, int w, int C, const float* w_dev, double* out_dev, void* ws_dev,
+                     size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a6) Frechet distance.
  * Replaces calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps)
  *                                           image_realism/FID/fid_score.py:121-171

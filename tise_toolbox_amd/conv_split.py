@@ -9,8 +9,10 @@ block, one 128-byte line = one K-step of the convolution -- and a last block [hi
 zero padding to the kernel's tile multiples) and launches ``tise_conv_split_f16``.
 """
 import ctypes
+import functools
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -122,6 +124,25 @@ def rowwin_fits(ow, kw):
     j = (ow + 126) // ow + 1
     rows = 128 + j * (kw - 1) + 1
     return -(-rows // 32) in (5, 6)
+
+
+def rowwin_divides(ow, kw):
+    """Host mirror of launch_rowwin_any's check (csrc/conv_split.hip): the row-window kernel divides by OW and by OW + KW - 1
+    with 16-bit multiply-shift reciprocals, which must be exact for every u < 512 + OW; else the launcher answers
+    TISE_ERR_UNSUPPORTED before any launch.  KW = 3: true up to OW = 123 and at 224, false at 124..128, 256, 299, 384, 512."""
+    return _rowwin_divides(int(ow), int(kw))
+
+
+@functools.lru_cache(maxsize=None)
+def _rowwin_divides(ow, kw):
+    if ow < 1 or kw < 1:
+        return False
+    u = np.arange(512 + ow, dtype=np.uint64)
+    for d in (ow, ow + kw - 1):
+        inv = 65536 // d + 1
+        if not np.array_equal(((u * np.uint64(inv)) & np.uint64(0xffffffff)) >> np.uint64(16), u // np.uint64(d)):
+            return False
+    return True
 
 
 # conv_pipe.hip: configuration 34 = register-resident-weights sliding-window kernel (Cin = 32, 3x3, stride 1), up to 64 couts per launch
@@ -288,9 +309,11 @@ class SplitConv:
             oh, ow = self.pooled_out_hw(h, w)
             if pooled_input == "v":                             # the producer took the horizontal half (pool_h)
                 ow = w
-        if self.variant == "rowwin" and not rowwin_fits(ow, self.kw):
+        if self.variant == "rowwin" and not (rowwin_fits(ow, self.kw) and rowwin_divides(ow, self.kw)):
             # rows so short that the window of a 128-pixel tile needs more than the kernel's six pieces per wave (OW < 7
-            # at KW = 3): the default kernel serves the layer from its own packing, built on first use
+            # at KW = 3), or so long that the kernel's 16-bit reciprocal of the row length is not exact (OW >= 124 at KW = 3,
+            # with exceptions such as 224; the launcher refuses those): the default kernel serves the layer from its own
+            # packing, built on first use
             if self._fallback is None:
                 self._fallback = SplitConv(self._orig[0], self._orig[1], self.stride, self.padding, x.device, tn=self.tn, variant="fast", check=False)
             return self._fallback(x, segs)

@@ -1206,3 +1206,84 @@ def pool2x2_pairs(xs, ys, out=None):
     _lib.call("tise_pool2x2_pairs", _ptr(table), _ptr(out_table), ctypes.c_int64(n), mh, mw, 1 if dtype == torch.float32 else 0,
               _stream())
     return ox, oy
+
+
+LPIPS_MAX_SIDE, LPIPS_MAX_PAIRS, LPIPS_WG_PIXELS, LPIPS_MAX_CHANNELS = 16384, 32767, 256, 512       # TISE_LPIPS_* of the header
+
+
+def lpips_input_split(xs, ys, lut, out=None):
+    """Two (N,H,W,3) uint8 CUDA tensors or two lists of (H,W,3) uint8 CUDA tensors, ALL of one size, and the (3,256) float32
+    input table -> the split tensor (2N,H,W,64) fp16 conv1_1 reads (tise_lpips_input_split): images 0..N-1 side one, N..2N-1
+    side two; channels 0..2 = lut[c][byte] in split form, channels 3..31 zero in both halves."""
+    xs, ys, _ = _pair_images(xs, ys, "lpips_input_split", 1, (torch.uint8,))
+    n, dev = len(xs), _side_device(xs)
+    _, hs, ws = _pair_geometry(xs)
+    h, w = int(hs[0]), int(ws[0])
+    if bool((hs != h).any()) or bool((ws != w).any()):
+        raise ValueError("lpips_input_split: all pairs of a launch must have one size")
+    if n > LPIPS_MAX_PAIRS:
+        raise ValueError(f"lpips_input_split: at most {LPIPS_MAX_PAIRS} pairs per launch (got {n})")
+    _require_cuda(lut)
+    if lut.dtype != torch.float32 or lut.shape != (3, 256) or not lut.is_contiguous() or lut.device != dev:
+        raise ValueError(f"lpips_input_split: the table must be (3,256) contiguous float32 on {dev}")
+    if out is None:
+        out = torch.empty((2 * n, h, w, 64), dtype=torch.float16, device=dev)
+    elif out.dtype != torch.float16 or out.shape != (2 * n, h, w, 64) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"lpips_input_split: out must be ({2 * n},{h},{w},64) contiguous float16 on {dev}")
+    table, _, _ = _pair_table(xs, ys, dev)
+    _lib.call("tise_lpips_input_split", _ptr(table), ctypes.c_int64(n), h, w, _ptr(lut), _ptr(out), _stream())
+    return out
+
+
+def maxpool2s2_split(x, out=None, out_off=0, x_off=0, channels=None):
+    """max_pool2d(2, stride 2) (floor) of ``channels`` channels from ``x_off`` of a split tensor (N,H,W,2C) into the channels from
+    ``out_off`` of a split tensor (N,H//2,W//2,2C') (tise_maxpool2s2_split_nhwc; default: all channels into a fresh tensor)."""
+    _require_cuda(x)
+    if x.dtype != torch.float16 or x.dim() != 4 or x.shape[3] % 32 or not x.is_contiguous():
+        raise ValueError(f"maxpool2s2_split: a contiguous split tensor (N,H,W,2C) fp16, C % 16 == 0 (got {tuple(x.shape)} {x.dtype})")
+    n, h, w, c2 = x.shape
+    if h < 2 or w < 2:
+        raise ValueError(f"maxpool2s2_split: both sides must be at least 2 (got {h} x {w})")
+    c = c2 // 2 - x_off if channels is None else int(channels)
+    if out is None:
+        out = torch.empty((n, h // 2, w // 2, 2 * (out_off + c)), dtype=torch.float16, device=x.device)
+    elif (out.dtype != torch.float16 or out.dim() != 4 or out.shape[:3] != (n, h // 2, w // 2) or out.shape[3] % 32
+          or not out.is_contiguous() or out.device != x.device):
+        raise ValueError(f"maxpool2s2_split: out must be a contiguous split tensor ({n},{h // 2},{w // 2},2C') on {x.device}")
+    _lib.call("tise_maxpool2s2_split_nhwc", _ptr(x), c2 // 2, int(x_off), n, h, w, c, _ptr(out), out.shape[3] // 2, int(out_off),
+              _stream())
+    return out
+
+
+def lpips_workspace_bytes(n, h, w):
+    nb = ctypes.c_size_t(0)
+    _lib.call("tise_lpips_workspace_bytes", ctypes.c_int64(n), int(h), int(w), ctypes.byref(nb))
+    return nb.value
+
+
+def lpips_layer(feat, weight, out, workspace=None):
+    """One LPIPS tap: split features (2N,h,w,2C) fp16 (images 0..N-1 side one, N..2N-1 side two), ``weight`` C float32 ->
+    out[i] += mean over the pixels of sum_c w_c (a_c / n(a) - b_c / n(b))^2, n(v) = sqrt(sum_c v_c^2) + 1e-10 (tise_lpips_layer:
+    fp64 in a fixed order, no atomics; an identical pair adds exactly 0.0).  ``out``: N float64, ``workspace``: uint8 of at least
+    lpips_workspace_bytes(N, h, w)."""
+    _require_cuda(feat, weight, out)
+    if feat.dtype != torch.float16 or feat.dim() != 4 or feat.shape[0] % 2 or feat.shape[3] % 32 or not feat.is_contiguous():
+        raise ValueError(f"lpips_layer: a contiguous split tensor (2N,h,w,2C) fp16, C % 16 == 0 (got {tuple(feat.shape)} {feat.dtype})")
+    if feat.shape[3] // 2 > LPIPS_MAX_CHANNELS:
+        raise ValueError(f"lpips_layer: at most {LPIPS_MAX_CHANNELS} channels (got {feat.shape[3] // 2})")
+    n, h, w, c = feat.shape[0] // 2, feat.shape[1], feat.shape[2], feat.shape[3] // 2
+    dev = feat.device
+    if weight.dtype != torch.float32 or weight.shape != (c,) or not weight.is_contiguous() or weight.device != dev:
+        raise ValueError(f"lpips_layer: weight must be {c} contiguous float32 on {dev}")
+    if out.dtype != torch.float64 or out.shape != (n,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"lpips_layer: out must be {n} contiguous float64 on {dev}")
+    if n == 0:
+        return out
+    need = lpips_workspace_bytes(n, h, w)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or workspace.device != dev:
+        raise ValueError(f"lpips_layer: workspace must be at least {need} contiguous uint8 on {dev}")
+    _lib.call("tise_lpips_layer", _ptr(feat), ctypes.c_int64(n), h, w, c, _ptr(weight), _ptr(out), _ptr(workspace),
+              ctypes.c_size_t(workspace.numel()), _stream())
+    return out

@@ -241,15 +241,20 @@ def _images(loader, dev):
             yield from (batch.clone() if batch.is_cuda else batch.to(dev, non_blocking=True)).unbind(0)
 
 
-def _concat(parts, ms_ssim):
+def _concat(parts, ms_ssim, per_batch=None):
+    if per_batch is not None:
+        parts = parts or [per_batch([], [])]
+        return {k: np.concatenate([p[k] for p in parts], axis=0) for k in parts[0]}
     keys = ["psnr", "ssim", "sse", "h", "w"] + (["ms_ssim", "ms_scale_means"] if ms_ssim else [])
     if not parts:
         return psnr_ssim_from_images([], [], ms_ssim)
     return {k: np.concatenate([p[k] for p in parts], axis=0) for k in keys}
 
 
-def paired_from_files(files1, files2, ms_ssim=False, batch_size=50, options=None, device=None):
-    """Per-pair arrays (psnr_ssim_from_images' dict) of files1[i] against files2[i], this process's lists as they are."""
+def paired_from_files(files1, files2, ms_ssim=False, batch_size=50, options=None, device=None, per_batch=None):
+    """Per-pair arrays (psnr_ssim_from_images' dict) of files1[i] against files2[i], this process's lists as they are.
+    ``per_batch``: a callable (xs, ys) -> dict of per-pair numpy arrays that takes psnr_ssim_from_images' place on every batch
+    (two lists of (H,W,3) uint8 device tensors; called with two empty lists for an empty shard) -- lpips.py's use of this loop."""
     from .engine import require_gpu
     require_gpu()
     if len(files1) != len(files2):
@@ -258,7 +263,7 @@ def paired_from_files(files1, files2, ms_ssim=False, batch_size=50, options=None
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     batch_size = max(1, int(batch_size))
     if not files1:
-        return _concat([], ms_ssim)
+        return _concat([], ms_ssim, per_batch)
     workers = min(feeds.resolve_workers(options.num_workers, tdist.env_world()[1]), len(files2))
 
     def consume(loader):                                     # runs again from the start when the ring meets a ragged directory
@@ -271,7 +276,7 @@ def paired_from_files(files1, files2, ms_ssim=False, batch_size=50, options=None
                 if a.shape != b.shape:
                     raise RuntimeError(f"pair {base + k}: {files1[base + k]} is {a.shape[0]} x {a.shape[1]}, "
                                        f"{files2[base + k]} is {b.shape[0]} x {b.shape[1]}; both images of a pair must have one size")
-            parts.append(psnr_ssim_from_images(xs, ys, ms_ssim))
+            parts.append(psnr_ssim_from_images(xs, ys, ms_ssim) if per_batch is None else per_batch(xs, ys))
             base += len(xs)
             xs, ys = [], []
         for a, b in zip(_images(loader, dev), _images(other, dev)):
@@ -283,7 +288,7 @@ def paired_from_files(files1, files2, ms_ssim=False, batch_size=50, options=None
             flush()
         if base != len(files1):
             raise RuntimeError(f"the feeds delivered {base} pairs of {len(files1)}")
-        return _concat(parts, ms_ssim)
+        return _concat(parts, ms_ssim, per_batch)
     return feeds.run(feeds.PAIRED, list(files1), options, consume, dev, batch_size,
                      loader_args={"ring": {"batch_size": 1, "group": batch_size}})
 
