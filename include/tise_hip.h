@@ -501,6 +501,63 @@ int tise_lpips_layer(const void* feat_dev, int64_t n, int h, int w, int C, const
                      size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DISTS of image PAIRS (csrc/dists.hip; tise_toolbox_amd/dists_hip.py).  No counterpart in the reference; restated from Ding, Ma,
+ * Wang & Simoncelli 2020, "Image Quality Assessment: Unifying Structure and Texture Similarity" (the DISTS_pytorch package from
+ * memory; parity with its numbers is unpinned):
+ *   stage 0  the image itself, x = b / 255, 3 channels.
+ *   input    (x - mean_c) / std_c, mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225): a 3 x 256 fp32 table the caller
+ *            forms; tise_lpips_input_split turns the bytes into the split tensor conv1_1 reads.
+ *   network  torchvision VGG-16 `features`: thirteen 3 x 3 / stride 1 / padding 1 convolutions with ReLU (tise_conv_split_f16);
+ *            each of the four max-pools replaced by the L2 pool y = sqrt(conv(x^2, g, stride 2, padding 1, depthwise) + 1e-12),
+ *            g = [[1,2,1],[2,4,2],[1,2,1]] / 16, zero padding, output ceil(H/2) x ceil(W/2); taps relu1_2, relu2_2, relu3_3,
+ *            relu4_3, relu5_3.  Channels of the six stages: 3, 64, 128, 256, 512, 512.
+ *   head     per stage, pair and channel over the h w pixels: mx, my the means, vx, vy = mean (x - mx)^2, cxy = mean (x - mx)(y - my);
+ *            S1 = (2 mx my + c1) / (mx^2 + my^2 + c1), S2 = (2 cxy + c2) / (vx + vy + c2), c1 = c2 = 1e-6.
+ *   score    sum over stages and channels of alpha_c (1 - S1_c) + beta_c (1 - S2_c), alpha and beta divided by (sum alpha + sum beta).
+ * All calls take n PAIRS as 2n images: 0..n-1 side one, n..2n-1 side two.  LIMITS: 1 <= h, w <= TISE_DISTS_MAX_SIDE,
+ * n <= TISE_DISTS_MAX_PAIRS.
+ * ------------------------------------------------------------------------------------------ */
+#define TISE_DISTS_MAX_SIDE 16384
+#define TISE_DISTS_MAX_PAIRS 32767
+#define TISE_DISTS_WG_PIXELS 512     /* pixels of one pair that one workgroup of the head sums */
+#define TISE_DISTS_MAX_CHANNELS 512  /* of a stage: two channels per thread of the finishing workgroup */
+#define TISE_DISTS_SUM_PIXELS 4096   /* pixels of one pair per workgroup of tise_dists_image_sums_u8 */
+
+/* L2 (Hanning) pool, 3 x 3 / stride 2 / zero padding 1, of a channel slice of a split tensor into a channel slice of another;
+ * arguments as tise_maxpool2s2_split_nhwc / tise_maxpool3s2_split_nhwc.  out = sqrt(sum over the nine taps of g (hi + lo 2^-11)^2 +
+ * 1e-12): the value, its square and the weighted terms are exact in fp64, the nine terms are added in row-major tap order (a tap
+ * outside the image contributes 0), then the fp64 square root, one rounding to fp32 and the split hi = fp16(v), lo = fp16((v - hi)
+ * 2^11).  The output is (n, ceil(h/2), ceil(w/2), ..).  C % 8 == 0, h, w >= 1, both tensors 16-byte aligned.  The output never
+ * exceeds the largest input magnitude (+ 1e-6), so the range guard of the split format is not involved. */
+int tise_l2pool3s2_split_nhwc(const void* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, void* out_dev, int64_t out_ld,
+                              int out_off, void* stream);
+
+/* bytes = 8 * n * C * (7 * ceil(h w / TISE_DISTS_WG_PIXELS) + 2): per pair, workgroup and channel four doubles of the first pass
+ * (sum and count of pixels differing from the first, both sides) and three of the second (xx, yy, xy), per pair and channel the two means.
+ * TISE_ERR_INVALID_ARG: NULL bytes, n < 0, h or w < 1, C < 16 or C % 16.  TISE_ERR_UNSUPPORTED: the limits above,
+ * C > TISE_DISTS_MAX_CHANNELS. */
+int tise_dists_workspace_bytes(int64_t n, int h, int w, int C, size_t* bytes);
+
+/* One stage.  feat_dev: split tensor (2n, h, w, C), 16 <= C <= TISE_DISTS_MAX_CHANNELS, C % 16 == 0, 16-byte aligned; alpha_dev,
+ * beta_dev: C doubles each, already divided by (sum alpha + sum beta); out_dev[i] += sum_c alpha_c (1 - S1_c) + beta_c (1 - S2_c) of
+ * pair i (n doubles, 8-byte aligned: the caller zeroes them before the first stage); ws_dev: 8-byte aligned scratch of at least
+ * tise_dists_workspace_bytes(n, h, w, C).  hi + lo 2^-11 is formed exactly, everything after it is fp64 in a fixed order, two passes
+ * (the means, then the centered second moments), no floating-point atomics: two calls give the same bits, a pair's bits depend on
+ * its own features only, an identical pair adds exactly 0.0, a channel that is constant over the pixels has variance and
+ * covariance exactly 0, a channel that is zero on both sides adds exactly 0.
+ * TISE_ERR_INVALID_ARG: a NULL or misaligned pointer, n < 0, h or w < 1, C < 16 or C % 16, a workspace too small.
+ * TISE_ERR_UNSUPPORTED: the limits above, C > TISE_DISTS_MAX_CHANNELS.  n == 0: TISE_OK, no HIP call. */
+int tise_dists_layer(const void* feat_dev, int64_t n, int h, int w, int C, const double* alpha_dev, const double* beta_dev,
+                     double* out_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
+/* Stage 0 on the bytes.  table_dev as for tise_lpips_input_split (a record of another size or with a NULL image leaves zeros).
+ * out_dev: (n, 3, 5) int64, 8-byte aligned, zeroed by the call: per pair and colour the sums over the pixels of bx, by, bx^2, by^2,
+ * bx by (exact integer atomics, order-free).  The host forms S1 and S2 of the three colours from them.
+ * TISE_ERR_INVALID_ARG: a NULL or misaligned pointer, n < 0, h or w < 1.  TISE_ERR_UNSUPPORTED: the limits above.  n == 0: TISE_OK,
+ * no HIP call. */
+int tise_dists_image_sums_u8(const tise_pair_t* table_dev, int64_t n, int h, int w, int64_t* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a6) Frechet distance.
  * Replaces calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps)
  *                                           image_realism/FID/fid_score.py:121-171

@@ -115,6 +115,11 @@ SIGNATURES = {
                                             c_int64, c_int, c_void_p]),
     "tise_lpips_workspace_bytes": (c_int, [c_int64, c_int, c_int, POINTER(c_size_t)]),
     "tise_lpips_layer": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tise_l2pool3s2_split_nhwc": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                           c_int64, c_int, c_void_p]),
+    "tise_dists_workspace_bytes": (c_int, [c_int64, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "tise_dists_layer": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tise_dists_image_sums_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "tise_frechet_create": (c_int, [c_int, POINTER(c_void_p)]),
     "tise_frechet_destroy": (c_int, [c_void_p]),
     "tise_frechet_distance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),

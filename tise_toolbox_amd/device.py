@@ -1287,3 +1287,87 @@ def lpips_layer(feat, weight, out, workspace=None):
     _lib.call("tise_lpips_layer", _ptr(feat), ctypes.c_int64(n), h, w, c, _ptr(weight), _ptr(out), _ptr(workspace),
               ctypes.c_size_t(workspace.numel()), _stream())
     return out
+
+
+# TISE_DISTS_* of the header
+DISTS_MAX_SIDE, DISTS_MAX_PAIRS, DISTS_WG_PIXELS, DISTS_MAX_CHANNELS, DISTS_SUM_PIXELS = 16384, 32767, 512, 512, 4096
+
+
+def l2pool3s2_split(x, out=None, out_off=0, x_off=0, channels=None):
+    """DISTS's L2 (Hanning) pool, sqrt(conv(x^2, [[1,2,1],[2,4,2],[1,2,1]] / 16, stride 2, zero padding 1) + 1e-12), of ``channels``
+    channels from ``x_off`` of a split tensor (N,H,W,2C) into the channels from ``out_off`` of a split tensor
+    (N,ceil(H/2),ceil(W/2),2C') (tise_l2pool3s2_split_nhwc: fp64 in a fixed order, one rounding to fp32, split again; default: all
+    channels into a fresh tensor)."""
+    _require_cuda(x)
+    if x.dtype != torch.float16 or x.dim() != 4 or x.shape[3] % 32 or not x.is_contiguous():
+        raise ValueError(f"l2pool3s2_split: a contiguous split tensor (N,H,W,2C) fp16, C % 16 == 0 (got {tuple(x.shape)} {x.dtype})")
+    n, h, w, c2 = x.shape
+    if h < 1 or w < 1:
+        raise ValueError(f"l2pool3s2_split: both sides must be at least 1 (got {h} x {w})")
+    oh, ow = (h + 1) // 2, (w + 1) // 2
+    c = c2 // 2 - x_off if channels is None else int(channels)
+    if out is None:
+        out = torch.empty((n, oh, ow, 2 * (out_off + c)), dtype=torch.float16, device=x.device)
+    elif (out.dtype != torch.float16 or out.dim() != 4 or out.shape[:3] != (n, oh, ow) or out.shape[3] % 32
+          or not out.is_contiguous() or out.device != x.device):
+        raise ValueError(f"l2pool3s2_split: out must be a contiguous split tensor ({n},{oh},{ow},2C') on {x.device}")
+    _lib.call("tise_l2pool3s2_split_nhwc", _ptr(x), c2 // 2, int(x_off), n, h, w, c, _ptr(out), out.shape[3] // 2, int(out_off),
+              _stream())
+    return out
+
+
+def dists_workspace_bytes(n, h, w, c):
+    nb = ctypes.c_size_t(0)
+    _lib.call("tise_dists_workspace_bytes", ctypes.c_int64(n), int(h), int(w), int(c), ctypes.byref(nb))
+    return nb.value
+
+
+def dists_layer(feat, alpha, beta, out, workspace=None):
+    """One DISTS stage: split features (2N,h,w,2C) fp16 (images 0..N-1 side one, N..2N-1 side two), ``alpha`` and ``beta`` C float64
+    each (already divided by sum alpha + sum beta) -> out[i] += sum_c alpha_c (1 - S1_c) + beta_c (1 - S2_c), S1 and S2 from the
+    per-channel means, centered variances and covariance over the pixels (tise_dists_layer: fp64 in a fixed order, two passes, no
+    atomics; an identical pair adds exactly 0.0).  ``out``: N float64, ``workspace``: uint8 of at least
+    dists_workspace_bytes(N, h, w, C)."""
+    _require_cuda(feat, alpha, beta, out)
+    if feat.dtype != torch.float16 or feat.dim() != 4 or feat.shape[0] % 2 or feat.shape[3] % 32 or not feat.is_contiguous():
+        raise ValueError(f"dists_layer: a contiguous split tensor (2N,h,w,2C) fp16, C % 16 == 0 (got {tuple(feat.shape)} {feat.dtype})")
+    if feat.shape[3] // 2 > DISTS_MAX_CHANNELS:
+        raise ValueError(f"dists_layer: at most {DISTS_MAX_CHANNELS} channels (got {feat.shape[3] // 2})")
+    n, h, w, c = feat.shape[0] // 2, feat.shape[1], feat.shape[2], feat.shape[3] // 2
+    dev = feat.device
+    for name, t in (("alpha", alpha), ("beta", beta)):
+        if t.dtype != torch.float64 or t.shape != (c,) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"dists_layer: {name} must be {c} contiguous float64 on {dev}")
+    if out.dtype != torch.float64 or out.shape != (n,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"dists_layer: out must be {n} contiguous float64 on {dev}")
+    if n == 0:
+        return out
+    need = dists_workspace_bytes(n, h, w, c)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or workspace.device != dev:
+        raise ValueError(f"dists_layer: workspace must be at least {need} contiguous uint8 on {dev}")
+    _lib.call("tise_dists_layer", _ptr(feat), ctypes.c_int64(n), h, w, c, _ptr(alpha), _ptr(beta), _ptr(out), _ptr(workspace),
+              ctypes.c_size_t(workspace.numel()), _stream())
+    return out
+
+
+def dists_image_sums(xs, ys, out=None):
+    """Two (N,H,W,3) uint8 CUDA tensors or two lists of (H,W,3) uint8 CUDA tensors, ALL of one size -> (N,3,5) int64 on the
+    device: per pair and colour the sums over the pixels of bx, by, bx^2, by^2, bx by (tise_dists_image_sums_u8: exact) -- DISTS's
+    stage 0, from which the host forms S1 and S2."""
+    xs, ys, _ = _pair_images(xs, ys, "dists_image_sums", 1, (torch.uint8,))
+    n, dev = len(xs), _side_device(xs)
+    _, hs, ws = _pair_geometry(xs)
+    h, w = int(hs[0]), int(ws[0])
+    if bool((hs != h).any()) or bool((ws != w).any()):
+        raise ValueError("dists_image_sums: all pairs of a launch must have one size")
+    if n > DISTS_MAX_PAIRS:
+        raise ValueError(f"dists_image_sums: at most {DISTS_MAX_PAIRS} pairs per launch (got {n})")
+    if out is None:
+        out = torch.empty((n, 3, 5), dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.shape != (n, 3, 5) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"dists_image_sums: out must be ({n},3,5) contiguous int64 on {dev}")
+    table, _, _ = _pair_table(xs, ys, dev)
+    _lib.call("tise_dists_image_sums_u8", _ptr(table), ctypes.c_int64(n), h, w, _ptr(out), _stream())
+    return out

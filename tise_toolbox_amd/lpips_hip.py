@@ -24,6 +24,51 @@ def pairs_per_chunk(h, w, budget=ACTIVATION_BUDGET_BYTES):
     return int(max(1, min(device.LPIPS_MAX_PAIRS, budget // (512 * int(h) * int(w)))))
 
 
+def vgg_convs(convs, dev):
+    """The thirteen convolutions of a torch VGG-16 trunk as ``SplitConv``s left to "auto"; conv1_1 becomes a 32-channel layer with 29
+    zero weight columns.  The caller has checked the parameters (check=False)."""
+    out = []
+    for k, conv in enumerate(convs):
+        w, b = conv.weight.detach().float(), conv.bias.detach().float()
+        if k == 0:                                           # conv1_1 as a 32-channel layer: 29 zero weight columns
+            w = torch.cat([w, torch.zeros((w.shape[0], 29, 3, 3), dtype=w.dtype)], 1)
+        out.append(SplitConv(w, b, (1, 1), (1, 1), dev, name=f"features.{lpips_model.CONV_INDICES[k]}", check=False))
+    return out
+
+
+def chunks_by_size(xs, ys, check_size, what, budget):
+    """Two (N,H,W,3) uint8 device tensors or two lists of (H_i,W_i,3) uint8 device tensors -> (N, [(indices, x side, y side), ..]):
+    the pairs grouped by size and every group cut under the activation budget; a side of a chunk is a slice of the stacked
+    tensor where the chunk is contiguous in it, else a list.  Wrong dtypes, shapes and sizes raise before anything is enqueued."""
+    stacked = isinstance(xs, torch.Tensor) and isinstance(ys, torch.Tensor) and xs.dim() == 4 and ys.dim() == 4
+    if stacked:
+        if xs.shape != ys.shape:
+            raise ValueError(f"two (N,H,W,3) batches of one shape (got {tuple(xs.shape)} and {tuple(ys.shape)})")
+    else:
+        xs = [(c[0] if c.dim() == 4 and c.shape[0] == 1 else c) for c in xs]
+        ys = [(c[0] if c.dim() == 4 and c.shape[0] == 1 else c) for c in ys]
+        if len(xs) != len(ys):
+            raise ValueError(f"{len(xs)} images on side one, {len(ys)} on side two")
+    groups = {}
+    for i, (a, b) in enumerate(zip(xs, ys)):
+        if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() != 3 or b.dim() != 3 or a.shape[-1] != 3 or b.shape[-1] != 3:
+            raise ValueError(f"pair {i} must be two (H,W,3) uint8 images")
+        if a.shape != b.shape:
+            raise ValueError(f"pair {i} has two sizes ({a.shape[0]} x {a.shape[1]} and {b.shape[0]} x {b.shape[1]})")
+        check_size(a.shape[0], a.shape[1], f"{what}: pair {i}")
+        groups.setdefault((a.shape[0], a.shape[1]), []).append(i)
+    chunks = []
+    for (h, w), idx in groups.items():
+        step = pairs_per_chunk(h, w, budget)
+        for at in range(0, len(idx), step):
+            part = idx[at:at + step]
+            if stacked and part == list(range(part[0], part[0] + len(part))):
+                chunks.append((part, xs[part[0]:part[0] + len(part)], ys[part[0]:part[0] + len(part)]))
+            else:
+                chunks.append((part, [xs[i] for i in part], [ys[i] for i in part]))
+    return len(xs), chunks
+
+
 class HipLpips:
     def __init__(self, model, device_=None, budget=ACTIVATION_BUDGET_BYTES):
         from .engine import require_gpu
@@ -40,12 +85,7 @@ class HipLpips:
         if float(model.table.abs().max()) > 65504.0:
             raise ValueError("LPIPS VGG-16: the input table leaves the fp16 range of the split format")
         self.table = model.table.detach().float().contiguous().to(self.dev)
-        self.convs = []
-        for k, conv in enumerate(model.convs):
-            w, b = conv.weight.detach().float(), conv.bias.detach().float()
-            if k == 0:                                           # conv1_1 as a 32-channel layer: 29 zero weight columns
-                w = torch.cat([w, torch.zeros((w.shape[0], 29, 3, 3), dtype=w.dtype)], 1)
-            self.convs.append(SplitConv(w, b, (1, 1), (1, 1), self.dev, name=f"features.{lpips_model.CONV_INDICES[k]}", check=False))
+        self.convs = vgg_convs(model.convs, self.dev)
         self.lins = [lin.detach().float().contiguous().to(self.dev) for lin in model.lins]
 
     def _chunk(self, xs, ys):
@@ -69,34 +109,10 @@ class HipLpips:
     def __call__(self, xs, ys):
         """Two (N,H,W,3) uint8 device tensors or two lists of (H_i,W_i,3) uint8 device tensors (pair by pair one size, every side
         >= 16) -> (N,) float64 numpy array.  Raises FloatingPointError when an activation left the fp16 range of the split format."""
-        stacked = isinstance(xs, torch.Tensor) and isinstance(ys, torch.Tensor) and xs.dim() == 4 and ys.dim() == 4
-        if stacked:
-            if xs.shape != ys.shape:
-                raise ValueError(f"two (N,H,W,3) batches of one shape (got {tuple(xs.shape)} and {tuple(ys.shape)})")
-        else:
-            xs = [(c[0] if c.dim() == 4 and c.shape[0] == 1 else c) for c in xs]
-            ys = [(c[0] if c.dim() == 4 and c.shape[0] == 1 else c) for c in ys]
-            if len(xs) != len(ys):
-                raise ValueError(f"{len(xs)} images on side one, {len(ys)} on side two")
-        groups = {}
-        for i, (a, b) in enumerate(zip(xs, ys)):
-            if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.dim() != 3 or b.dim() != 3 or a.shape[-1] != 3 or b.shape[-1] != 3:
-                raise ValueError(f"pair {i} must be two (H,W,3) uint8 images")
-            if a.shape != b.shape:
-                raise ValueError(f"pair {i} has two sizes ({a.shape[0]} x {a.shape[1]} and {b.shape[0]} x {b.shape[1]})")
-            lpips_model.check_size(a.shape[0], a.shape[1], f"LPIPS: pair {i}")
-            groups.setdefault((a.shape[0], a.shape[1]), []).append(i)
-        n = len(xs)
+        n, chunks = chunks_by_size(xs, ys, lpips_model.check_size, "LPIPS", self.budget)
         res = torch.zeros(n, dtype=torch.float64, device=self.dev)
-        for (h, w), idx in groups.items():
-            step = pairs_per_chunk(h, w, self.budget)
-            for at in range(0, len(idx), step):
-                part = idx[at:at + step]
-                if stacked and part == list(range(part[0], part[0] + len(part))):
-                    got = self._chunk(xs[part[0]:part[0] + len(part)], ys[part[0]:part[0] + len(part)])
-                else:
-                    got = self._chunk([xs[i] for i in part], [ys[i] for i in part])
-                res[torch.as_tensor(part, device=self.dev)] = got
+        for part, xp, yp in chunks:
+            res[torch.as_tensor(part, device=self.dev)] = self._chunk(xp, yp)
         if n and device.read_split_overflow():
             raise FloatingPointError("LPIPS VGG-16 trunk: an activation exceeded the fp16 range of the split-precision format "
                                      "(|v| > 65504); the result is not usable")
