@@ -456,7 +456,7 @@ int tise_pool2x2_pairs(const tise_pair_t* table_dev, const tise_pair_t* out_tabl
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * LPIPS (VGG-16) of image PAIRS (csrc/lpips.hip; tise_toolbox_amd/lpips_hip.py).  No counterpart in the reference; restated from
+ * LPIPS (VGG-16) of image PAIRS (csrc/lpips.hip, csrc/split_px.h; tise_toolbox_amd/lpips_hip.py on vgg_pairs_hip.py).  No counterpart in the reference; restated from
  * Zhang, Isola, Efros, Shechtman & Wang 2018 (the `lpips` package v0.1, net = vgg):
  *   input    8-bit RGB; x = b / 127.5 - 1, then (x - shift_c) / scale_c, shift = (-0.030, -0.088, -0.188), scale = (0.458, 0.448,
  *            0.450): a 3 x 256 fp32 table the caller forms.
@@ -501,7 +501,7 @@ int tise_lpips_layer(const void* feat_dev, int64_t n, int h, int w, int C, const
                      size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * DISTS of image PAIRS (csrc/dists.hip; tise_toolbox_amd/dists_hip.py).  No counterpart in the reference; restated from Ding, Ma,
+ * DISTS of image PAIRS (csrc/dists.hip, csrc/split_px.h; tise_toolbox_amd/dists_hip.py on vgg_pairs_hip.py).  No counterpart in the reference; restated from Ding, Ma,
  * Wang & Simoncelli 2020, "Image Quality Assessment: Unifying Structure and Texture Similarity" (the DISTS_pytorch package from
  * memory; parity with its numbers is unpinned):
  *   stage 0  the image itself, x = b / 255, 3 channels.

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from tise_toolbox_amd import dists, dists_model
+from tise_toolbox_amd import dists, dists_model, paired
 
 
 def test_input_table_is_numpy_fp32():
@@ -194,12 +194,12 @@ def test_cli_surface_and_host_arithmetic(tmp_path):
     assert torch.equal(model.alpha, dists_model.DistsVGG16().init_synthetic(2).alpha)
     # {n, sum, sum of squares} -> mean and population std; additive over shards, an empty one included
     v = np.array([0.25, 0.5, 0.0, 0.125])
-    s = dists.sums(v[:3]) + dists.sums(v[3:]) + dists.sums([])
+    s = paired.value_sums(v[:3]) + paired.value_sums(v[3:]) + paired.value_sums([])
     res = dists.result_from_sums(s)
     assert res["n"] == 4 and res["dists"] == v.mean() and res["dists_std"] == pytest.approx(v.std(), abs=1e-15)
     assert dists.result_lines(res) == [f"DISTS: {v.mean()} +- {res['dists_std']}"]
     assert dists.result_lines(res, weights.SYNTHETIC_TAG)[0].endswith(weights.SYNTHETIC_TAG)
     with pytest.raises(RuntimeError, match="at least one pair"):
-        dists.result_from_sums(dists.sums([]))
+        dists.result_from_sums(paired.value_sums([]))
     text = dists.per_pair_csv(["a/0.png", "a/1.png"], ["b/0.jpg", "b/1.jpg"], {"h": [16, 35], "w": [16, 67], "dists": [0.0, 0.1]})
     assert text == "pair,file1,file2,h,w,dists\n0,a/0.png,b/0.jpg,16,16,0.0\n1,a/1.png,b/1.jpg,35,67,0.1\n"

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from tise_toolbox_amd import conv_split, lpips, lpips_model
+from tise_toolbox_amd import conv_split, lpips, lpips_model, paired
 
 
 def test_input_table_is_numpy_fp32():
@@ -167,19 +167,19 @@ def test_cli_surface_and_host_arithmetic(tmp_path):
     assert torch.equal(model.convs[0].weight, lpips_model.LpipsVGG16().init_synthetic(2).convs[0].weight)
     # {n, sum, sum of squares} -> mean and population std; additive over shards, an empty one included
     v = np.array([0.25, 0.5, 0.0, 0.125])
-    s = lpips.sums(v[:3]) + lpips.sums(v[3:]) + lpips.sums([])
+    s = paired.value_sums(v[:3]) + paired.value_sums(v[3:]) + paired.value_sums([])
     res = lpips.result_from_sums(s)
     assert res["n"] == 4 and res["lpips"] == v.mean() and res["lpips_std"] == pytest.approx(v.std(), abs=1e-15)
     assert lpips.result_lines(res) == [f"LPIPS (vgg): {v.mean()} +- {res['lpips_std']}"]
     assert lpips.result_lines(res, weights.SYNTHETIC_TAG)[0].endswith(weights.SYNTHETIC_TAG)
     with pytest.raises(RuntimeError, match="at least one pair"):
-        lpips.result_from_sums(lpips.sums([]))
+        lpips.result_from_sums(paired.value_sums([]))
     text = lpips.per_pair_csv(["a/0.png", "a/1.png"], ["b/0.jpg", "b/1.jpg"], {"h": [16, 35], "w": [16, 67], "lpips": [0.0, 0.1]})
     assert text == "pair,file1,file2,h,w,lpips\n0,a/0.png,b/0.jpg,16,16,0.0\n1,a/1.png,b/1.jpg,35,67,0.1\n"
 
 
 def test_chunking_by_the_byte_budget():
-    from tise_toolbox_amd import lpips_hip
-    assert lpips_hip.ACTIVATION_BUDGET_BYTES == 2 << 30
-    assert lpips_hip.pairs_per_chunk(256, 256) == 64 and lpips_hip.pairs_per_chunk(256, 256, 1) == 1
-    assert lpips_hip.pairs_per_chunk(16, 16) == 16384 and lpips_hip.pairs_per_chunk(16, 16, 1 << 62) == 32767
+    from tise_toolbox_amd import vgg_pairs_hip
+    assert vgg_pairs_hip.ACTIVATION_BUDGET_BYTES == 2 << 30
+    assert vgg_pairs_hip.pairs_per_chunk(256, 256) == 64 and vgg_pairs_hip.pairs_per_chunk(256, 256, 1) == 1
+    assert vgg_pairs_hip.pairs_per_chunk(16, 16) == 16384 and vgg_pairs_hip.pairs_per_chunk(16, 16, 1 << 62) == 32767

@@ -203,3 +203,48 @@ def test_cli_arguments():
             paired.parse_args(argv)
     from tise_toolbox_amd import feeds
     assert feeds.PAIRED.drop_last is False and feeds.PAIRED.kinds == feeds.IS.kinds
+
+
+# the options every pair-metric CLI has: flag, default, help (None: no help text; a dict: the wording differs by tool, which
+# --help has always shown -- paired prints several result lines and has no stand-in parameters to seed)
+_SEED_MODEL = "seed of the --self-pairs draw and of the --synthetic-weights parameters"
+COMMON_OPTIONS = {
+    "path1": ("--path1", None, "folder of originals (with --self-pairs: the one folder)"),
+    "path2": ("--path2", None, "folder of reconstructions, paired by relative path without extension"),
+    "self_pairs": ("--self-pairs", 0, "N random pairs (i != j) of --path1 instead of two folders"),
+    "seed": ("--seed", 0, {"paired": "seed of the --self-pairs draw", "lpips": _SEED_MODEL, "dists": _SEED_MODEL}),
+    "per_pair": ("--per-pair", "", "write one CSV line per pair here"),
+    "saved_file": ("--saved_file", "", {"paired": "write the result lines here as well", "lpips": "write the result line here as well",
+                                        "dists": "write the result line here as well"}),
+    "batch_size": ("--batch-size", 50, None),
+    "png_feed": ("--png-feed", "ring", None),
+    "jpeg_feed": ("--jpeg-feed", None, None),
+    "num_workers": ("--num-workers", 0, "image decode processes per side (0 = auto)"),
+    "gpu_id": ("--gpu_id", "0", None),
+}
+OWN_OPTIONS = {"paired": {"ms_ssim"}, "lpips": {"weights", "lpips_weights", "synthetic_weights"},
+               "dists": {"weights", "dists_weights", "synthetic_weights"}}
+
+
+def test_the_three_pair_parsers_agree_on_the_common_options(monkeypatch, capsys):
+    import argparse
+    from tise_toolbox_amd import dists, lpips, paired
+    seen = []
+    real = argparse.ArgumentParser.parse_args
+    monkeypatch.setattr(argparse.ArgumentParser, "parse_args", lambda self, argv=None: (seen.append(self), real(self, argv))[1])
+    for name, mod in (("paired", paired), ("lpips", lpips), ("dists", dists)):
+        del seen[:]
+        mod.parse_args(["--path1", "A", "--path2", "B"])
+        actions = {a.dest: a for a in seen[0]._actions if a.dest != "help"}
+        assert set(actions) == set(COMMON_OPTIONS) | OWN_OPTIONS[name], name
+        for dest, (flag, default, text) in COMMON_OPTIONS.items():
+            a = actions[dest]
+            want = text[name] if isinstance(text, dict) else text
+            assert (a.option_strings, a.default, a.help) == ([flag], default, want), (name, dest)
+        assert actions["path1"].required and actions["png_feed"].choices == ["ring", "dataloader"]
+        assert actions["jpeg_feed"].choices == ["native", "pillow"]
+        for argv, said in ((["--path1", "A", "--self-pairs", "3", "--path2", "X"], "--self-pairs takes --path1 only"),
+                           (["--path1", "A"], "give --path2, or --self-pairs N")):
+            with pytest.raises(SystemExit) as e:
+                mod.parse_args(argv)
+            assert e.value.code == 2 and capsys.readouterr().err.rstrip().endswith("error: " + said), (name, argv)

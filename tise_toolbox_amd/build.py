@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtise_hip.so")
 SOURCES = ["capi.hip", "stats.hip", "resize.hip", "resize_f32.hip", "resize_tf1.hip", "resize_torch.hip", "is_score.hip", "frechet.hip", "trunk_ops.hip", "conv_split.hip", "conv_pipe.hip", "retrieval.hip", "clip_ops.hip", "png_unfilter.hip", "calibrate.hip", "jpeg_idct.hip", "mmd.hip", "knn.hip", "ssim.hip", "lpips.hip", "dists.hip"]
-HEADERS = ["common.h", "gemm_tile.h", "rows_tile.h", "conv_epilogue.h", "resize_plan.h", os.path.join("..", "..", "include", "tise_hip.h")]
+HEADERS = ["common.h", "gemm_tile.h", "rows_tile.h", "conv_epilogue.h", "resize_plan.h", "split_px.h", os.path.join("..", "..", "include", "tise_hip.h")]
 
 
 def _hipcc():

@@ -33,10 +33,9 @@
 // input magnitude (plus 1e-6) -- the guard cannot fire here and this file keeps no flag word; the convolutions keep theirs.
 #include <math.h>
 #include "common.h"
+#include "split_px.h"
 
 namespace {
-
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
 
 constexpr int kMaxSide = TISE_DISTS_MAX_SIDE;
 constexpr int64_t kMaxPairs = TISE_DISTS_MAX_PAIRS;
@@ -45,29 +44,12 @@ constexpr int kMaxC = TISE_DISTS_MAX_CHANNELS;         // two channels per threa
 constexpr int kSumPix = TISE_DISTS_SUM_PIXELS;         // pixels of one pair per workgroup of the stage-0 sums
 constexpr double kC1 = 1e-6, kC2 = 1e-6;
 
-// the 8 channels of chunk `ch8` of a pixel as exact doubles
-__device__ __forceinline__ void load_chunk(const _Float16* __restrict__ pixel, int C, int ch8, double v[8]) {
-    const _Float16* q = pixel + tise_ilv_off(8 * ch8, C);
-    const half8v vh = *reinterpret_cast<const half8v*>(q);
-    const half8v vl = *reinterpret_cast<const half8v*>(q + tise_ilv_second(8 * ch8, C));
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (double)(float)vh[i] + (double)(float)vl[i] * (1.0 / 2048.0);
-}
-
 __global__ __launch_bounds__(256) void l2pool3s2_split_kernel(const _Float16* __restrict__ x, int x_C, int x_off,
                                                               int N, int H, int W, int C8,
                                                               _Float16* __restrict__ out, int out_C, int out_off) {
 #pragma clang fp contract(off)
-    const int OH = (H + 1) / 2, OW = (W + 1) / 2;
-    const unsigned per_img = (unsigned)OH * (unsigned)OW * (unsigned)C8;
-    const unsigned e = blockIdx.x * 256u + threadIdx.x;
-    if (e >= per_img) return;
-    const unsigned pix = e / (unsigned)C8;
-    const int c8 = (int)(e - pix * (unsigned)C8);
-    const int oh = (int)(pix / (unsigned)OW), ow = (int)(pix - (unsigned)oh * (unsigned)OW);
-    const int64_t n = blockIdx.y;
-    const int64_t p = n * OH * OW + pix;
-    const int xo = tise_ilv_off(x_off + 8 * c8, x_C), xs = tise_ilv_second(x_off + 8 * c8, x_C);
+    const SplitPoolThread t = split_pool_thread((H + 1) / 2, (W + 1) / 2, C8, x_C, x_off);
+    if (!t.live) return;
     double acc[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = 0.0;
@@ -75,29 +57,18 @@ __global__ __launch_bounds__(256) void l2pool3s2_split_kernel(const _Float16* __
     for (int dh = 0; dh < 3; ++dh)
 #pragma unroll
         for (int dw = 0; dw < 3; ++dw) {
-            const int ih = 2 * oh - 1 + dh, iw = 2 * ow - 1 + dw;
+            const int ih = 2 * t.oh - 1 + dh, iw = 2 * t.ow - 1 + dw;
             if (ih < 0 || ih >= H || iw < 0 || iw >= W) continue;            // zero padding: the tap contributes 0
             const double g = (dh == 1 ? 0.5 : 0.25) * (dw == 1 ? 0.5 : 0.25);
-            const _Float16* q = x + ((n * H + ih) * W + iw) * (2 * (int64_t)x_C) + xo;
-            const half8v vh = *reinterpret_cast<const half8v*>(q);
-            const half8v vl = *reinterpret_cast<const half8v*>(q + xs);
+            double v[8];
+            split_load8_f64(x + ((t.n * H + ih) * W + iw) * t.x_px + t.xo, t.xs, v);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const double v = (double)(float)vh[i] + (double)(float)vl[i] * (1.0 / 2048.0);
-                acc[i] += g * (v * v);
-            }
+            for (int i = 0; i < 8; ++i) acc[i] += g * (v[i] * v[i]);
         }
-    half8v bh, bl;
+    float f[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float f = (float)sqrt(acc[i] + 1e-12);
-        bh[i] = (_Float16)f;
-        bl[i] = (_Float16)((f - (float)bh[i]) * 2048.f);
-    }
-    const int ch = out_off + 8 * c8;
-    _Float16* d = out + p * (2 * (int64_t)out_C) + tise_ilv_off(ch, out_C);
-    *reinterpret_cast<half8v*>(d) = bh;
-    *reinterpret_cast<half8v*>(d + tise_ilv_second(ch, out_C)) = bl;
+    for (int i = 0; i < 8; ++i) f[i] = (float)sqrt(acc[i] + 1e-12);
+    t.store8(f, out, out_C, out_off);
 }
 
 // Adds the 8 values of every thread over the P pixel slots of a chunk, slot 0 first, and writes the C sums to dst[0..C).
@@ -137,10 +108,10 @@ __global__ __launch_bounds__(256) void dists_sum_kernel(const _Float16* __restri
 #pragma unroll
         for (int i = 0; i < 8; ++i) p[i] = sum[i] = nd[i] = 0.0;
         if (active) {
-            load_chunk(f, C, j, p);                                      // the image's first pixel
+            split_chunk_f64(f, C, j, p);                                      // the image's first pixel
             for (int64_t q = q0 + g; q < q1; q += P) {
                 double v[8];
-                load_chunk(f + q * (2 * (int64_t)C), C, j, v);
+                split_chunk_f64(f + q * (2 * (int64_t)C), C, j, v);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     sum[i] += v[i];
@@ -198,8 +169,8 @@ __global__ __launch_bounds__(256) void dists_center_kernel(const _Float16* __res
         }
         for (int64_t q = q0 + g; q < q1; q += P) {
             double a[8], b[8];
-            load_chunk(fa + q * (2 * (int64_t)C), C, j, a);
-            load_chunk(fb + q * (2 * (int64_t)C), C, j, b);
+            split_chunk_f64(fa + q * (2 * (int64_t)C), C, j, a);
+            split_chunk_f64(fb + q * (2 * (int64_t)C), C, j, b);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const double dx = a[i] - mx[i], dy = b[i] - my[i];
@@ -284,33 +255,18 @@ __global__ __launch_bounds__(256) void dists_image_sums_kernel(const tise_pair_t
     }
 }
 
-int check_sizes(int64_t n, int h, int w) {
-    if (n < 0 || h < 1 || w < 1) return TISE_ERR_INVALID_ARG;
-    if (h > kMaxSide || w > kMaxSide || n > kMaxPairs) return TISE_ERR_UNSUPPORTED;
-    return TISE_OK;
-}
-
 }  // namespace
 
 extern "C" int tise_l2pool3s2_split_nhwc(const void* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, void* out_dev,
                                          int64_t out_ld, int out_off, void* stream) {
-    if (!x_dev || !out_dev || n < 0 || h < 1 || w < 1 || C <= 0 || C % 8 || x_ld % 16 || x_off % 8 || out_ld % 16 || out_off % 8 ||
-        x_off < 0 || out_off < 0 || x_off + C > x_ld || out_off + C > out_ld || x_ld > 0x7fffffff || out_ld > 0x7fffffff ||
-        ((uintptr_t)x_dev & 15) || ((uintptr_t)out_dev & 15))
-        return TISE_ERR_INVALID_ARG;
-    if (n == 0) return TISE_OK;
+    if (!split_pool_args_ok(x_dev, x_ld, x_off, n, h, w, 1, C, out_dev, out_ld, out_off)) return TISE_ERR_INVALID_ARG;
     const int oh = (int)(((int64_t)h + 1) / 2), ow = (int)(((int64_t)w + 1) / 2);
-    if (n > 65535 || (int64_t)oh * ow * (C / 8) >= 0x7fffff00LL) return TISE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(l2pool3s2_split_kernel, dim3((unsigned)(((int64_t)oh * ow * (C / 8) + 255) / 256), (unsigned)n), dim3(256), 0,
-                       (hipStream_t)stream, reinterpret_cast<const _Float16*>(x_dev), (int)x_ld, x_off, n, h, w, C / 8,
-                       reinterpret_cast<_Float16*>(out_dev), (int)out_ld, out_off);
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    return split_pool_launch(l2pool3s2_split_kernel, oh, ow, x_dev, x_ld, x_off, n, h, w, C, out_dev, out_ld, out_off, stream);
 }
 
 extern "C" int tise_dists_workspace_bytes(int64_t n, int h, int w, int C, size_t* bytes) {
     if (!bytes || C < 16 || C % 16) return TISE_ERR_INVALID_ARG;
-    const int st = check_sizes(n, h, w);
+    const int st = check_sizes(n, h, w, kMaxSide, kMaxPairs);
     if (st != TISE_OK) return st;
     if (C > kMaxC) return TISE_ERR_UNSUPPORTED;
     const int64_t slots = ceil_div64((int64_t)h * w, kWgPix);
@@ -351,7 +307,7 @@ extern "C" int tise_dists_layer(const void* feat_dev, int64_t n, int h, int w, i
 
 extern "C" int tise_dists_image_sums_u8(const tise_pair_t* table_dev, int64_t n, int h, int w, int64_t* out_dev, void* stream) {
     if (!table_dev || !out_dev || ((uintptr_t)table_dev & 7) || ((uintptr_t)out_dev & 7)) return TISE_ERR_INVALID_ARG;
-    const int st = check_sizes(n, h, w);
+    const int st = check_sizes(n, h, w, kMaxSide, kMaxPairs);
     if (st != TISE_OK) return st;
     if (n == 0) return TISE_OK;
     hipStream_t s = (hipStream_t)stream;

@@ -31,10 +31,9 @@
 // -- so this file keeps no flag word; the convolutions between them keep theirs.
 #include <math.h>
 #include "common.h"
+#include "split_px.h"
 
 namespace {
-
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
 
 constexpr int kMaxSide = TISE_LPIPS_MAX_SIDE;
 constexpr int64_t kMaxPairs = TISE_LPIPS_MAX_PAIRS;
@@ -69,17 +68,8 @@ __global__ __launch_bounds__(256) void lpips_input_kernel(const tise_pair_t* __r
 __global__ __launch_bounds__(256) void maxpool2s2_split_kernel(const _Float16* __restrict__ x, int x_C, int x_off,
                                                                int N, int H, int W, int C8,
                                                                _Float16* __restrict__ out, int out_C, int out_off) {
-    const int OH = H / 2, OW = W / 2;
-    const unsigned per_img = (unsigned)OH * (unsigned)OW * (unsigned)C8;
-    const unsigned e = blockIdx.x * 256u + threadIdx.x;
-    if (e >= per_img) return;
-    const unsigned pix = e / (unsigned)C8;
-    const int c8 = (int)(e - pix * (unsigned)C8);
-    const unsigned oh = pix / (unsigned)OW, ow = pix - oh * (unsigned)OW;
-    const int64_t n = blockIdx.y;
-    const int64_t p = n * OH * OW + pix;
-    const int64_t base = (n * H + 2 * oh) * W + 2 * ow;
-    const int xo = tise_ilv_off(x_off + 8 * c8, x_C), xs = tise_ilv_second(x_off + 8 * c8, x_C);
+    const SplitPoolThread t = split_pool_thread(H / 2, W / 2, C8, x_C, x_off);
+    if (!t.live) return;
     float bv[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) bv[i] = -INFINITY;
@@ -87,31 +77,12 @@ __global__ __launch_bounds__(256) void maxpool2s2_split_kernel(const _Float16* _
     for (int dh = 0; dh < 2; ++dh)
 #pragma unroll
         for (int dw = 0; dw < 2; ++dw) {
-            const _Float16* q = x + (base + (int64_t)dh * W + dw) * (2 * (int64_t)x_C) + xo;
-            const half8v vh = *reinterpret_cast<const half8v*>(q);
-            const half8v vl = *reinterpret_cast<const half8v*>(q + xs);
+            float v[8];
+            split_load8_f32(x + ((t.n * H + 2 * t.oh + dh) * W + 2 * t.ow + dw) * t.x_px + t.xo, t.xs, v);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) bv[i] = fmaxf(bv[i], (float)vh[i] + (float)vl[i] * (1.f / 2048.f));
+            for (int i = 0; i < 8; ++i) bv[i] = fmaxf(bv[i], v[i]);
         }
-    half8v bh, bl;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        bh[i] = (_Float16)bv[i];
-        bl[i] = (_Float16)((bv[i] - (float)bh[i]) * 2048.f);
-    }
-    const int ch = out_off + 8 * c8;
-    _Float16* d = out + p * (2 * (int64_t)out_C) + tise_ilv_off(ch, out_C);
-    *reinterpret_cast<half8v*>(d) = bh;
-    *reinterpret_cast<half8v*>(d + tise_ilv_second(ch, out_C)) = bl;
-}
-
-// the 8 channels of chunk `ch8` of a pixel as exact doubles
-__device__ __forceinline__ void load_chunk(const _Float16* __restrict__ pixel, int C, int ch8, double v[8]) {
-    const _Float16* q = pixel + tise_ilv_off(8 * ch8, C);
-    const half8v vh = *reinterpret_cast<const half8v*>(q);
-    const half8v vl = *reinterpret_cast<const half8v*>(q + tise_ilv_second(8 * ch8, C));
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (double)(float)vh[i] + (double)(float)vl[i] * (1.0 / 2048.0);
+    t.store8(bv, out, out_C, out_off);
 }
 
 // sum over the G lanes of a group (G a power of two, groups aligned): the same bits in every lane of the group
@@ -143,8 +114,8 @@ __global__ __launch_bounds__(256) void lpips_head_kernel(const _Float16* __restr
 #pragma unroll
         for (int i = 0; i < 8; ++i) a[i] = b[i] = 0.0;
         if (live && has_chunk) {
-            load_chunk(fa + q * (2 * (int64_t)C), C, j, a);
-            load_chunk(fb + q * (2 * (int64_t)C), C, j, b);
+            split_chunk_f64(fa + q * (2 * (int64_t)C), C, j, a);
+            split_chunk_f64(fb + q * (2 * (int64_t)C), C, j, b);
         }
         double sa = 0.0, sb = 0.0;
 #pragma unroll
@@ -179,19 +150,13 @@ __global__ __launch_bounds__(64) void lpips_finish_kernel(const double* __restri
     if (lane == 0) out[blockIdx.x] += acc / (double)hw;
 }
 
-int check_sizes(int64_t n, int h, int w) {
-    if (n < 0 || h < 1 || w < 1) return TISE_ERR_INVALID_ARG;
-    if (h > kMaxSide || w > kMaxSide || n > kMaxPairs) return TISE_ERR_UNSUPPORTED;
-    return TISE_OK;
-}
-
 }  // namespace
 
 extern "C" int tise_lpips_input_split(const tise_pair_t* table_dev, int64_t n, int h, int w, const float* lut_dev, void* out_dev,
                                       void* stream) {
     if (!table_dev || !lut_dev || !out_dev || ((uintptr_t)table_dev & 7) || ((uintptr_t)lut_dev & 3) || ((uintptr_t)out_dev & 15))
         return TISE_ERR_INVALID_ARG;
-    const int st = check_sizes(n, h, w);
+    const int st = check_sizes(n, h, w, kMaxSide, kMaxPairs);
     if (st != TISE_OK) return st;
     if (n == 0) return TISE_OK;
     const int64_t blocks = ceil_div64((int64_t)h * w * 8, 256);
@@ -203,23 +168,13 @@ extern "C" int tise_lpips_input_split(const tise_pair_t* table_dev, int64_t n, i
 
 extern "C" int tise_maxpool2s2_split_nhwc(const void* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, void* out_dev,
                                           int64_t out_ld, int out_off, void* stream) {
-    if (!x_dev || !out_dev || n < 0 || h < 2 || w < 2 || C <= 0 || C % 8 || x_ld % 16 || x_off % 8 || out_ld % 16 || out_off % 8 ||
-        x_off < 0 || out_off < 0 || x_off + C > x_ld || out_off + C > out_ld || x_ld > 0x7fffffff || out_ld > 0x7fffffff ||
-        ((uintptr_t)x_dev & 15) || ((uintptr_t)out_dev & 15))
-        return TISE_ERR_INVALID_ARG;
-    if (n == 0) return TISE_OK;
-    const int oh = h / 2, ow = w / 2;
-    if (n > 65535 || (int64_t)oh * ow * (C / 8) >= 0x7fffff00LL) return TISE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(maxpool2s2_split_kernel, dim3((unsigned)(((int64_t)oh * ow * (C / 8) + 255) / 256), (unsigned)n), dim3(256), 0,
-                       (hipStream_t)stream, reinterpret_cast<const _Float16*>(x_dev), (int)x_ld, x_off, n, h, w, C / 8,
-                       reinterpret_cast<_Float16*>(out_dev), (int)out_ld, out_off);
-    TISE_LAUNCH_CHECK();
-    return TISE_OK;
+    if (!split_pool_args_ok(x_dev, x_ld, x_off, n, h, w, 2, C, out_dev, out_ld, out_off)) return TISE_ERR_INVALID_ARG;
+    return split_pool_launch(maxpool2s2_split_kernel, h / 2, w / 2, x_dev, x_ld, x_off, n, h, w, C, out_dev, out_ld, out_off, stream);
 }
 
 extern "C" int tise_lpips_workspace_bytes(int64_t n, int h, int w, size_t* bytes) {
     if (!bytes) return TISE_ERR_INVALID_ARG;
-    const int st = check_sizes(n, h, w);
+    const int st = check_sizes(n, h, w, kMaxSide, kMaxPairs);
     if (st != TISE_OK) return st;
     *bytes = (size_t)(n * ceil_div64((int64_t)h * w, kHeadPix)) * sizeof(double);
     return TISE_OK;

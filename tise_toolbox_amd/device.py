@@ -1209,20 +1209,68 @@ def pool2x2_pairs(xs, ys, out=None):
 
 
 LPIPS_MAX_SIDE, LPIPS_MAX_PAIRS, LPIPS_WG_PIXELS, LPIPS_MAX_CHANNELS = 16384, 32767, 256, 512       # TISE_LPIPS_* of the header
+# TISE_DISTS_* of the header
+DISTS_MAX_SIDE, DISTS_MAX_PAIRS, DISTS_WG_PIXELS, DISTS_MAX_CHANNELS, DISTS_SUM_PIXELS = 16384, 32767, 512, 512, 4096
+
+
+def _one_size_pairs(xs, ys, fn, max_pairs):
+    """_pair_images' uint8 sides for a launch that takes pairs of ONE size, at most ``max_pairs`` -> (xs, ys, n, device, h, w)."""
+    xs, ys, _ = _pair_images(xs, ys, fn, 1, (torch.uint8,))
+    n, dev = len(xs), _side_device(xs)
+    _, hs, ws = _pair_geometry(xs)
+    h, w = int(hs[0]), int(ws[0])
+    if bool((hs != h).any()) or bool((ws != w).any()):
+        raise ValueError(f"{fn}: all pairs of a launch must have one size")
+    if n > max_pairs:
+        raise ValueError(f"{fn}: at most {max_pairs} pairs per launch (got {n})")
+    return xs, ys, n, dev, h, w
+
+
+def _require_split(x, fn, pairs=False):
+    """A contiguous split tensor (N,H,W,2C), C % 16 == 0; ``pairs``: (2N,h,w,2C), both sides of N pairs."""
+    if x.dtype != torch.float16 or x.dim() != 4 or (pairs and x.shape[0] % 2) or x.shape[3] % 32 or not x.is_contiguous():
+        raise ValueError(f"{fn}: a contiguous split tensor {'(2N,h,w,2C)' if pairs else '(N,H,W,2C)'} fp16, C % 16 == 0 "
+                         f"(got {tuple(x.shape)} {x.dtype})")
+
+
+def _pool_split(fn, symbol, min_side, out_side, x, out, out_off, x_off, channels):
+    """The body of a split-tensor pool: (N,H,W,2C) -> (N,out_side(H),out_side(W),2C') through the C entry point ``symbol``."""
+    _require_cuda(x)
+    _require_split(x, fn)
+    n, h, w, c2 = x.shape
+    if h < min_side or w < min_side:
+        raise ValueError(f"{fn}: both sides must be at least {min_side} (got {h} x {w})")
+    oh, ow = out_side(h), out_side(w)
+    c = c2 // 2 - x_off if channels is None else int(channels)
+    if out is None:
+        out = torch.empty((n, oh, ow, 2 * (out_off + c)), dtype=torch.float16, device=x.device)
+    elif (out.dtype != torch.float16 or out.dim() != 4 or out.shape[:3] != (n, oh, ow) or out.shape[3] % 32
+          or not out.is_contiguous() or out.device != x.device):
+        raise ValueError(f"{fn}: out must be a contiguous split tensor ({n},{oh},{ow},2C') on {x.device}")
+    _lib.call(symbol, _ptr(x), c2 // 2, int(x_off), n, h, w, c, _ptr(out), out.shape[3] // 2, int(out_off), _stream())
+    return out
+
+
+def _layer_buffers(fn, out, workspace, n, dev, need):
+    """The ``out`` and ``workspace`` arguments of a *_layer call on N pairs -> the workspace to use (a fresh one of ``need()``
+    bytes by default), or None when N == 0 and there is nothing to launch."""
+    if out.dtype != torch.float64 or out.shape != (n,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"{fn}: out must be {n} contiguous float64 on {dev}")
+    if n == 0:
+        return None
+    need = need()
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or workspace.device != dev:
+        raise ValueError(f"{fn}: workspace must be at least {need} contiguous uint8 on {dev}")
+    return workspace
 
 
 def lpips_input_split(xs, ys, lut, out=None):
     """Two (N,H,W,3) uint8 CUDA tensors or two lists of (H,W,3) uint8 CUDA tensors, ALL of one size, and the (3,256) float32
     input table -> the split tensor (2N,H,W,64) fp16 conv1_1 reads (tise_lpips_input_split): images 0..N-1 side one, N..2N-1
     side two; channels 0..2 = lut[c][byte] in split form, channels 3..31 zero in both halves."""
-    xs, ys, _ = _pair_images(xs, ys, "lpips_input_split", 1, (torch.uint8,))
-    n, dev = len(xs), _side_device(xs)
-    _, hs, ws = _pair_geometry(xs)
-    h, w = int(hs[0]), int(ws[0])
-    if bool((hs != h).any()) or bool((ws != w).any()):
-        raise ValueError("lpips_input_split: all pairs of a launch must have one size")
-    if n > LPIPS_MAX_PAIRS:
-        raise ValueError(f"lpips_input_split: at most {LPIPS_MAX_PAIRS} pairs per launch (got {n})")
+    xs, ys, n, dev, h, w = _one_size_pairs(xs, ys, "lpips_input_split", LPIPS_MAX_PAIRS)
     _require_cuda(lut)
     if lut.dtype != torch.float32 or lut.shape != (3, 256) or not lut.is_contiguous() or lut.device != dev:
         raise ValueError(f"lpips_input_split: the table must be (3,256) contiguous float32 on {dev}")
@@ -1238,21 +1286,7 @@ def lpips_input_split(xs, ys, lut, out=None):
 def maxpool2s2_split(x, out=None, out_off=0, x_off=0, channels=None):
     """max_pool2d(2, stride 2) (floor) of ``channels`` channels from ``x_off`` of a split tensor (N,H,W,2C) into the channels from
     ``out_off`` of a split tensor (N,H//2,W//2,2C') (tise_maxpool2s2_split_nhwc; default: all channels into a fresh tensor)."""
-    _require_cuda(x)
-    if x.dtype != torch.float16 or x.dim() != 4 or x.shape[3] % 32 or not x.is_contiguous():
-        raise ValueError(f"maxpool2s2_split: a contiguous split tensor (N,H,W,2C) fp16, C % 16 == 0 (got {tuple(x.shape)} {x.dtype})")
-    n, h, w, c2 = x.shape
-    if h < 2 or w < 2:
-        raise ValueError(f"maxpool2s2_split: both sides must be at least 2 (got {h} x {w})")
-    c = c2 // 2 - x_off if channels is None else int(channels)
-    if out is None:
-        out = torch.empty((n, h // 2, w // 2, 2 * (out_off + c)), dtype=torch.float16, device=x.device)
-    elif (out.dtype != torch.float16 or out.dim() != 4 or out.shape[:3] != (n, h // 2, w // 2) or out.shape[3] % 32
-          or not out.is_contiguous() or out.device != x.device):
-        raise ValueError(f"maxpool2s2_split: out must be a contiguous split tensor ({n},{h // 2},{w // 2},2C') on {x.device}")
-    _lib.call("tise_maxpool2s2_split_nhwc", _ptr(x), c2 // 2, int(x_off), n, h, w, c, _ptr(out), out.shape[3] // 2, int(out_off),
-              _stream())
-    return out
+    return _pool_split("maxpool2s2_split", "tise_maxpool2s2_split_nhwc", 2, lambda s: s // 2, x, out, out_off, x_off, channels)
 
 
 def lpips_workspace_bytes(n, h, w):
@@ -1267,30 +1301,18 @@ def lpips_layer(feat, weight, out, workspace=None):
     fp64 in a fixed order, no atomics; an identical pair adds exactly 0.0).  ``out``: N float64, ``workspace``: uint8 of at least
     lpips_workspace_bytes(N, h, w)."""
     _require_cuda(feat, weight, out)
-    if feat.dtype != torch.float16 or feat.dim() != 4 or feat.shape[0] % 2 or feat.shape[3] % 32 or not feat.is_contiguous():
-        raise ValueError(f"lpips_layer: a contiguous split tensor (2N,h,w,2C) fp16, C % 16 == 0 (got {tuple(feat.shape)} {feat.dtype})")
+    _require_split(feat, "lpips_layer", pairs=True)
     if feat.shape[3] // 2 > LPIPS_MAX_CHANNELS:
         raise ValueError(f"lpips_layer: at most {LPIPS_MAX_CHANNELS} channels (got {feat.shape[3] // 2})")
     n, h, w, c = feat.shape[0] // 2, feat.shape[1], feat.shape[2], feat.shape[3] // 2
     dev = feat.device
     if weight.dtype != torch.float32 or weight.shape != (c,) or not weight.is_contiguous() or weight.device != dev:
         raise ValueError(f"lpips_layer: weight must be {c} contiguous float32 on {dev}")
-    if out.dtype != torch.float64 or out.shape != (n,) or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"lpips_layer: out must be {n} contiguous float64 on {dev}")
-    if n == 0:
-        return out
-    need = lpips_workspace_bytes(n, h, w)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or workspace.device != dev:
-        raise ValueError(f"lpips_layer: workspace must be at least {need} contiguous uint8 on {dev}")
-    _lib.call("tise_lpips_layer", _ptr(feat), ctypes.c_int64(n), h, w, c, _ptr(weight), _ptr(out), _ptr(workspace),
-              ctypes.c_size_t(workspace.numel()), _stream())
+    workspace = _layer_buffers("lpips_layer", out, workspace, n, dev, lambda: lpips_workspace_bytes(n, h, w))
+    if workspace is not None:
+        _lib.call("tise_lpips_layer", _ptr(feat), ctypes.c_int64(n), h, w, c, _ptr(weight), _ptr(out), _ptr(workspace),
+                  ctypes.c_size_t(workspace.numel()), _stream())
     return out
-
-
-# TISE_DISTS_* of the header
-DISTS_MAX_SIDE, DISTS_MAX_PAIRS, DISTS_WG_PIXELS, DISTS_MAX_CHANNELS, DISTS_SUM_PIXELS = 16384, 32767, 512, 512, 4096
 
 
 def l2pool3s2_split(x, out=None, out_off=0, x_off=0, channels=None):
@@ -1298,22 +1320,7 @@ def l2pool3s2_split(x, out=None, out_off=0, x_off=0, channels=None):
     channels from ``x_off`` of a split tensor (N,H,W,2C) into the channels from ``out_off`` of a split tensor
     (N,ceil(H/2),ceil(W/2),2C') (tise_l2pool3s2_split_nhwc: fp64 in a fixed order, one rounding to fp32, split again; default: all
     channels into a fresh tensor)."""
-    _require_cuda(x)
-    if x.dtype != torch.float16 or x.dim() != 4 or x.shape[3] % 32 or not x.is_contiguous():
-        raise ValueError(f"l2pool3s2_split: a contiguous split tensor (N,H,W,2C) fp16, C % 16 == 0 (got {tuple(x.shape)} {x.dtype})")
-    n, h, w, c2 = x.shape
-    if h < 1 or w < 1:
-        raise ValueError(f"l2pool3s2_split: both sides must be at least 1 (got {h} x {w})")
-    oh, ow = (h + 1) // 2, (w + 1) // 2
-    c = c2 // 2 - x_off if channels is None else int(channels)
-    if out is None:
-        out = torch.empty((n, oh, ow, 2 * (out_off + c)), dtype=torch.float16, device=x.device)
-    elif (out.dtype != torch.float16 or out.dim() != 4 or out.shape[:3] != (n, oh, ow) or out.shape[3] % 32
-          or not out.is_contiguous() or out.device != x.device):
-        raise ValueError(f"l2pool3s2_split: out must be a contiguous split tensor ({n},{oh},{ow},2C') on {x.device}")
-    _lib.call("tise_l2pool3s2_split_nhwc", _ptr(x), c2 // 2, int(x_off), n, h, w, c, _ptr(out), out.shape[3] // 2, int(out_off),
-              _stream())
-    return out
+    return _pool_split("l2pool3s2_split", "tise_l2pool3s2_split_nhwc", 1, lambda s: (s + 1) // 2, x, out, out_off, x_off, channels)
 
 
 def dists_workspace_bytes(n, h, w, c):
@@ -1329,8 +1336,7 @@ def dists_layer(feat, alpha, beta, out, workspace=None):
     atomics; an identical pair adds exactly 0.0).  ``out``: N float64, ``workspace``: uint8 of at least
     dists_workspace_bytes(N, h, w, C)."""
     _require_cuda(feat, alpha, beta, out)
-    if feat.dtype != torch.float16 or feat.dim() != 4 or feat.shape[0] % 2 or feat.shape[3] % 32 or not feat.is_contiguous():
-        raise ValueError(f"dists_layer: a contiguous split tensor (2N,h,w,2C) fp16, C % 16 == 0 (got {tuple(feat.shape)} {feat.dtype})")
+    _require_split(feat, "dists_layer", pairs=True)
     if feat.shape[3] // 2 > DISTS_MAX_CHANNELS:
         raise ValueError(f"dists_layer: at most {DISTS_MAX_CHANNELS} channels (got {feat.shape[3] // 2})")
     n, h, w, c = feat.shape[0] // 2, feat.shape[1], feat.shape[2], feat.shape[3] // 2
@@ -1338,17 +1344,10 @@ def dists_layer(feat, alpha, beta, out, workspace=None):
     for name, t in (("alpha", alpha), ("beta", beta)):
         if t.dtype != torch.float64 or t.shape != (c,) or not t.is_contiguous() or t.device != dev:
             raise ValueError(f"dists_layer: {name} must be {c} contiguous float64 on {dev}")
-    if out.dtype != torch.float64 or out.shape != (n,) or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"dists_layer: out must be {n} contiguous float64 on {dev}")
-    if n == 0:
-        return out
-    need = dists_workspace_bytes(n, h, w, c)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or workspace.device != dev:
-        raise ValueError(f"dists_layer: workspace must be at least {need} contiguous uint8 on {dev}")
-    _lib.call("tise_dists_layer", _ptr(feat), ctypes.c_int64(n), h, w, c, _ptr(alpha), _ptr(beta), _ptr(out), _ptr(workspace),
-              ctypes.c_size_t(workspace.numel()), _stream())
+    workspace = _layer_buffers("dists_layer", out, workspace, n, dev, lambda: dists_workspace_bytes(n, h, w, c))
+    if workspace is not None:
+        _lib.call("tise_dists_layer", _ptr(feat), ctypes.c_int64(n), h, w, c, _ptr(alpha), _ptr(beta), _ptr(out), _ptr(workspace),
+                  ctypes.c_size_t(workspace.numel()), _stream())
     return out
 
 
@@ -1356,14 +1355,7 @@ def dists_image_sums(xs, ys, out=None):
     """Two (N,H,W,3) uint8 CUDA tensors or two lists of (H,W,3) uint8 CUDA tensors, ALL of one size -> (N,3,5) int64 on the
     device: per pair and colour the sums over the pixels of bx, by, bx^2, by^2, bx by (tise_dists_image_sums_u8: exact) -- DISTS's
     stage 0, from which the host forms S1 and S2."""
-    xs, ys, _ = _pair_images(xs, ys, "dists_image_sums", 1, (torch.uint8,))
-    n, dev = len(xs), _side_device(xs)
-    _, hs, ws = _pair_geometry(xs)
-    h, w = int(hs[0]), int(ws[0])
-    if bool((hs != h).any()) or bool((ws != w).any()):
-        raise ValueError("dists_image_sums: all pairs of a launch must have one size")
-    if n > DISTS_MAX_PAIRS:
-        raise ValueError(f"dists_image_sums: at most {DISTS_MAX_PAIRS} pairs per launch (got {n})")
+    xs, ys, n, dev, h, w = _one_size_pairs(xs, ys, "dists_image_sums", DISTS_MAX_PAIRS)
     if out is None:
         out = torch.empty((n, 3, 5), dtype=torch.int64, device=dev)
     elif out.dtype != torch.int64 or out.shape != (n, 3, 5) or not out.is_contiguous() or out.device != dev:

@@ -10,7 +10,7 @@ with its numbers is UNPINNED, see README).
   stage 0  the image itself, x = b / 255 in the module's dtype: 3 channels.
   input    (x - mean_c) / std_c with mean = (0.485, 0.456, 0.406), std = (0.229, 0.224, 0.225), computed in fp32 from fp32(b / 255)
            and tabulated: ``input_table()`` is the (3, 256) table every route, the fp64 module included, reads.
-  network  torchvision VGG-16 ``features``: the thirteen 3 x 3 / stride 1 / padding 1 convolutions of lpips_model.CONV_INDICES, each
+  network  torchvision VGG-16 ``features``: the thirteen 3 x 3 / stride 1 / padding 1 convolutions of vgg_pairs.CONV_INDICES, each
            followed by ReLU; each of the four max-pools replaced by the L2 pool y = sqrt(conv(x^2, g, stride 2, padding 1,
            depthwise) + 1e-12), g = a a^T / sum with a = (0.5, 1, 0.5), zero padding: the output is ceil(H/2) x ceil(W/2).
   taps     relu1_2, relu2_2, relu3_3, relu4_3, relu5_3; channels of the six stages 3, 64, 128, 256, 512, 512 = 1475.
@@ -20,19 +20,16 @@ with its numbers is UNPINNED, see README).
            alpha_c (1 - S1_c) + beta_c (1 - S2_c) -- the package's 1 - (sum alpha S1 + sum beta S2) written so that nothing cancels:
            an identical pair is exactly 0.0.
 """
-import os
-
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import lpips_model
-from .lpips_model import CONV_CHANNELS, CONV_INDICES, POOL_BEFORE, TAP_AFTER, _load_file, default_weights_path
+from .vgg_pairs import (CONV_CHANNELS, CONV_INDICES, MIN_SIDE, POOL_BEFORE, TAP_AFTER, VGG16Pairs, default_weights_path,  # noqa: F401
+                        named_source)
 
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
-MIN_SIDE = 16
 C1 = C2 = 1e-6
 POOL_EPS = 1e-12
 POOL_TAPS = (0.25, 0.5, 0.25)                                               # a / sum(a), a = (0.5, 1, 0.5): g = a a^T / sum
@@ -84,32 +81,22 @@ def stage_terms(x, y):
     return s1, s2
 
 
-class DistsVGG16(nn.Module):
+class DistsVGG16(VGG16Pairs):
     """The definition above in plain torch.  ``forward(a, b)``: two (N,H,W,3) uint8 tensors -> (N,) DISTS in the module's dtype
     (fp32 as built, fp64 after ``.double()``)."""
+    check_size = staticmethod(check_size)
 
     def __init__(self):
-        super().__init__()
-        self.convs = nn.ModuleList([nn.Conv2d(ci, co, 3, stride=1, padding=1) for ci, co in CONV_CHANNELS])
+        super().__init__(input_table())
         self.alpha = nn.Parameter(torch.full((1, N_CHANNELS, 1, 1), 0.1), requires_grad=False)
         self.beta = nn.Parameter(torch.full((1, N_CHANNELS, 1, 1), 0.1), requires_grad=False)
-        self.register_buffer("table", input_table())
-        self.synthetic = False
-        for p in self.parameters():
-            p.requires_grad_(False)
+        self.freeze()
 
     # ---- parameters --------------------------------------------------------------------------------------------------
-    def load_trunk(self, source):
-        """A torchvision ``vgg16`` state_dict or its file: lpips_model.LpipsVGG16.load_trunk's checks and refusals, on this
-        module's convolutions."""
-        lpips_model.LpipsVGG16.load_trunk(self, source)
-        return self
-
     def load_dists_weights(self, source):
         """The package's parameter file (keys ``alpha`` and ``beta``, each (1, 1475, 1, 1)) or its dict.  Any other shape is
         refused, naming both."""
-        path = source if isinstance(source, (str, os.PathLike)) else "state_dict"
-        sd = _load_file(source) if isinstance(source, (str, os.PathLike)) else source
+        path, sd = named_source(source)
         want = (1, N_CHANNELS, 1, 1)
         for key in ("alpha", "beta"):
             got = tuple(sd[key].shape) if key in sd and hasattr(sd[key], "shape") else None
@@ -124,13 +111,9 @@ class DistsVGG16(nn.Module):
         """Seeded stand-in parameters (weights.py's rules: plumbing and throughput runs only, result lines are tagged):
         He-scaled normal convolutions and small normal biases as LPIPS's stand-ins, alpha and beta = |N(0.1, 0.01)|."""
         g = torch.Generator().manual_seed(int(seed))
-        for conv in self.convs:
-            fan_in = conv.in_channels * 9
-            conv.weight.copy_((torch.randn(conv.weight.shape, generator=g, dtype=torch.float64) * (2.0 / fan_in) ** 0.5).to(conv.weight.dtype))
-            conv.bias.copy_((torch.randn(conv.bias.shape, generator=g, dtype=torch.float64) * 0.05).to(conv.bias.dtype))
+        self.init_synthetic_trunk(g)
         for p in (self.alpha, self.beta):
             p.copy_((0.1 + 0.01 * torch.randn(p.shape, generator=g, dtype=torch.float64)).abs().to(p.dtype))
-        self.synthetic = True
         return self
 
     def normalized_weights(self):
@@ -142,37 +125,21 @@ class DistsVGG16(nn.Module):
     # ---- arithmetic --------------------------------------------------------------------------------------------------
     def prepare(self, img):
         """(N,H,W,3) uint8 -> (stage 0 (N,3,H,W) = b / 255, the network input (N,3,H,W): the table look-up), module's dtype."""
-        if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3:
-            raise ValueError(f"images must be (N,H,W,3) uint8 (got {tuple(img.shape)} {img.dtype})")
-        check_size(img.shape[1], img.shape[2])
-        dtype = self.convs[0].weight.dtype
-        idx = img.long().permute(0, 3, 1, 2)
-        t = self.table.to(dtype)
-        return idx.to(dtype) / 255, torch.stack([t[c][idx[:, c]] for c in range(3)], dim=1)
+        idx, x = self.table_lookup(img)
+        return idx.to(self.dtype) / 255, x
 
     def stages(self, img, amax=None):
         """(N,H,W,3) uint8 -> the six stage tensors.  ``amax``: a list that receives the largest |activation| of every convolution."""
         x0, x = self.prepare(img)
-        out = [x0]
-        for k, conv in enumerate(self.convs):
-            if k in POOL_BEFORE:
-                x = l2pool(x)
-            x = F.relu(conv(x))
-            if amax is not None:
-                amax.append(float(x.abs().max()))
-            if k in TAP_AFTER:
-                out.append(x)
-        return out
+        return [x0] + self.features(x, l2pool, amax)
 
     def similarities(self, a, b, amax=None):
         """-> (S1, S2, alpha, beta): S (N,1475) in the module's dtype, the normalised weights (1475,) in the module's dtype."""
-        if a.shape != b.shape:
-            raise ValueError(f"both images of a pair must have one size (got {tuple(a.shape)} and {tuple(b.shape)})")
+        self.check_pair(a, b)
         n = a.shape[0]
         st = self.stages(torch.cat([a, b], 0), amax)
         terms = [stage_terms(t[:n], t[n:]) for t in st]
-        dtype = self.convs[0].weight.dtype
-        al, be = (w.to(dtype) for w in self.normalized_weights())
+        al, be = (w.to(self.dtype) for w in self.normalized_weights())
         return torch.cat([t[0] for t in terms], 1), torch.cat([t[1] for t in terms], 1), al, be
 
     def forward(self, a, b, amax=None):

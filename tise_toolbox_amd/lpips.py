@@ -14,13 +14,7 @@ rank 0 writes.  Two parameter files are needed -- torchvision's VGG-16 (--weight
 vgg16-397923af.pth) and the lpips package's linear layers (--lpips-weights); neither comes with the project.
 --synthetic-weights runs seeded stand-ins and tags every result line (weights.py).
 """
-import argparse
-import os
-
-import numpy as np
-import torch
-
-from . import _lib, dist as tdist, feeds, lpips_model, paired, weights as tweights
+from . import dist as tdist, lpips_model, paired
 
 NET = "vgg"
 
@@ -37,19 +31,9 @@ def lpips_from_images(xs, ys, model=None):
     return model(xs, ys)
 
 
-def sums(values):
-    """(3,) float64 {n, sum, sum of squares}: additive over shards, an empty one included."""
-    v = np.asarray(values, dtype=np.float64).reshape(-1)
-    return np.array([v.size, v.sum(), (v * v).sum()], dtype=np.float64)
-
-
 def result_from_sums(s):
-    s = np.asarray(s, dtype=np.float64)
-    if int(s[0]) < 1:
-        raise RuntimeError("LPIPS needs at least one pair")
-    mean = s[1] / s[0]
-    var = max(s[2] / s[0] - mean * mean, 0.0) if np.isfinite(mean) else float("nan")
-    return {"n": int(s[0]), "lpips": float(mean), "lpips_std": float(np.sqrt(var))}
+    """{n, sum, sum of squares} (paired.value_sums: additive over shards) -> mean and population standard deviation."""
+    return paired.value_result(s, "lpips", "LPIPS")
 
 
 def result_lines(res, tag=""):
@@ -57,122 +41,53 @@ def result_lines(res, tag=""):
 
 
 def per_pair_csv(files1, files2, per):
-    rows = ["pair,file1,file2,h,w,lpips"]
-    for i, (f1, f2) in enumerate(zip(files1, files2)):
-        rows.append(f"{i},{f1},{f2},{int(per['h'][i])},{int(per['w'][i])},{float(per['lpips'][i])!r}")
-    return "\n".join(rows) + "\n"
+    return paired.value_csv("lpips", files1, files2, per)
 
 
-def _evaluate(files1, files2, hip, batch_size, options, device):
-    rank, world, _ = tdist.env_world()
-    lo, hi = tdist.shard_range(len(files1), rank, world)
-
-    def per_batch(xs, ys):
-        return {"lpips": hip(xs, ys) if len(xs) else np.zeros(0), "h": np.array([a.shape[0] for a in xs], dtype=np.int64),
-                "w": np.array([a.shape[1] for a in xs], dtype=np.int64)}
-    per = paired.paired_from_files(files1[lo:hi], files2[lo:hi], False, batch_size, options, device, per_batch=per_batch)
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    acc = torch.from_numpy(sums(per["lpips"])).to(dev)
-    tdist.all_reduce_sum_(acc)                               # {n, sum, sum of squares}: the only exchange
-    res = result_from_sums(acc.cpu().numpy())
-    res["per_pair"], res["files1"], res["files2"], res["range"] = per, list(files1), list(files2), (lo, hi)
-    return res
-
-
-def _hip(model, device):
+def _evaluate(files1, files2, model, batch_size, options, device):
     from .engine import require_gpu
     from .lpips_hip import HipLpips
     require_gpu()
-    return model if isinstance(model, HipLpips) else HipLpips(model, device)
+    hip = model if isinstance(model, HipLpips) else HipLpips(model, device)
+    return paired.evaluate_pairs(files1, files2, paired.value_per_batch("lpips", hip), lambda per: paired.value_sums(per["lpips"]),
+                                 result_from_sums, batch_size, options, device)
 
 
 def calculate_lpips_given_paths(path1, path2, model, batch_size=50, options=None, device=None):
     """LPIPS of every pair of two directories (paired.pair_files) -> dict: lpips, lpips_std, n; per_pair (this rank's arrays
     lpips, h, w), files1, files2, range.  ``model``: LpipsVGG16 or HipLpips.  Under torchrun every rank returns the totals."""
-    files1, files2 = paired.pair_files(path1, path2)
-    return _evaluate(files1, files2, _hip(model, device), batch_size, options, device)
+    return _evaluate(*paired.pair_files(path1, path2), model, batch_size, options, device)
 
 
 def calculate_lpips_self_pairs(path, n_pairs, model, seed=0, batch_size=50, options=None, device=None):
     """``n_pairs`` random pairs (paired.draw_self_pairs) of ONE directory's sorted file list -> calculate_lpips_given_paths' dict."""
-    files = paired.list_files(path)
-    idx = paired.draw_self_pairs(len(files), n_pairs, seed)
-    return _evaluate([files[i] for i in idx[:, 0]], [files[j] for j in idx[:, 1]], _hip(model, device), batch_size, options, device)
+    return _evaluate(*paired.self_pair_files(path, n_pairs, seed), model, batch_size, options, device)
 
 
 def parse_args(argv=None):
-    parser = argparse.ArgumentParser(description="LPIPS (VGG-16) of image pairs")
-    parser.add_argument("--path1", required=True, type=str, help="folder of originals (with --self-pairs: the one folder)")
-    parser.add_argument("--path2", default=None, type=str, help="folder of reconstructions, paired by relative path without extension")
-    parser.add_argument("--self-pairs", default=0, type=int, help="N random pairs (i != j) of --path1 instead of two folders")
-    parser.add_argument("--seed", default=0, type=int, help="seed of the --self-pairs draw and of the --synthetic-weights parameters")
-    parser.add_argument("--per-pair", default="", type=str, help="write one CSV line per pair here")
-    parser.add_argument("--saved_file", default="", type=str, help="write the result line here as well")
-    parser.add_argument("--batch-size", default=50, type=int)
-    parser.add_argument("--weights", default="", type=str, help="torchvision VGG-16 state_dict (vgg16-397923af.pth)")
-    parser.add_argument("--lpips-weights", default="", type=str, help="the lpips package's linear layers for VGG-16 (vgg.pth)")
-    parser.add_argument("--synthetic-weights", action="store_true",
-                        help="seeded stand-in parameters: plumbing / throughput runs only (result lines are tagged)")
-    parser.add_argument("--png-feed", default="ring", choices=["ring", "dataloader"])
-    parser.add_argument("--jpeg-feed", default=None, choices=["native", "pillow"])
-    parser.add_argument("--num-workers", default=0, type=int, help="image decode processes per side (0 = auto)")
-    parser.add_argument("--gpu_id", default="0", type=str)
-    args = parser.parse_args(argv)
-    if args.self_pairs:
-        if args.path2:
-            parser.error("--self-pairs takes --path1 only")
-    elif not args.path2:
-        parser.error("give --path2, or --self-pairs N")
-    if args.synthetic_weights and (args.weights or args.lpips_weights):
-        parser.error("--synthetic-weights and --weights / --lpips-weights are mutually exclusive")
-    return args
+    return paired.parse_model_pair_args(argv, "LPIPS (VGG-16) of image pairs", "--lpips-weights",
+                                        "the lpips package's linear layers for VGG-16 (vgg.pth)")
 
 
 def resolve_model(args):
     """-> (LpipsVGG16, tag).  The trunk file: --weights, else the default cache path if it exists; the linear layers have no
     default path.  Anything missing without --synthetic-weights is an error, never a silent stand-in."""
-    if args.synthetic_weights:
-        tweights.warn_synthetic("LPIPS VGG-16")
-        return lpips_model.build_model(synthetic=True, seed=args.seed), tweights.SYNTHETIC_TAG
-    trunk = args.weights or (lpips_model.default_weights_path() if os.path.exists(lpips_model.default_weights_path()) else "")
-    for what, path in (("--weights", trunk), ("--lpips-weights", args.lpips_weights)):
-        if path and not os.path.exists(path):
-            raise RuntimeError("Invalid path: %s" % path)
-    if not trunk or not args.lpips_weights:
-        raise RuntimeError(
-            "no parameters for LPIPS VGG-16: it needs torchvision's VGG-16 (--weights PATH, or the file at "
-            f"{lpips_model.default_weights_path()!r}) and the lpips package's linear layers (--lpips-weights PATH); neither can be "
-            "downloaded here.  Pass both, or --synthetic-weights for a plumbing/throughput run with seeded stand-ins")
-    return lpips_model.build_model(trunk, args.lpips_weights), ""
+    default = lpips_model.default_weights_path()
+    missing = ("no parameters for LPIPS VGG-16: it needs torchvision's VGG-16 (--weights PATH, or the file at "
+               f"{default!r}) and the lpips package's linear layers (--lpips-weights PATH); neither can be "
+               "downloaded here.  Pass both, or --synthetic-weights for a plumbing/throughput run with seeded stand-ins")
+    return paired.resolve_model_files(args, "LPIPS VGG-16", args.lpips_weights, default, lpips_model.build_model, missing)
 
 
 def main(argv=None):
     args = parse_args(argv)
-    if not torch.cuda.is_available():
-        raise _lib.TiseLibraryError("lpips needs an MI355X: there is no CPU path")
-    rank, world, local_rank = tdist.init_from_env()
-    dev = torch.device(f"cuda:{local_rank}" if world > 1 else f"cuda:{args.gpu_id}")
-    torch.cuda.set_device(dev)
+    dev = paired.cli_device(args, "lpips")
     model, tag = resolve_model(args)
-    options = feeds.Options(png_feed=args.png_feed, jpeg_feed=args.jpeg_feed, num_workers=args.num_workers)
     if args.self_pairs:
-        res = calculate_lpips_self_pairs(args.path1, args.self_pairs, model, args.seed, args.batch_size, options, dev)
+        res = calculate_lpips_self_pairs(args.path1, args.self_pairs, model, args.seed, args.batch_size, paired.feed_options(args), dev)
     else:
-        res = calculate_lpips_given_paths(args.path1, args.path2, model, args.batch_size, options, dev)
-    lines = result_lines(res, tag)
-    if args.per_pair:
-        per, (lo, hi) = res["per_pair"], res["range"]
-        cols = [np.arange(lo, hi, dtype=np.float64), per["h"], per["w"], per["lpips"]]
-        rows = tdist.all_gather_rows(torch.from_numpy(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1)).to(dev)).cpu().numpy()
-        if tdist.is_main():
-            with open(args.per_pair, "w") as f:
-                f.write(per_pair_csv(res["files1"], res["files2"], {"h": rows[:, 1], "w": rows[:, 2], "lpips": rows[:, 3]}))
-    if tdist.is_main():
-        if args.saved_file:
-            with open(args.saved_file, "w") as f:
-                f.write("\n".join(lines))                                  # no trailing newline, like paired --saved_file
-        print("\n".join(lines))
-    return res
+        res = calculate_lpips_given_paths(args.path1, args.path2, model, args.batch_size, paired.feed_options(args), dev)
+    return paired.finish_cli(args, res, result_lines(res, tag), ["lpips"], per_pair_csv, dev)
 
 
 if __name__ == "__main__":

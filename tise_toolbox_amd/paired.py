@@ -144,10 +144,7 @@ def result_from_sums(sums):
     for k, name in enumerate(METRICS):
         n, s, ss = sums[3 * k:3 * k + 3]
         if n > 0:
-            mean = s / n
-            with np.errstate(invalid="ignore"):
-                var = max(ss / n - mean * mean, 0.0) if np.isfinite(mean) else float("nan")
-            res[name], res[name + "_std"] = float(mean), float(np.sqrt(var))
+            res[name], res[name + "_std"] = mean_std_from_sums(n, s, ss)
     return res
 
 
@@ -293,87 +290,196 @@ def paired_from_files(files1, files2, ms_ssim=False, batch_size=50, options=None
                      loader_args={"ring": {"batch_size": 1, "group": batch_size}})
 
 
-def _evaluate(files1, files2, ms_ssim, batch_size, options, device):
-    """This rank's shard of the pairs -> (totals over all ranks, this rank's per-pair arrays, [lo, hi))."""
+# ---- the scaffold of a pair-metric CLI (this one, lpips.py, dists.py) -----------------------------------------------------
+def value_sums(values):
+    """(3,) float64 {n, sum, sum of squares}: additive over shards, an empty one included."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    return np.array([v.size, v.sum(), (v * v).sum()], dtype=np.float64)
+
+
+def mean_std_from_sums(n, s, ss):
+    """{n, sum, sum of squares}, n > 0 -> (mean, population standard deviation); an inf among the values makes the mean inf and the
+    std nan, as numpy's mean and std do."""
+    mean = s / n
+    with np.errstate(invalid="ignore"):
+        var = max(ss / n - mean * mean, 0.0) if np.isfinite(mean) else float("nan")
+    return float(mean), float(np.sqrt(var))
+
+
+def value_result(sums, name, what):
+    """value_sums' totals of a one-number metric -> {n, <name>, <name>_std}."""
+    sums = np.asarray(sums, dtype=np.float64)
+    if int(sums[0]) < 1:
+        raise RuntimeError(f"{what} needs at least one pair")
+    mean, std = mean_std_from_sums(*sums)
+    return {"n": int(sums[0]), name: mean, name + "_std": std}
+
+
+def value_csv(name, files1, files2, per):
+    """The --per-pair text of a one-number metric: the header and one line per pair."""
+    rows = [f"pair,file1,file2,h,w,{name}"]
+    for i, (f1, f2) in enumerate(zip(files1, files2)):
+        rows.append(f"{i},{f1},{f2},{int(per['h'][i])},{int(per['w'][i])},{float(per[name][i])!r}")
+    return "\n".join(rows) + "\n"
+
+
+def value_per_batch(name, fn):
+    """paired_from_files' per-batch hook of a one-number metric: ``fn(xs, ys)`` -> (n,) float64, not called on an empty shard."""
+    def per_batch(xs, ys):
+        return {name: fn(xs, ys) if len(xs) else np.zeros(0), "h": np.array([a.shape[0] for a in xs], dtype=np.int64),
+                "w": np.array([a.shape[1] for a in xs], dtype=np.int64)}
+    return per_batch
+
+
+def self_pair_files(path, n_pairs, seed=0):
+    """``n_pairs`` random pairs (draw_self_pairs) of ONE directory's sorted file list -> ([files[i]], [files[j]])."""
+    files = list_files(path)
+    idx = draw_self_pairs(len(files), n_pairs, seed)
+    return [files[i] for i in idx[:, 0]], [files[j] for j in idx[:, 1]]
+
+
+def evaluate_pairs(files1, files2, per_batch, sums_of, result_of, batch_size=50, options=None, device=None, ms_ssim=False):
+    """This rank's shard of the pairs -> ``result_of`` (totals over all ranks) with per_pair (this rank's arrays), files1, files2
+    and range [lo, hi).  ``sums_of``: per-pair arrays -> a float64 vector that is additive over shards."""
     rank, world, _ = tdist.env_world()
     lo, hi = tdist.shard_range(len(files1), rank, world)
-    per = paired_from_files(files1[lo:hi], files2[lo:hi], ms_ssim, batch_size, options, device)
+    per = paired_from_files(files1[lo:hi], files2[lo:hi], ms_ssim, batch_size, options, device, per_batch=per_batch)
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    acc = torch.from_numpy(metric_sums(per)).to(dev)
-    tdist.all_reduce_sum_(acc)                               # {n, sum, sum of squares} x 3 and the identical count: the only exchange
-    res = result_from_sums(acc.cpu().numpy())
+    acc = torch.from_numpy(sums_of(per)).to(dev)
+    tdist.all_reduce_sum_(acc)                               # {n, sum, sum of squares} per metric: the only exchange
+    res = result_of(acc.cpu().numpy())
     res["per_pair"], res["files1"], res["files2"], res["range"] = per, list(files1), list(files2), (lo, hi)
     return res
 
 
-def calculate_paired_given_paths(path1, path2, ms_ssim=False, batch_size=50, options=None, device=None):
-    """PSNR, SSIM and (``ms_ssim``) MS-SSIM of every pair of two directories (pair_files) -> dict: psnr, psnr_std, ssim, ssim_std,
-    [ms_ssim, ms_ssim_std,] n, identical; per_pair (this rank's arrays), files1, files2, range.  Under torchrun every rank
-    returns the totals."""
-    files1, files2 = pair_files(path1, path2)
-    return _evaluate(files1, files2, ms_ssim, batch_size, options, device)
-
-
-def calculate_self_pairs(path, n_pairs, seed=0, ms_ssim=False, batch_size=50, options=None, device=None):
-    """The diversity use: ``n_pairs`` random pairs (draw_self_pairs) of ONE directory's sorted file list, side one files[i], side
-    two files[j] -> calculate_paired_given_paths' dict (the diversity number is its ms_ssim: pass ``ms_ssim=True``)."""
-    files = list_files(path)
-    idx = draw_self_pairs(len(files), n_pairs, seed)
-    return _evaluate([files[i] for i in idx[:, 0]], [files[j] for j in idx[:, 1]], ms_ssim, batch_size, options, device)
-
-
-def parse_args(argv=None):
-    parser = argparse.ArgumentParser(description="PSNR, SSIM and MS-SSIM of image pairs")
+def add_pair_arguments(parser, seed_help, saved_file_help, after_path2=None, after_batch_size=None):
+    """The options every pair-metric CLI has, in the order of its --help; ``after_*``: callables that add the tool's own."""
     parser.add_argument("--path1", required=True, type=str, help="folder of originals (with --self-pairs: the one folder)")
     parser.add_argument("--path2", default=None, type=str, help="folder of reconstructions, paired by relative path without extension")
-    parser.add_argument("--ms-ssim", action="store_true", help="five-scale MS-SSIM as well (smaller side >= 176)")
+    if after_path2:
+        after_path2(parser)
     parser.add_argument("--self-pairs", default=0, type=int, help="N random pairs (i != j) of --path1 instead of two folders")
-    parser.add_argument("--seed", default=0, type=int, help="seed of the --self-pairs draw")
+    parser.add_argument("--seed", default=0, type=int, help=seed_help)
     parser.add_argument("--per-pair", default="", type=str, help="write one CSV line per pair here")
-    parser.add_argument("--saved_file", default="", type=str, help="write the result lines here as well")
+    parser.add_argument("--saved_file", default="", type=str, help=saved_file_help)
     parser.add_argument("--batch-size", default=50, type=int)
+    if after_batch_size:
+        after_batch_size(parser)
     parser.add_argument("--png-feed", default="ring", choices=["ring", "dataloader"])
     parser.add_argument("--jpeg-feed", default=None, choices=["native", "pillow"])
     parser.add_argument("--num-workers", default=0, type=int, help="image decode processes per side (0 = auto)")
     parser.add_argument("--gpu_id", default="0", type=str)
-    args = parser.parse_args(argv)
+
+
+def check_pair_arguments(parser, args):
     if args.self_pairs:
         if args.path2:
             parser.error("--self-pairs takes --path1 only")
     elif not args.path2:
         parser.error("give --path2, or --self-pairs N")
+
+
+def parse_model_pair_args(argv, description, flag, flag_help):
+    """The parser of a pair metric on VGG-16: the common options, --weights, ``flag`` (the head's file) and --synthetic-weights."""
+    def own(p):
+        p.add_argument("--weights", default="", type=str, help="torchvision VGG-16 state_dict (vgg16-397923af.pth)")
+        p.add_argument(flag, default="", type=str, help=flag_help)
+        p.add_argument("--synthetic-weights", action="store_true",
+                       help="seeded stand-in parameters: plumbing / throughput runs only (result lines are tagged)")
+    parser = argparse.ArgumentParser(description=description)
+    add_pair_arguments(parser, "seed of the --self-pairs draw and of the --synthetic-weights parameters",
+                       "write the result line here as well", after_batch_size=own)
+    args = parser.parse_args(argv)
+    check_pair_arguments(parser, args)
+    if args.synthetic_weights and (args.weights or getattr(args, flag[2:].replace("-", "_"))):
+        parser.error(f"--synthetic-weights and --weights / {flag} are mutually exclusive")
     return args
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def resolve_model_files(args, what, head_file, default_trunk, build_model, missing):
+    """-> (model, tag) of a pair metric on VGG-16.  The trunk file: --weights, else ``default_trunk`` if it exists; the head's
+    file has no default path.  Anything missing without --synthetic-weights is an error (``missing``), never a silent stand-in."""
+    from . import weights as tweights
+    if args.synthetic_weights:
+        tweights.warn_synthetic(what)
+        return build_model(synthetic=True, seed=args.seed), tweights.SYNTHETIC_TAG
+    trunk = args.weights or (default_trunk if os.path.exists(default_trunk) else "")
+    for path in (trunk, head_file):
+        if path and not os.path.exists(path):
+            raise RuntimeError("Invalid path: %s" % path)
+    if not trunk or not head_file:
+        raise RuntimeError(missing)
+    return build_model(trunk, head_file), ""
+
+
+def cli_device(args, tool):
+    """The device of this process (torchrun's local rank, else --gpu_id), made current."""
     if not torch.cuda.is_available():
-        raise _lib.TiseLibraryError("paired needs an MI355X: there is no CPU path")
+        raise _lib.TiseLibraryError(f"{tool} needs an MI355X: there is no CPU path")
     rank, world, local_rank = tdist.init_from_env()
     dev = torch.device(f"cuda:{local_rank}" if world > 1 else f"cuda:{args.gpu_id}")
     torch.cuda.set_device(dev)
-    options = feeds.Options(png_feed=args.png_feed, jpeg_feed=args.jpeg_feed, num_workers=args.num_workers)
-    if args.self_pairs:
-        res = calculate_self_pairs(args.path1, args.self_pairs, args.seed, args.ms_ssim, args.batch_size, options, dev)
-    else:
-        res = calculate_paired_given_paths(args.path1, args.path2, args.ms_ssim, args.batch_size, options, dev)
-    lines = result_lines(res)
+    return dev
+
+
+def feed_options(args):
+    return feeds.Options(png_feed=args.png_feed, jpeg_feed=args.jpeg_feed, num_workers=args.num_workers)
+
+
+def finish_cli(args, res, lines, columns, csv_of, dev):
+    """--per-pair (the ranks' rows of h, w and ``columns`` gathered, ``csv_of(files1, files2, arrays)`` written by rank 0),
+    --saved_file and the print."""
     if args.per_pair:
         per, (lo, hi) = res["per_pair"], res["range"]
-        cols = [np.arange(lo, hi, dtype=np.float64), per["h"], per["w"], per["psnr"], per["ssim"]] + ([per["ms_ssim"]] if args.ms_ssim else [])
+        names = ["h", "w"] + list(columns)
+        cols = [np.arange(lo, hi, dtype=np.float64)] + [per[c] for c in names]
         rows = tdist.all_gather_rows(torch.from_numpy(np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1)).to(dev)).cpu().numpy()
         if tdist.is_main():
-            allp = {"h": rows[:, 1], "w": rows[:, 2], "psnr": rows[:, 3], "ssim": rows[:, 4]}
-            if args.ms_ssim:
-                allp["ms_ssim"] = rows[:, 5]
             with open(args.per_pair, "w") as f:
-                f.write(per_pair_csv(res["files1"], res["files2"], allp))
+                f.write(csv_of(res["files1"], res["files2"], {c: rows[:, k + 1] for k, c in enumerate(names)}))
     if tdist.is_main():
         if args.saved_file:
             with open(args.saved_file, "w") as f:
                 f.write("\n".join(lines))                                  # no trailing newline, like cmmd --saved_file
         print("\n".join(lines))
     return res
+
+
+# ---- this CLI --------------------------------------------------------------------------------------------------------
+def _evaluate(files1, files2, ms_ssim, batch_size, options, device):
+    return evaluate_pairs(files1, files2, None, metric_sums, result_from_sums, batch_size, options, device, ms_ssim)
+
+
+def calculate_paired_given_paths(path1, path2, ms_ssim=False, batch_size=50, options=None, device=None):
+    """PSNR, SSIM and (``ms_ssim``) MS-SSIM of every pair of two directories (pair_files) -> dict: psnr, psnr_std, ssim, ssim_std,
+    [ms_ssim, ms_ssim_std,] n, identical; per_pair (this rank's arrays), files1, files2, range.  Under torchrun every rank
+    returns the totals."""
+    return _evaluate(*pair_files(path1, path2), ms_ssim, batch_size, options, device)
+
+
+def calculate_self_pairs(path, n_pairs, seed=0, ms_ssim=False, batch_size=50, options=None, device=None):
+    """The diversity use: ``n_pairs`` random pairs (draw_self_pairs) of ONE directory's sorted file list, side one files[i], side
+    two files[j] -> calculate_paired_given_paths' dict (the diversity number is its ms_ssim: pass ``ms_ssim=True``)."""
+    return _evaluate(*self_pair_files(path, n_pairs, seed), ms_ssim, batch_size, options, device)
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description="PSNR, SSIM and MS-SSIM of image pairs")
+    add_pair_arguments(parser, "seed of the --self-pairs draw", "write the result lines here as well", after_path2=lambda p: p.add_argument(
+        "--ms-ssim", action="store_true", help="five-scale MS-SSIM as well (smaller side >= 176)"))
+    args = parser.parse_args(argv)
+    check_pair_arguments(parser, args)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    dev = cli_device(args, "paired")
+    if args.self_pairs:
+        res = calculate_self_pairs(args.path1, args.self_pairs, args.seed, args.ms_ssim, args.batch_size, feed_options(args), dev)
+    else:
+        res = calculate_paired_given_paths(args.path1, args.path2, args.ms_ssim, args.batch_size, feed_options(args), dev)
+    return finish_cli(args, res, result_lines(res), ["psnr", "ssim"] + (["ms_ssim"] if args.ms_ssim else []), per_pair_csv, dev)
 
 
 if __name__ == "__main__":
