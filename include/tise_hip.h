@@ -726,6 +726,49 @@ int tise_stem_conv3x3s2_split_u8(const uint8_t* x_dev, const float* lut_dev, int
  * 4-byte aligned.  Same values as the entry point above to split-precision accuracy (not the same bits). */
 int tise_stem_conv3x3s2_split_u8_mfma(const uint8_t* x_dev, const float* lut_dev, int n, int h, int w, const void* wsplit_dev,
                                       const float* scale_dev, const float* bias_dev, void* out_dev, void* stream);
+/* ResNet (csrc/resnet.hip, csrc/conv_pipe.hip; tise_toolbox_amd/resnet_hip.py).  No counterpart in the reference, which has no
+ * residual network; tise_toolbox_amd/resnet_model.py is the definition.
+ *
+ * The stem: 3 -> 64 channels, 7 x 7, stride 2, ZERO padding 3 of the normalised input, on the matrix cores straight from the
+ * uint8 NHWC image (n, h, w, 3) and the 3 x 256 fp32 table lut_dev.  out_dev: split tensor (n, (h-1)/2+1, (w-1)/2+1, 64) =
+ * split(max(scale * conv + bias, 0)) with the range guard and ReLU of every other layer.  A tap outside the image contributes
+ * exactly 0 (not lut[c][0]); no byte outside [x_dev, x_dev + n h w 3) is read; x_dev may sit at any address.
+ * wsplit_dev: 28672 fp16 = [7 kh][2 s2][2 planes hi, lo][2 cout tiles t][64 lanes][8 j] of the BatchNorm-folded weights, each cout
+ * pre-scaled by a power of two: entry (kh, s2, plane, t, lane, j) is the weight of cout 32 t + lane % 32 at slot
+ * s = 16 s2 + 8 (lane / 32) + j of filter row kh, where slot s < 21 is tap (kw = s / 3, c = s % 3) and slots 21..31 are zero
+ * (K = 7 x 32 = 224).  scale_dev[64] undoes the pre-scaling, bias_dev[64]; wsplit / scale / bias / out 16-byte aligned.
+ * Three-term split scheme of tise_stem_conv3x3s2_split_u8_mfma; a fixed summation order per output element: the bits do not
+ * depend on the batch position or on a second call.
+ * TISE_ERR_INVALID_ARG: a NULL or misaligned pointer, n < 0, h or w < 1 (the entry's minimum is one pixel).
+ * TISE_ERR_UNSUPPORTED: n oh ow >= 2^31 - 256.  n == 0: TISE_OK, no HIP call. */
+int tise_stem_conv7x7s2_split_u8_mfma(const uint8_t* x_dev, const float* lut_dev, int n, int h, int w, const void* wsplit_dev,
+                                      const float* scale_dev, const float* bias_dev, void* out_dev, void* stream);
+/* The input of the same layer when it runs as a 32-channel tise_conv_split_f16 layer instead: (n, h, w, 3) uint8 at any address
+ * -> split tensor (n, h, w, 32), 16-byte aligned: channels 0..2 = lut[c][byte] in split form, channels 3..31 zero in both halves
+ * (tise_lpips_input_split on one contiguous batch).  TISE_ERR_INVALID_ARG: a NULL or misaligned pointer, n < 0, h or w < 1.
+ * TISE_ERR_UNSUPPORTED: n > 65535, h w > 2^27. */
+int tise_resnet_input_split(const uint8_t* x_dev, const float* lut_dev, int n, int h, int w, void* out_dev, void* stream);
+/* The end of a bottleneck block, split(max((raw + bias) + identity, 0)) on `pixels` pixels of C channels:
+ *   t = raw + bias                  raw_dev: fp32 NHWC (pixels, raw_ld), channels [raw_off, raw_off + C): tise_conv_split_f16's
+ *                                   mode-1 output (scale * conv, no bias); bias_dev: C fp32
+ *   u = hi + lo 2^-11 (exact)       id_split_dev: split tensor (pixels, id_ld), channels from id_off;  OR
+ *   u = id_raw + id_bias            id_raw_dev: fp32 NHWC (pixels, id_raw_ld) from id_raw_off, id_bias_dev: C fp32 (the downsample
+ *                                   convolution's mode-1 output).  Exactly one of id_split_dev / id_raw_dev is non-NULL.
+ *   v = t + u                       fp32, in this order, nothing fused
+ *   out = split(max(v, 0))          out_dev: split tensor (pixels, out_ld), channels from out_off
+ * The range guard is raised where v is NaN or |v| > 65504, tested before the max (a non-finite input cannot leave as 0 unseen).
+ * C % 8 == 0; split ld % 16 == 0, off % 8 == 0; fp32 ld % 4 == 0, off % 4 == 0; off + C <= ld; all pointers 16-byte aligned;
+ * out_dev equal to an input pointer is refused.  No atomics on values; the bits do not depend on the position in the batch.
+ * TISE_ERR_INVALID_ARG: any of the above.  TISE_ERR_UNSUPPORTED: pixels C / 8 >= 2^39.  pixels == 0: TISE_OK, no HIP call. */
+int tise_residual_relu_split_nhwc(const float* raw_dev, int64_t raw_ld, int raw_off, const float* bias_dev, const void* id_split_dev,
+                                  int64_t id_ld, int id_off, const float* id_raw_dev, int64_t id_raw_ld, int id_raw_off,
+                                  const float* id_bias_dev, int64_t pixels, int C, void* out_dev, int64_t out_ld, int out_off,
+                                  void* stream);
+/* 3 x 3 / stride 2 / padding 1 max-pool, padding ignored (-inf), of a channel slice of a split tensor into a channel slice of
+ * another: (n, h, w) -> (n, (h-1)/2+1, (w-1)/2+1).  Arguments and value arithmetic as tise_maxpool3s2_split_nhwc (the maximum of
+ * the exact fp32 values hi + lo 2^-11, split again).  C % 8 == 0, h, w >= 1, both tensors 16-byte aligned and distinct. */
+int tise_maxpool3s2p1_split_nhwc(const void* x_dev, int64_t x_ld, int x_off, int n, int h, int w, int C, void* out_dev,
+                                 int64_t out_ld, int out_off, void* stream);
 /* Global average of a split tensor (n, hw, C), C % 32 == 0 -> fp32 (n, C): AdaptiveAvgPool2d((1,1)) of the last block. */
 int tise_split_mean_nhwc(const void* x_dev, int n, int hw, int C, float* out_dev, void* stream);
 /* the same mean, also written as a split row (n, 2C) fp16 (layout above): the operand of the classifier layer, which runs

@@ -159,6 +159,13 @@ SIGNATURES = {
                                               c_void_p]),
     "tise_stem_conv3x3s2_split_u8_mfma": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                                    c_void_p, c_void_p]),
+    "tise_stem_conv7x7s2_split_u8_mfma": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p]),
+    "tise_resnet_input_split": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "tise_residual_relu_split_nhwc": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                               c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "tise_maxpool3s2p1_split_nhwc": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                              c_int64, c_int, c_void_p]),
     "tise_split_mean_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "tise_split_mean_both_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "tise_conv_split_f16": (c_int, [c_void_p, c_int, c_void_p]),

@@ -68,6 +68,7 @@ int tise_memcpy_h2d_async(void* dst_dev, const void* src_host, size_t bytes, voi
 int tise_internal_split_flag_conv_split(int* host_flag, void* stream);
 int tise_internal_split_flag_conv_pipe(int* host_flag, void* stream);
 int tise_internal_split_flag_trunk_ops(int* host_flag, void* stream);
+int tise_internal_split_flag_resnet(int* host_flag, void* stream);
 
 int tise_split_overflow_check(int* flag_host, void* stream) {
     if (!flag_host) return TISE_ERR_INVALID_ARG;
@@ -75,6 +76,7 @@ int tise_split_overflow_check(int* flag_host, void* stream) {
     int rc = tise_internal_split_flag_conv_split(flag_host, stream);
     if (rc == TISE_OK) rc = tise_internal_split_flag_conv_pipe(flag_host, stream);
     if (rc == TISE_OK) rc = tise_internal_split_flag_trunk_ops(flag_host, stream);
+    if (rc == TISE_OK) rc = tise_internal_split_flag_resnet(flag_host, stream);
     return rc;
 }
 

@@ -5,6 +5,7 @@
 //   conv_regw32_kernel   (configuration 34)  register-resident-weights sliding-window kernel for Cin = 32, 3x3, stride 1
 //                        (Conv2d_2a, Conv2d_2b)
 //   stem_mfma_u8_kernel                       Conv2d_1a (3 -> 32, 3x3 stride 2) straight from the uint8 pixels
+//   stem7_mfma_u8_kernel                      ResNet's conv1 (3 -> 64, 7x7 stride 2, zero padding 3) straight from the uint8 pixels
 //
 // Removed, with their measurements kept in profiles/ and DESIGN.md: round 1's 3-stage persistent kernels (configurations
 // 0-15, 40-47; within +-3 % of the default kernel); round 2's LDS-resident-weights window kernel (configuration 33; 1.05 ms
@@ -659,7 +660,154 @@ __global__ __launch_bounds__(256) void stem_mfma_u8_kernel(const uint8_t* __rest
 #undef STEM_ALIGN
 }
 
+// ------------------------------------------------------------------------------------------------
+// ResNet's stem (3 -> 64 channels, 7x7, stride 2, ZERO padding 3 of the normalised input) on the matrix cores, from the uint8
+// image.  As a 32-channel layer of the generic kernel it is 49 K-steps of which 29/32 multiply zeros (1.26 GMAC at 224 x 224 for
+// 118 MMAC of work).  Here K = 7 filter rows x 32 slots = seven K-steps: slot s < 21 of row kh is tap (kw = s / 3, c = s % 3),
+// slots 21..31 carry zero weights -- a filter row's 21 taps are 21 CONSECUTIVE bytes of an image row.
+//   tile        a workgroup of 8 waves owns 8 output rows x 32 output columns of one image; wave w = output row 8 g + w, lane
+//               (pixel = lane & 31, half = lane >> 5).  A wave's 32 pixels are consecutive output pixels of one row, so
+//               conv_epi's linear epilogue stores them (rows past the end of the output row are cut off through args.M).
+//   patch       the tile's input, 21 rows x 69 pixels x 3 bytes, is converted ONCE into LDS: one dword (hi | lo << 16) of the
+//               table value per byte, 0 for a byte outside the image (that IS the zero padding: a tap outside contributes
+//               exactly 0, not lut[c][0]).  One global byte load and one table gather per patch byte -- 0.3 M per 224 x 224 image
+//               against 1.8 M for a gather per tap and output pixel.  Only bytes inside the image are ever addressed, one at
+//               a time: no byte outside [x, x + n h w 3) is read and the base needs no alignment.
+//   A fragments per filter row 16 ds_read_b32 per lane: slot s of pixel ow sits 6 ow + s dwords into patch row 2 w + kh.  The
+//               slots >= 21 read the neighbouring pixel's (finite) values or the zero tail; their weights are zero.
+//   weights     57 KB, in LDS for the workgroup's life, packed by the host in fragment order (resnet_hip.pack_stem7_mfma):
+//               [kh][K half s2][plane hi / lo][cout tile t][lane][8]: a fragment read is 64 consecutive 16-byte pieces.
+// Three-term split scheme of stem_mfma_u8_kernel: main(b_hi, a_hi) + corr(b_lo, a_hi) + corr(b_hi, a_lo).  84 MFMAs (32x32x16),
+// 112 patch reads and 56 weight reads per wave and tile.  Range guard: conv_epi's, which also sees the pixels computed past the
+// end of an output row (convolutions of real neighbouring bytes: conservative, as for the grid kernels, common.h).
+constexpr int S7_PITCH = 208;                                  // dwords per patch row: 69 pixels x 3 = 207, + 1
+constexpr int S7_ROWS = 21;                                    // 2 * 8 + 5
+constexpr int S7_PATCH = S7_ROWS * S7_PITCH + 16;              // + the zero tail the last row's slots 21..31 reach into
+constexpr int S7_WBYTES = 7 * 2 * 2 * 2 * 64 * 16;             // 57344
+constexpr int S7_OFF_LUT = S7_WBYTES, S7_OFF_PATCH = S7_OFF_LUT + 3 * 256 * 4, S7_OFF_EPI = S7_OFF_PATCH + S7_PATCH * 4,
+              S7_OFF_STAGE = S7_OFF_EPI + 2048, S7_LDS = S7_OFF_STAGE + 8 * conv_epi::Staging<1>::BYTES;
+static_assert(S7_OFF_EPI % 16 == 0 && S7_LDS <= 160 * 1024, "stem 7x7 LDS layout");
+
+__global__ __launch_bounds__(512) void stem7_mfma_u8_kernel(const uint8_t* __restrict__ x, const float* __restrict__ lut,
+                                                            int N, int H, int W, const _Float16* __restrict__ wsp,
+                                                            const ConvArgs p, int groups, int chunks, long long ntiles) {
+    constexpr int STG = conv_epi::Staging<1>::BYTES;
+    extern __shared__ __attribute__((aligned(16))) unsigned char s7_smem[];
+    u32x4_t* wl = reinterpret_cast<u32x4_t*>(s7_smem);
+    unsigned* lut2 = reinterpret_cast<unsigned*>(s7_smem + S7_OFF_LUT);
+    unsigned* patch = reinterpret_cast<unsigned*>(s7_smem + S7_OFF_PATCH);
+    unsigned char* epi = s7_smem + S7_OFF_EPI;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int i = tid; i < S7_WBYTES / 16; i += 512) wl[i] = reinterpret_cast<const u32x4_t*>(wsp)[i];
+    for (int i = tid; i < 3 * 256; i += 512) {
+        const float v = lut[i];
+        const _Float16 hi = (_Float16)v;
+        const _Float16 lo = (_Float16)((v - (float)hi) * 2048.0f);
+        lut2[i] = (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
+    }
+    if (tid < 16) patch[S7_ROWS * S7_PITCH + tid] = 0u;
+    {
+        conv_epi::float4_t sc_pre = {0.f, 0.f, 0.f, 0.f}, bs_pre = {0.f, 0.f, 0.f, 0.f};
+        if (tid < 16) {
+            sc_pre = *reinterpret_cast<const conv_epi::float4_t*>(p.scale + 4 * tid);
+            bs_pre = *reinterpret_cast<const conv_epi::float4_t*>(p.bias + 4 * tid);
+        }
+        conv_epi::prepare<64>(p, epi, 0, sc_pre, bs_pre);
+    }
+    unsigned char* stage = s7_smem + S7_OFF_STAGE + wave * STG;
+    const int OH = p.OH, OW = p.OW;
+    const int px = lane & 31, half = lane >> 5;
+    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long long ng = tile / chunks;
+        const int chunk = (int)(tile - ng * chunks);
+        const long long n = ng / groups;
+        const int g = (int)(ng - n * groups);
+        const int ih0 = 16 * g - 3, iw0 = 64 * chunk - 3;     // the patch's first input row and column
+        __syncthreads();                                      // the tables (first tile) / the previous tile's fragment reads
+        for (int e = tid; e < S7_ROWS * S7_PITCH; e += 512) {
+            const int r = e / S7_PITCH, cb = e - r * S7_PITCH;
+            const int col = cb / 3, c = cb - 3 * col;
+            const int ih = ih0 + r, iw = iw0 + col;
+            unsigned v = 0u;
+            if (cb < 207 && ih >= 0 && ih < H && iw >= 0 && iw < W)
+                v = lut2[c * 256 + x[((n * H + ih) * W + iw) * 3 + c]];
+            patch[e] = v;
+        }
+        __syncthreads();
+        const int oh = 8 * g + wave;
+        if (oh >= OH) continue;                               // wave-uniform; the barriers are at the top of the loop
+        float16_t acc_main[1][2], acc_corr[1][2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) { acc_main[0][t][j] = 0.f; acc_corr[0][t][j] = 0.f; }
+        const unsigned* prow = patch + (2 * wave) * S7_PITCH + 6 * px + 8 * half;
+#pragma unroll
+        for (int kh = 0; kh < 7; ++kh) {
+            unsigned wv[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) wv[u] = prow[kh * S7_PITCH + (u >> 3) * 16 + (u & 7)];
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                u32x4_t ah, al;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const unsigned w0 = wv[s2 * 8 + 2 * q], w1 = wv[s2 * 8 + 2 * q + 1];
+                    ah[q] = __builtin_amdgcn_perm(w1, w0, 0x05040100u);     // hi halves of slots 2q, 2q + 1
+                    al[q] = __builtin_amdgcn_perm(w1, w0, 0x07060302u);     // lo halves
+                }
+                const half8_t a_hi = __builtin_bit_cast(half8_t, ah), a_lo = __builtin_bit_cast(half8_t, al);
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const half8_t b_hi = __builtin_bit_cast(half8_t, wl[(((kh * 2 + s2) * 2 + 0) * 2 + t) * 64 + lane]);
+                    const half8_t b_lo = __builtin_bit_cast(half8_t, wl[(((kh * 2 + s2) * 2 + 1) * 2 + t) * 64 + lane]);
+                    acc_corr[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b_lo, a_hi, acc_corr[0][t], 0, 0, 0);
+                    acc_main[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b_hi, a_hi, acc_main[0][t], 0, 0, 0);
+                    acc_corr[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b_hi, a_lo, acc_corr[0][t], 0, 0, 0);
+                }
+            }
+        }
+        const long long m0w = (n * OH + oh) * (long long)OW + 32 * chunk;
+        ConvArgs q = p;
+        const int left = OW - 32 * chunk;
+        q.M = m0w + (left < 32 ? left : 32);                  // the epilogue drops the tile rows past the end of the output row
+        conv_epi::store_tiles_desc<2, 1, false, 64>(q, acc_main, acc_corr, stage, epi, m0w);
+    }
+}
+
 }  // namespace
+
+extern "C" int tise_stem_conv7x7s2_split_u8_mfma(const uint8_t* x_dev, const float* lut_dev, int n, int h, int w, const void* wsplit_dev,
+                                                 const float* scale_dev, const float* bias_dev, void* out_dev, void* stream) {
+    if (!x_dev || !lut_dev || !wsplit_dev || !scale_dev || !bias_dev || !out_dev || n < 0 || h < 1 || w < 1 ||
+        (reinterpret_cast<uintptr_t>(lut_dev) & 3) || (reinterpret_cast<uintptr_t>(wsplit_dev) & 15) ||
+        (reinterpret_cast<uintptr_t>(scale_dev) & 15) || (reinterpret_cast<uintptr_t>(bias_dev) & 15) ||
+        (reinterpret_cast<uintptr_t>(out_dev) & 15))
+        return TISE_ERR_INVALID_ARG;
+    if (n == 0) return TISE_OK;
+    const int oh = (h - 1) / 2 + 1, ow = (w - 1) / 2 + 1;
+    const long long M = (long long)n * oh * ow;
+    if (M >= 0x7fffff00LL || h > 0x3fffff00 || w > 0x3fffff00) return TISE_ERR_UNSUPPORTED;
+    tise_conv_args a;
+    memset(&a, 0, sizeof(a));
+    a.scale = scale_dev; a.bias = bias_dev;
+    a.N = n; a.H = h; a.W = w; a.Cin = 3; a.KH = 7; a.KW = 7; a.SH = 2; a.SW = 2; a.PH = 3; a.PW = 3; a.OH = oh; a.OW = ow;
+    a.Cout = 64; a.K = 147; a.Kpad = 224; a.M = M; a.nseg = 1;
+    a.seg[0].c0 = 0; a.seg[0].c1 = 64; a.seg[0].dst = out_dev; a.seg[0].ld = 64; a.seg[0].off = 0; a.seg[0].mode = 0;
+    const int groups = (oh + 7) / 8, chunks = (ow + 31) / 32;
+    const long long ntiles = (long long)n * groups * chunks;
+    const int ncu = tise_cu_count();
+    const long long grid = ntiles < ncu ? ntiles : ncu;       // the weights and the tables are loaded once per workgroup
+    static std::atomic<unsigned long long> attr_set{0};
+    if (tise_first_use_on_this_device(attr_set))
+        TISE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(stem7_mfma_u8_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(stem7_mfma_u8_kernel, dim3((unsigned)grid), dim3(512), S7_LDS, (hipStream_t)stream, x_dev, lut_dev, n, h, w,
+                       reinterpret_cast<const _Float16*>(wsplit_dev), a, groups, chunks, ntiles);
+    TISE_LAUNCH_CHECK();
+    return TISE_OK;
+}
 
 extern "C" int tise_stem_conv3x3s2_split_u8_mfma(const uint8_t* x_dev, const float* lut_dev, int n, int h, int w, const void* wsplit_dev,
                                                  const float* scale_dev, const float* bias_dev, void* out_dev, void* stream) {

@@ -1363,3 +1363,119 @@ def dists_image_sums(xs, ys, out=None):
     table, _, _ = _pair_table(xs, ys, dev)
     _lib.call("tise_dists_image_sums_u8", _ptr(table), ctypes.c_int64(n), h, w, _ptr(out), _stream())
     return out
+
+
+# ---- ResNet (csrc/resnet.hip, the 7 x 7 stem of csrc/conv_pipe.hip; resnet_hip.py) --------------------------------------------
+
+def _require_u8_batch(x, fn):
+    _require_cuda(x)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3 or x.stride(3) != 1 or x.stride(2) != 3 \
+            or x.stride(1) != 3 * x.shape[2] or (x.shape[0] > 1 and x.stride(0) != 3 * x.shape[1] * x.shape[2]):
+        raise ValueError(f"{fn}: a dense (N,H,W,3) uint8 batch (got {tuple(x.shape)} {x.dtype}, strides {tuple(x.stride())})")
+
+
+def _require_table(lut, dev, fn):
+    _require_cuda(lut)
+    if lut.dtype != torch.float32 or lut.shape != (3, 256) or not lut.is_contiguous() or lut.device != dev:
+        raise ValueError(f"{fn}: the table must be (3,256) contiguous float32 on {dev}")
+
+
+def stem_conv7x7s2_supported(x):
+    """Whether tise_stem_conv7x7s2_split_u8_mfma takes this dense (N,H,W,3) uint8 batch: any address, H and W >= 1, fewer than
+    2^31 - 256 output pixels (the header's refusals, mirrored so that a caller can choose its route before any launch)."""
+    n, h, w, _ = x.shape
+    return h >= 1 and w >= 1 and n * ((h - 1) // 2 + 1) * ((w - 1) // 2 + 1) < 0x7fffff00
+
+
+def stem_conv7x7s2_split_u8(x, lut, wsplit, scale, bias, out=None):
+    """ResNet's stem on the matrix cores (tise_stem_conv7x7s2_split_u8_mfma): a dense (N,H,W,3) uint8 batch at any address and the
+    (3,256) table -> the split tensor (N,(H-1)//2+1,(W-1)//2+1,128) fp16 of max(scale conv + bias, 0), zero padding 3 of the table
+    values.  ``wsplit``: 28672 fp16 in the kernel's order (resnet_hip.pack_stem7_mfma), ``scale`` / ``bias``: 64 fp32."""
+    _require_u8_batch(x, "stem_conv7x7s2_split_u8")
+    _require_table(lut, x.device, "stem_conv7x7s2_split_u8")
+    n, h, w, _ = x.shape
+    if wsplit.dtype != torch.float16 or wsplit.numel() != 28672 or not wsplit.is_contiguous() or wsplit.device != x.device:
+        raise ValueError("stem_conv7x7s2_split_u8: wsplit must be 28672 contiguous float16 on the batch's device")
+    for t in (scale, bias):
+        if t.dtype != torch.float32 or t.shape != (64,) or not t.is_contiguous() or t.device != x.device:
+            raise ValueError("stem_conv7x7s2_split_u8: scale and bias must be 64 contiguous float32 on the batch's device")
+    oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    if out is None:
+        out = torch.empty((n, oh, ow, 128), dtype=torch.float16, device=x.device)
+    elif out.dtype != torch.float16 or out.shape != (n, oh, ow, 128) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"stem_conv7x7s2_split_u8: out must be ({n},{oh},{ow},128) contiguous float16 on {x.device}")
+    _lib.call("tise_stem_conv7x7s2_split_u8_mfma", _ptr(x), _ptr(lut), n, h, w, _ptr(wsplit), _ptr(scale), _ptr(bias), _ptr(out), _stream())
+    return out
+
+
+def resnet_input_split(x, lut, out=None):
+    """A dense (N,H,W,3) uint8 batch at any address and the (3,256) table -> the split tensor (N,H,W,64) fp16 a 32-channel first
+    layer reads (tise_resnet_input_split): channels 0..2 = lut[c][byte] in split form, channels 3..31 zero in both halves."""
+    _require_u8_batch(x, "resnet_input_split")
+    _require_table(lut, x.device, "resnet_input_split")
+    n, h, w, _ = x.shape
+    if out is None:
+        out = torch.empty((n, h, w, 64), dtype=torch.float16, device=x.device)
+    elif out.dtype != torch.float16 or out.shape != (n, h, w, 64) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"resnet_input_split: out must be ({n},{h},{w},64) contiguous float16 on {x.device}")
+    _lib.call("tise_resnet_input_split", _ptr(x), _ptr(lut), n, h, w, _ptr(out), _stream())
+    return out
+
+
+def resize_u8_filter_only(src_u8, out_hw, filter="bicubic"):
+    """(N,H,W,3) uint8 CUDA tensor -> the Pillow-exact resized uint8 image (N,oh,ow,3) for ``filter`` "bilinear" or "bicubic"
+    (tise_resize_u8 with no float output: the bytes ``resize_u8_lut(..., return_u8=True)`` returns)."""
+    _require_cuda(src_u8)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3:
+        raise ValueError("src_u8 must be (N,H,W,3) uint8")
+    oh, ow = (int(v) for v in out_hw)
+    src_u8 = _vertical_pass_first(src_u8.contiguous(), oh, filter)
+    n, h, w, _ = src_u8.shape
+    u8 = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=src_u8.device)
+    _lib.call("tise_resize_u8", _ptr(src_u8), n, h, w, None, oh, ow, 1, _IDENTITY_LUT.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+              _ptr(u8), _FILTERS[filter], _stream())
+    return u8
+
+
+def maxpool3s2p1_split(x, out=None, out_off=0, x_off=0, channels=None):
+    """max_pool2d(3, stride 2, padding 1) of ``channels`` channels from ``x_off`` of a split tensor (N,H,W,2C) into the channels from
+    ``out_off`` of a split tensor (N,(H-1)//2+1,(W-1)//2+1,2C') (tise_maxpool3s2p1_split_nhwc; default: all channels into a fresh
+    tensor).  The padding does not take part: an all-negative window keeps its largest value."""
+    return _pool_split("maxpool3s2p1_split", "tise_maxpool3s2p1_split_nhwc", 1, lambda s: (s - 1) // 2 + 1, x, out, out_off, x_off, channels)
+
+
+def residual_relu_split(raw, bias, identity, id_bias=None, out=None, raw_off=0, id_off=0, out_off=0, channels=None):
+    """The end of a bottleneck block (tise_residual_relu_split_nhwc): out = split(max((raw + bias) + u, 0)) in fp32, in that order.
+    ``raw``: fp32 (..., Cr) -- a convolution's mode-1 output -- channels from ``raw_off``; ``bias``: C fp32.  ``identity``: a split
+    tensor (..., 2 Ci) fp16 (u = hi + lo 2^-11, ``id_bias`` None) or fp32 (..., Ci) with ``id_bias`` (u = identity + id_bias),
+    channels from ``id_off``.  ``out``: a split tensor (..., 2 Co), channels from ``out_off`` (default: a fresh one of C channels).
+    The leading dimensions of the three tensors must agree.  The range guard is raised where the sum is NaN or beyond +-65504."""
+    _require_cuda(raw, bias, identity, id_bias, out)
+    if raw.dtype != torch.float32 or raw.dim() < 2 or not raw.is_contiguous():
+        raise ValueError("residual_relu_split: raw must be contiguous float32 (..., C)")
+    lead = tuple(raw.shape[:-1])
+    pixels = 1
+    for s in lead:
+        pixels *= int(s)
+    c = raw.shape[-1] - raw_off if channels is None else int(channels)
+    if bias.dtype != torch.float32 or bias.shape != (c,) or not bias.is_contiguous():
+        raise ValueError(f"residual_relu_split: bias must be {c} contiguous float32")
+    split_id = identity.dtype == torch.float16
+    if split_id == (id_bias is not None) or identity.dtype not in (torch.float16, torch.float32) or not identity.is_contiguous() \
+            or tuple(identity.shape[:-1]) != lead:
+        raise ValueError("residual_relu_split: identity is a contiguous split tensor (fp16, no id_bias) or fp32 with id_bias, of raw's "
+                         "leading dimensions")
+    if id_bias is not None and (id_bias.dtype != torch.float32 or id_bias.shape != (c,) or not id_bias.is_contiguous()):
+        raise ValueError(f"residual_relu_split: id_bias must be {c} contiguous float32")
+    if out is None:
+        out = torch.empty(lead + (2 * (out_off + c),), dtype=torch.float16, device=raw.device)
+    elif out.dtype != torch.float16 or tuple(out.shape[:-1]) != lead or not out.is_contiguous() or out.device != raw.device:
+        raise ValueError("residual_relu_split: out must be a contiguous split tensor of raw's leading dimensions on its device")
+    null = ctypes.c_void_p(None)
+    if split_id:
+        ids = (_ptr(identity), ctypes.c_int64(identity.shape[-1] // 2), int(id_off), null, ctypes.c_int64(0), 0, null)
+    else:
+        ids = (null, ctypes.c_int64(0), 0, _ptr(identity), ctypes.c_int64(identity.shape[-1]), int(id_off), _ptr(id_bias))
+    _lib.call("tise_residual_relu_split_nhwc", _ptr(raw), ctypes.c_int64(raw.shape[-1]), int(raw_off), _ptr(bias), *ids,
+              ctypes.c_int64(pixels), c, _ptr(out), ctypes.c_int64(out.shape[-1] // 2), int(out_off), _stream())
+    return out

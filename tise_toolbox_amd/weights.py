@@ -39,6 +39,8 @@ _KINDS = {
     "dinov2-vits14": ("DINOv2 ViT-S/14", lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "dinov2_vits14_pretrain.pth")]),
     "dinov2-vitb14": ("DINOv2 ViT-B/14", lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "dinov2_vitb14_pretrain.pth")]),
     "dinov2-vitl14": ("DINOv2 ViT-L/14", lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "dinov2_vitl14_pretrain.pth")]),
+    # the trunk of FD-SwAV (fd_swav), under the name torch.hub's facebookresearch/swav caches the released file (from memory: UNPINNED)
+    "swav-resnet50": ("SwAV ResNet-50 (800 epochs)", lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "swav_800ep_pretrain.pth.tar")]),
 }
 
 
