@@ -190,22 +190,15 @@ def encode_paths(model, paths, dev, batch, workers, feed, convert_first, finish,
     """The image loop embed_paths and cmmd.embed_image_dir share: ``finish(model.encode_image(batch))`` of the files ``paths``, in
     order, every file used -> (len(paths), model.out_dim) tensor of ``dtype``.  The images are preprocessed at the tower's
     own input resolution (``model.resolution``; 224 for a model that does not say) on both roads."""
-    out = []
     size = getattr(model, "resolution", 224)
     # a tower with a preprocessing of its own (dinov2_hip.HipDino) brings it along; the CLIP towers have none: clip's
     on_device = getattr(model, "preprocess_device", clip_model.preprocess_device)
     on_host = getattr(model, "preprocess", clip_model.preprocess)
 
-    def consume(loader):
-        out.clear()                                           # the DataLoader pass after a ring that met an odd file starts afresh
-        for x in loader:
-            # the ring delivers uint8 (the tower's preprocess on the device), the DataLoader's workers preprocessed fp32
-            f = model.encode_image((on_device(x, size) if x.dtype == torch.uint8 else x.to(dev)).half())
-            out.append(finish(f))
-    feeds.run(feeds.CLIP, paths, feeds.Options(png_feed=feed, num_workers=workers), consume, dev, batch, tdist.world_size(),
-              loader_args={"ring": {"batch_size": 1, "group": batch, "rgb_only": not convert_first},
-                           "dataloader": {"dataset": _Paths(paths, convert_first, size, on_host), "pin_memory": False, "collate": None}})
-    return torch.cat(out).contiguous() if out else torch.empty((0, getattr(model, "out_dim", 512)), dtype=dtype, device=dev)
+    def per_batch(x):       # the ring delivers uint8 (the tower's preprocess on the device), the DataLoader's workers preprocessed fp32
+        return finish(model.encode_image((on_device(x, size) if x.dtype == torch.uint8 else x.to(dev)).half()))
+    return feeds.encode_files(per_batch, paths, dev, batch, workers, feed, _Paths(paths, convert_first, size, on_host), not convert_first,
+                              getattr(model, "out_dim", 512), dtype)
 
 
 class _Paths(torch.utils.data.Dataset):

@@ -226,11 +226,7 @@ def main(argv=None):
     wpath, tag = tweights.resolve(args.weights, args.synthetic_weights, tweights.inception_kind(NETWORK))
     print([args.ref, args.sample])
     result = evaluate(args.ref, args.sample, wpath, args.batch_size, args.save_stats, args.seed, args.is_split_size, not args.no_prdc)
-    lines = result_lines(result, tag)
-    if args.saved_file:
-        with open(args.saved_file, "w") as f:
-            f.write("\n".join(lines))                                  # no trailing newline, like the other CLIs' --saved_file
-    print("\n".join(lines))
+    tdist.write_lines(result_lines(result, tag), args.saved_file)
     return result
 
 

@@ -24,7 +24,7 @@ import torch
 
 from . import device
 from .engine import require_gpu
-from .kid import _to_device_f32
+from .feature_space import rows_f32
 
 
 def _check_shapes(train, gen):
@@ -56,7 +56,7 @@ def _search(train, gen):
     _check_shapes(train, gen)
     require_gpu()
     dev = train.device if isinstance(train, torch.Tensor) and train.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    T, G = _to_device_f32(train, dev), _to_device_f32(gen, dev)
+    T, G = rows_f32(train, dev), rows_f32(gen, dev)
     knn = device.KnnManifold(dev)
     d2_gen, idx = knn.nearest(G, T)
     d2_train, _ = knn.nearest(T, T, exclude_diagonal=True)

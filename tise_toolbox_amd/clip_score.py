@@ -255,12 +255,7 @@ def main(argv=None):
         raise RuntimeError("real CLIP weights need the BPE vocabulary: pass --vocab bpe_simple_vocab_16e6.txt.gz")
     res = calculate_clip_score_given_paths(args.image_dir, args.captions, args.rp_input_file, args.tower, wpath, args.vocab, args.prefix,
                                            args.w, args.batch_size, args.seed, args.num_workers, args.png_feed, args.save_features)
-    lines = result_lines(res, args.tower, tag)
-    if tdist.is_main():
-        if args.saved_file:
-            with open(args.saved_file, "w") as f:
-                f.write("\n".join(lines))                                  # no trailing newline, like cmmd --saved_file
-        print("\n".join(lines))
+    tdist.write_lines(result_lines(res, args.tower, tag), args.saved_file)
     return res
 
 

@@ -44,16 +44,14 @@ PREPROCESSING is clip._transform as clip_model restates it: convert to RGB, bicu
 resolution (224 or 336), centre crop.  CMMD's own loader crops the centre square BEFORE the resize; the two are identical for
 square images and differ by a rounding of the crop window otherwise.
 
-Every image of a directory is used (no drop-last).  Under torchrun the files are sharded as contiguous index ranges, the rows
-gathered in walk order on every rank (dist.all_gather_rows, as the --kid path), and rank 0 prints and writes.
+Every image of a directory is used (no drop-last).  The run, the feature files and the shared options are feature_space.py's;
+this module holds the CMMD arithmetic, the towers' table and the description of their space (``space``).
 """
 import argparse
-import os
 
-import numpy as np
 import torch
 
-from . import _lib, device, dist as tdist, img_data, weights as tweights
+from . import device, dist as tdist, feature_space as fs
 
 SIGMA = 10.0
 GAMMA = 1 / (2 * SIGMA ** 2)
@@ -96,30 +94,17 @@ def normalize_rows(t):
     return t / t.norm(dim=-1, keepdim=True)
 
 
-def _width(f):
-    shape = tuple(f.shape)
-    if len(shape) != 2:
-        raise ValueError("features must be (rows, dims)")
-    return shape[1]
-
-
-def _to_device_f32(f, dev):
-    if isinstance(f, torch.Tensor):
-        return f.to(dev, torch.float32)
-    return torch.as_tensor(np.ascontiguousarray(f, dtype=np.float32), device=dev)
-
-
 def cmmd_from_features(f1, f2, unbiased=False, sigma=SIGMA):
     """CMMD x 1000 of two embedding sets (device tensors or numpy arrays, (n, dims), un-normalised) -> Python float.  The rows are
     widened to fp32 and normalised in fp32 on the device; ONE grouped launch of one group."""
-    if _width(f1) != _width(f2):
-        raise ValueError(f"feature widths differ: {_width(f1)} and {_width(f2)}")
+    if fs.width(f1) != fs.width(f2):
+        raise ValueError(f"feature widths differ: {fs.width(f1)} and {fs.width(f2)}")
     if not sigma > 0:
         raise ValueError(f"sigma must be positive (got {sigma})")
     from .engine import require_gpu
     require_gpu()
     dev = f1.device if isinstance(f1, torch.Tensor) and f1.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    x, y = normalize_rows(_to_device_f32(f1, dev)), normalize_rows(_to_device_f32(f2, dev))
+    x, y = normalize_rows(fs.rows_f32(f1, dev)), normalize_rows(fs.rows_f32(f2, dev))
     n, m = x.shape[0], y.shape[0]
     cmmd_from_sums((0.0, 0.0, 0.0), n, m, unbiased)                        # too few rows: say so before the launch
     s = device.GaussianMMD(dev, 1 / (2 * float(sigma) ** 2)).sums(x, y, [0, n], [0, m]).cpu().numpy()
@@ -132,93 +117,41 @@ def embed_image_dir(towers, path, dev, batch, workers=0, feed="ring"):
     rank.  The loop is RP_coco.embed_paths' (feeds.CLIP: the PNG ring + clip_model.preprocess_device, the DataLoader for a
     ragged directory); the fp16 rows of the tower are widened, not normalised."""
     from . import RP_coco
-    files = img_data.get_filenames(path)
-    rank, world, _ = tdist.env_world()
-    lo, hi = tdist.shard_range(len(files), rank, world)
-    rows = RP_coco.encode_paths(towers, files[lo:hi], dev, batch, workers, feed, True, lambda f: f.float(), torch.float32)
-    return tdist.all_gather_rows(rows)
+    return fs.embed_image_dir(lambda files: RP_coco.encode_paths(towers, files, dev, batch, workers, feed, True, lambda f: f.float(),
+                                                                 torch.float32), path)
 
 
-def clip_statistics(feats):
-    """(mu, sigma) of un-normalised fp32 rows -> fp64 numpy arrays: np.mean / np.cov (ddof 1) on the device."""
-    stats = device.StatsAccumulator(feats.shape[1], feats.device)
-    stats.update(feats)
-    mu, sigma = stats.finalize()
-    out = mu.cpu().numpy(), sigma.cpu().numpy()
-    stats.close()
-    return out
+def space(tower=TOWER, weights=None, seed=0):
+    """The space of one CLIP image tower (an unknown ``tower`` is refused here).  ``weights=None``: seeded stand-in parameters of
+    ``seed`` (RP_coco.build_towers)."""
+    dims, network, _ = tower_info(tower)
+
+    def build_tower(dev):
+        from . import RP_coco
+        return RP_coco.build_towers(weights, dev, tower, seed)[0]
+    return fs.Space("cmmd", network, dims, build_tower, embed_image_dir)
+
+
+clip_statistics = fs.statistics
 
 
 def save_features_npz(path, feats, mu, sigma, tower=TOWER):
     """The feature file of --save-features: ``features`` (fp32, un-normalised, walk order), ``mu``, ``sigma`` and the network tag
     of ``tower``."""
-    from . import fid_score
-    fid_score.save_stats_npz(path, mu, sigma, tower_info(tower)[1], feats)
+    fs.save_features_npz(path, feats, mu, sigma, tower_info(tower)[1])
 
 
 def load_features_npz(path, tower=TOWER):
-    """-> (features fp32 (n, dims), mu, sigma) of a file --save-features wrote under the SAME ``tower``.  A file of another
-    network or tower (or of none: an Inception {mu, sigma} file) and a file without the rows are refused."""
-    from . import fid_score
-    DIMS, NETWORK, _ = tower_info(tower)
-    with np.load(path, allow_pickle=True) as f:
-        tag = str(f["network"]) if "network" in f.files else None
-        if tag is None:
-            raise RuntimeError(f"{path}: no network tag: not a feature file of {NETWORK} (make one with cmmd --save-features)")
-        fid_score.check_stats_network(path, tag, NETWORK)
-        if "features" not in f.files:
-            raise RuntimeError(f"{path}: no 'features' array in this file, and CMMD needs the embedding rows; "
-                               "make the file with cmmd --save-features")
-        feats = np.ascontiguousarray(f["features"], dtype=np.float32)
-        if feats.ndim != 2 or feats.shape[1] != DIMS:
-            raise RuntimeError(f"{path}: features of shape {feats.shape}, expected (n, {DIMS})")
-        return feats, f["mu"][:], f["sigma"][:]
-
-
-def _side(path, towers, dev, batch_size, num_workers, feed, with_stats, tower=TOWER):
-    """-> (fp32 device rows, mu | None, sigma | None) of a directory or a feature file."""
-    if path.endswith(".npz"):
-        feats, mu, sigma = load_features_npz(path, tower)
-        return torch.as_tensor(feats, device=dev), mu, sigma
-    feats = embed_image_dir(towers(), path, dev, batch_size, num_workers, feed)
-    if feats.shape[0] == 0:
-        raise RuntimeError(f"no images under {path}")
-    mu, sigma = clip_statistics(feats) if with_stats else (None, None)
-    return feats, mu, sigma
+    dims, network, _ = tower_info(tower)
+    return fs.load_features_npz(path, network, dims, "cmmd")
 
 
 def _given_paths(paths, batch_size, weights, seed, num_workers, feed, unbiased, clip_fid, save_features, want_cmmd=True,
                  tower=TOWER):
-    tower_info(tower)                                                      # an unknown tower: say so before anything is read
-    for p in paths:
-        if not os.path.exists(p):
-            raise RuntimeError("Invalid path: %s" % p)
-    if not torch.cuda.is_available():
-        raise _lib.TiseLibraryError("cmmd needs an MI355X: there is no CPU path")
-    _lib.load()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    built = []
-
-    def towers():                                                          # two feature files need no tower at all
-        if not built:
-            built.append(_towers(weights, seed, dev, tower))
-        return built[0]
-    f1, m1, s1 = _side(paths[0], towers, dev, batch_size, num_workers, feed, clip_fid or bool(save_features), tower)
-    if save_features and tdist.is_main():
-        save_features_npz(save_features, f1, m1, s1, tower)
-    f2, m2, s2 = _side(paths[1], towers, dev, batch_size, num_workers, feed, clip_fid, tower)
-    value = cmmd_from_features(f1, f2, unbiased) if want_cmmd else None
-    fid = None
-    if clip_fid:
-        from . import fid_score
-        fid = float(fid_score.calculate_frechet_distance(m1, s1, m2, s2))
-    return value, fid
-
-
-def _towers(weights, seed, dev, tower=TOWER):
-    """RP_coco.build_towers for ``tower``: the file's parameters, or the seeded stand-ins (``weights`` None) of ``seed``."""
-    from . import RP_coco
-    return RP_coco.build_towers(weights, dev, tower, seed)[0]
+    """-> (CMMD | None, CLIP-FID | None).  Without ``clip_fid`` and ``save_features`` no statistics kernel runs."""
+    res = fs.given_paths(space(tower, weights, seed), paths, batch_size, num_workers, feed, save_features,
+                         want=["cmmd"] * bool(want_cmmd) + ["fd"] * bool(clip_fid), unbiased=unbiased)
+    return res.get("cmmd"), res.get("fd")
 
 
 def calculate_cmmd_given_paths(paths, batch_size=50, weights=None, seed=0, num_workers=0, feed="ring", unbiased=False,
@@ -243,45 +176,28 @@ def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="CMMD and CLIP-FID on a CLIP image tower (ViT-B/32, or the paper's ViT-L/14@336)")
     parser.add_argument("--tower", default=TOWER, choices=list(clip_model.CONFIGS),
                         help="ViT-B/32 (default; clean-fid's CLIP-FID tower) or ViT-L/14@336 (the tower of the published CMMD figures)")
-    parser.add_argument("--path1", type=str, required=True, help="reference images: a directory, or a feature file of --save-features")
-    parser.add_argument("--path2", type=str, required=True, help="generated images: a directory, or a feature file of --save-features")
-    parser.add_argument("--batch-size", type=int, default=50)
-    parser.add_argument("--weights", default=None, type=str, help="OpenAI CLIP state_dict (.pt) of the chosen tower; default: ~/.cache/clip/ViT-B-32.pt or ViT-L-14-336px.pt")
-    parser.add_argument("--synthetic-weights", action="store_true",
-                        help="seeded stand-in tower (plumbing / throughput only; results are tagged)")
-    parser.add_argument("--seed", default=0, type=int, help="seed of the stand-in parameters")
+    fs.add_arguments(parser, "paths batch weights", weights_help="OpenAI CLIP state_dict (.pt) of the chosen tower; default: "
+                     "~/.cache/clip/ViT-B-32.pt or ViT-L-14-336px.pt")
     parser.add_argument("--clip-fid", action="store_true", help="also report the Frechet distance of the un-normalised embeddings")
     parser.add_argument("--unbiased", action="store_true",
                         help="the paper's unbiased estimator instead of the published implementation's V-statistic")
-    parser.add_argument("--save-features", default="", type=str,
-                        help="write --path1's embeddings (fp32, un-normalised), mu, sigma and the network tag to this .npz")
-    parser.add_argument("--saved_file", default="", type=str, help="write the result lines here as well")
-    parser.add_argument("--png-feed", default="ring", choices=["ring", "dataloader"])
-    parser.add_argument("--num-workers", default=0, type=int, help="image decode processes (0 = auto)")
-    parser.add_argument("--gpu", default="0", type=str, help="GPU to use")
-    return parser.parse_args(argv)
+    fs.add_arguments(parser, "output", rows="embeddings (fp32, un-normalised)")
+    return parser.parse_args(argv)                             # --weights with --synthetic-weights: weights.resolve refuses it
 
 
 def main(argv=None):
     args = parse_args(argv)
-    if not torch.cuda.is_available():
-        raise _lib.TiseLibraryError("cmmd needs an MI355X: there is no CPU path")
-    rank, world, local_rank = tdist.init_from_env()
-    dev = torch.device(f"cuda:{local_rank}" if world > 1 else f"cuda:{args.gpu}")
-    torch.cuda.set_device(dev)
-    wpath, tag = tweights.resolve(args.weights, args.synthetic_weights, tower_info(args.tower)[2], f"CLIP {args.tower}")
+    _, network, kind = tower_info(args.tower)
+    wpath, tag = fs.start_cli(args, "cmmd", network, kind, f"CLIP {args.tower}")
     value, fid = _given_paths([args.path1, args.path2], args.batch_size, wpath, args.seed, args.num_workers, args.png_feed,
                               args.unbiased, args.clip_fid, args.save_features, tower=args.tower)
     lines = [f"CMMD ({args.tower}): {value}{tag}"]
     if args.clip_fid:
         lines.append(f"CLIP-FID ({args.tower}): {fid}{tag}")
-    if tdist.is_main():
-        if args.saved_file:
-            with open(args.saved_file, "w") as f:
-                f.write("\n".join(lines))                                  # no trailing newline, like fid_score --saved_file
-        print("\n".join(lines))
+    tdist.write_lines(lines, args.saved_file)
     return value, fid
 
 
 if __name__ == "__main__":
     tdist.run_cli(main)
+

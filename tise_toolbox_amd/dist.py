@@ -231,3 +231,13 @@ def barrier():
 
 def is_main():
     return (not (dist.is_available() and dist.is_initialized())) or dist.get_rank() == 0
+
+
+def write_lines(lines, saved_file=""):
+    """The end of a CLI: rank 0 writes the result lines to ``saved_file`` (if one is named) and prints them."""
+    if is_main():
+        text = "\n".join(lines)
+        if saved_file:
+            with open(saved_file, "w") as f:
+                f.write(text)                                              # no trailing newline, like fid_score --saved_file
+        print(text)

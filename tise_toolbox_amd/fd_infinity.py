@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, device
 from .engine import frechet_solver, require_gpu
-from .kid import _to_device_f32
+from .feature_space import rows_f32
 
 
 def fd_infinity_sizes(m, num_points=15):
@@ -66,7 +66,7 @@ def fd_infinity_from_features(ref, gen, num_points=15, seed=0):
         raise ValueError(f"{gen.shape[0]} generated rows give one subset size only: there is no line to fit")
     require_gpu()
     dev = ref.device if isinstance(ref, torch.Tensor) and ref.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    R, G = _to_device_f32(ref, dev), _to_device_f32(gen, dev)
+    R, G = rows_f32(ref, dev), rows_f32(gen, dev)
     d = R.shape[1]
     with torch.cuda.device(dev):
         stats = device.StatsAccumulator(d, dev)

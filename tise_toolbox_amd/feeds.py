@@ -183,3 +183,19 @@ def run(site, files, options, consume, device, batch_size, world=None, loader_ar
             raise RuntimeError(f"--png-feed ring under torchrun needs images of one size ({e}); use --png-feed dataloader") from e
         print(f"[tise] png feed: images of different sizes ({e}); falling back to the DataLoader path", file=sys.stderr)
     return attempt("dataloader")
+
+
+def encode_files(per_batch, files, device, batch_size, workers, feed, dataset, rgb_only, width, dtype):
+    """The image loop of the towers (site CLIP): ``per_batch(x)`` -> device rows of every loader batch of ``files``, in order, every
+    file used -> one (len(files), width) tensor of ``dtype``.  The ring delivers uint8 batches of the files' own size (``rgb_only``:
+    it takes plain RGB files only), the DataLoader what ``dataset`` -- the tower's preprocess in the workers -- returns."""
+    out = []
+
+    def consume(loader):
+        out.clear()                                           # the DataLoader pass after a ring that met an odd file starts afresh
+        for x in loader:
+            out.append(per_batch(x))
+    run(CLIP, files, Options(png_feed=feed, num_workers=workers), consume, device, batch_size, tdist.world_size(),
+        loader_args={"ring": {"batch_size": 1, "group": batch_size, "rgb_only": rgb_only},
+                     "dataloader": {"dataset": dataset, "pin_memory": False, "collate": None}})
+    return torch.cat(out).contiguous() if out else torch.empty((0, width), dtype=dtype, device=device)

@@ -22,6 +22,7 @@ import torch
 
 from . import device
 from .engine import require_gpu
+from .feature_space import rows_f32
 
 
 def subset_indices(n1, n2, subsets=100, subset_size=1000, seed=0):
@@ -42,22 +43,12 @@ def subset_indices(n1, n2, subsets=100, subset_size=1000, seed=0):
     return i1.reshape(-1), i2.reshape(-1), m
 
 
-def _to_device_f32(f, dev):
-    if isinstance(f, torch.Tensor):
-        t = f.to(dev, torch.float32)
-    else:
-        t = torch.as_tensor(np.ascontiguousarray(f, dtype=np.float32), device=dev)
-    if t.dim() != 2:
-        raise ValueError("features must be (rows, dims)")
-    return t
-
-
 def kid_from_features(f1, f2, subsets=100, subset_size=1000, seed=0):
     """KID of two feature sets (device tensors or numpy arrays, (n, dims)) -> (mean, std) as Python floats.
     All subsets go through ONE grouped launch with one index upload per side."""
     require_gpu()
     dev = f1.device if isinstance(f1, torch.Tensor) and f1.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    f1, f2 = _to_device_f32(f1, dev), _to_device_f32(f2, dev)
+    f1, f2 = rows_f32(f1, dev), rows_f32(f2, dev)
     if f1.shape[1] != f2.shape[1]:
         raise ValueError(f"feature widths differ: {f1.shape[1]} and {f2.shape[1]}")
     mmd = device.PolynomialMMD(dev)
@@ -76,7 +67,7 @@ def per_class_kid(feats1_sorted, offsets1, feats2_sorted, offsets2, names, min_c
     ``skipped`` lists the classes with fewer than ``min_count`` (at least 2) rows on a side."""
     require_gpu()
     dev = feats1_sorted.device if isinstance(feats1_sorted, torch.Tensor) and feats1_sorted.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    f1, f2 = _to_device_f32(feats1_sorted, dev), _to_device_f32(feats2_sorted, dev)
+    f1, f2 = rows_f32(feats1_sorted, dev), rows_f32(feats2_sorted, dev)
     o1, o2 = np.asarray(offsets1, dtype=np.int64), np.asarray(offsets2, dtype=np.int64)
     if o1.size != len(names) + 1 or o2.size != len(names) + 1:
         raise ValueError("offsets need one more entry than there are class names")

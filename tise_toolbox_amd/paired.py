@@ -412,12 +412,13 @@ def resolve_model_files(args, what, head_file, default_trunk, build_model, missi
     return build_model(trunk, head_file), ""
 
 
-def cli_device(args, tool):
-    """The device of this process (torchrun's local rank, else --gpu_id), made current."""
+def cli_device(args, tool, gpu="gpu_id"):
+    """The device of this process (torchrun's local rank, else the option ``gpu``: --gpu_id, or --gpu where a CLI spells it so),
+    made current."""
     if not torch.cuda.is_available():
         raise _lib.TiseLibraryError(f"{tool} needs an MI355X: there is no CPU path")
     rank, world, local_rank = tdist.init_from_env()
-    dev = torch.device(f"cuda:{local_rank}" if world > 1 else f"cuda:{args.gpu_id}")
+    dev = torch.device(f"cuda:{local_rank}" if world > 1 else f"cuda:{getattr(args, gpu)}")
     torch.cuda.set_device(dev)
     return dev
 
@@ -437,11 +438,7 @@ def finish_cli(args, res, lines, columns, csv_of, dev):
         if tdist.is_main():
             with open(args.per_pair, "w") as f:
                 f.write(csv_of(res["files1"], res["files2"], {c: rows[:, k + 1] for k, c in enumerate(names)}))
-    if tdist.is_main():
-        if args.saved_file:
-            with open(args.saved_file, "w") as f:
-                f.write("\n".join(lines))                                  # no trailing newline, like cmmd --saved_file
-        print("\n".join(lines))
+    tdist.write_lines(lines, args.saved_file)
     return res
 
 

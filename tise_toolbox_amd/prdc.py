@@ -33,7 +33,7 @@ import torch
 
 from . import device
 from .engine import require_gpu
-from .kid import _to_device_f32
+from .feature_space import rows_f32
 
 
 def refuse_nonfinite_rows(sides):
@@ -61,7 +61,7 @@ def prdc_from_features(real, fake, nearest_k=5):
         raise ValueError(f"feature widths differ: {real.shape[1]} and {fake.shape[1]}")
     require_gpu()
     dev = real.device if isinstance(real, torch.Tensor) and real.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    R, F = _to_device_f32(real, dev), _to_device_f32(fake, dev)
+    R, F = rows_f32(real, dev), rows_f32(fake, dev)
     knn = device.KnnManifold(dev)
     r2R, r2F = knn.radius2(R, k), knn.radius2(F, k)
     cnt, rec, prec = knn.counts(R, r2R, F, r2F)

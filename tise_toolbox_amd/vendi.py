@@ -21,7 +21,7 @@ import torch
 
 from . import device
 from .engine import frechet_solver, require_gpu
-from .kid import _to_device_f32
+from .feature_space import rows_f32
 
 GRAM_CHUNK = 8192            # rows widened to fp64 at a time in the d x d route
 
@@ -60,7 +60,7 @@ def vendi_eigenvalues(f, route=None):
     route = gram_route(f.shape[0], f.shape[1], route)
     require_gpu()
     dev = f.device if isinstance(f, torch.Tensor) and f.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    x = cmmd.normalize_rows(_to_device_f32(f, dev))
+    x = cmmd.normalize_rows(rows_f32(f, dev))
     n, d = x.shape
     bad = ~torch.isfinite(x).all(dim=1)
     count, first = torch.stack([bad.sum(), torch.where(bad, torch.arange(n, device=dev), n).min()]).cpu().tolist()
