@@ -782,6 +782,39 @@ int tise_split_mean_both_nhwc(const void* x_dev, int n, int hw, int C, float* ou
 int tise_split_tap_rows(const void* x_dev, int n, int hw, int C, int c0, int nc, float* out_dev, int64_t ld, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The head of counting alignment, CA (csrc/countseg.hip; tise_toolbox_amd/countseg_hip.py).  counting_alignment/CA.py:120-128 and
+ * :150-187 define the metric; its network (nest.modules.fc_resnet50(channels=240) under peak_response_mapping with the median
+ * filter) is restated from Cholakkal, Sun, Khan & Shao 2019, "Object Counting and Instance Segmentation with Image-level
+ * Supervision", and the PRM package of Zhou et al. 2018; tise_toolbox_amd/countseg_model.py is the plain torch module.
+ *
+ * mix_dev: the RAW fp32 result of the 1 x 1 mix convolution (tise_conv_split_f16 mode 1: scale * conv, no bias), NHWC
+ * (n, h, w, ld), channels [off, off + 2 P).  With T_k = fp32(mix_k + b_mix[k]), k < 2 P, per image, class c < C and pixel p:
+ *   M_c(p) = b_cls[c] + sum_{k < P} W_cls[c][k] T_k(p)          the class map          fp64, k ascending (each product is exact)
+ *   D_c(p) = b_den[c] + sum_{k < P} W_den[c][k] T_{P+k}(p)      the density map
+ *   p is a local maximum of M_c iff M_c(q) < M_c(p) for every 8-neighbour q inside the map before p in row-major order and
+ *     M_c(q) <= M_c(p) for every one after it (max_pool2d(3, stride 1, padding -inf) returns p's own index)
+ *   med = the value of ascending rank (h w - 1) / 2 of M_c (the lower median, torch.median); peaks = the local maxima >= med
+ *   conf[i][c]  = (sum over the peaks of M_c(p), row-major) / #peaks;  peaks[i][c] = #peaks (>= 1)
+ *   den[i][c]   = (sum_p D_c(p), row-major) / (h w)
+ *   a NaN anywhere in M_c: conf[i][c] = NaN, peaks[i][c] = 0; nothing else is touched.
+ * maps_dev: NULL, or fp64 (n, 2 C, h w): M_0 .. M_{C-1}, D_0 .. D_{C-1} of every image.  All comparisons on the fp64 values; no
+ * floating-point atomics; the same bits in any batch, position or call.  One launch; no workspace.
+ * b_mix_dev: 2 P fp32; w_cls_dev, w_den_dev: (C, P) fp32; b_cls_dev, b_den_dev: C fp32; conf_dev, den_dev: (n, C) fp64;
+ * peaks_dev: (n, C) int32.  mix_dev 16-byte aligned, ld % 4 == 0, off % 4 == 0, P % 4 == 0, off + 2 P <= ld; fp32 and int32 arrays
+ * 4-byte, fp64 arrays 8-byte aligned.
+ * TISE_ERR_INVALID_ARG: a NULL (but maps_dev) or misaligned pointer, n < 0, h or w < 1, P < 4, C < 1, the rules above.
+ * TISE_ERR_UNSUPPORTED, before any HIP call: h w > TISE_COUNTSEG_MAX_PIXELS (the maps of a class group stay in the LDS of one
+ * CU), P > TISE_COUNTSEG_MAX_WIDTH, C > TISE_COUNTSEG_MAX_CLASSES, n > TISE_COUNTSEG_MAX_IMAGES.  n == 0: TISE_OK, no HIP call. */
+#define TISE_COUNTSEG_MAX_PIXELS 1024
+#define TISE_COUNTSEG_MAX_WIDTH 1024
+#define TISE_COUNTSEG_MAX_CLASSES 4096
+#define TISE_COUNTSEG_MAX_IMAGES 65535
+#define TISE_COUNTSEG_CLASS_GROUP 4   /* classes of one image per workgroup */
+int tise_countseg_head(const float* mix_dev, int64_t ld, int off, const float* b_mix_dev, const float* w_cls_dev,
+                       const float* b_cls_dev, const float* w_den_dev, const float* b_den_dev, int64_t n, int h, int w, int P, int C,
+                       double* conf_dev, double* den_dev, int* peaks_dev, double* maps_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * (a11, section 8 f3) Top-1 text retrieval for R-precision and the 2-way softmax test of PA.
  * Replaces the tail of the per-item loop of text_relevance/RP_coco.py:72-78 (logits_per_image ->
  * softmax -> argmax == 0) and positional_alignment/PA.py:37-42 (softmax[0] > 0.6) for n items at once.

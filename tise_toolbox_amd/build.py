@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtise_hip.so")
-SOURCES = ["capi.hip", "stats.hip", "resize.hip", "resize_f32.hip", "resize_tf1.hip", "resize_torch.hip", "is_score.hip", "frechet.hip", "trunk_ops.hip", "conv_split.hip", "conv_pipe.hip", "retrieval.hip", "clip_ops.hip", "png_unfilter.hip", "calibrate.hip", "jpeg_idct.hip", "mmd.hip", "knn.hip", "ssim.hip", "lpips.hip", "dists.hip", "resnet.hip"]
+SOURCES = ["capi.hip", "stats.hip", "resize.hip", "resize_f32.hip", "resize_tf1.hip", "resize_torch.hip", "is_score.hip", "frechet.hip", "trunk_ops.hip", "conv_split.hip", "conv_pipe.hip", "retrieval.hip", "clip_ops.hip", "png_unfilter.hip", "calibrate.hip", "jpeg_idct.hip", "mmd.hip", "knn.hip", "ssim.hip", "lpips.hip", "dists.hip", "resnet.hip", "countseg.hip"]
 HEADERS = ["common.h", "gemm_tile.h", "rows_tile.h", "conv_epilogue.h", "resize_plan.h", "split_px.h", os.path.join("..", "..", "include", "tise_hip.h")]
 
 

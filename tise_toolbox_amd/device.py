@@ -1479,3 +1479,37 @@ def residual_relu_split(raw, bias, identity, id_bias=None, out=None, raw_off=0, 
     _lib.call("tise_residual_relu_split_nhwc", _ptr(raw), ctypes.c_int64(raw.shape[-1]), int(raw_off), _ptr(bias), *ids,
               ctypes.c_int64(pixels), c, _ptr(out), ctypes.c_int64(out.shape[-1] // 2), int(out_off), _stream())
     return out
+
+
+# ---- counting alignment (csrc/countseg.hip; countseg_hip.py) --------------------------------------------------------------------
+COUNTSEG_MAX_PIXELS, COUNTSEG_MAX_WIDTH, COUNTSEG_MAX_CLASSES, COUNTSEG_MAX_IMAGES, COUNTSEG_CLASS_GROUP = 1024, 1024, 4096, 65535, 4
+
+
+def countseg_head(mix, b_mix, w_cls, b_cls, w_den, b_den, off=0, want_maps=False):
+    """CountSeg's two branches and peak stimulation (tise_countseg_head) on ``mix``: the raw fp32 result (N,h,w,ld) of the mix
+    convolution (SplitConv mode 1: scale * conv, no bias), channels [off, off + 2P).  ``b_mix``: 2P fp32; ``w_cls`` / ``w_den``:
+    (C,P) fp32; ``b_cls`` / ``b_den``: C fp32.  -> (conf (N,C) fp64, den (N,C) fp64, peaks (N,C) int32[, maps (N,2C,h w) fp64: the
+    class maps, then the density maps]).  conf = the mean of the local maxima of a class map that reach its lower median, den = the
+    mean of a density map; a NaN in a class map gives conf NaN and 0 peaks for that image and class only.  h w <= 1024."""
+    _require_cuda(mix, b_mix, w_cls, b_cls, w_den, b_den)
+    if mix.dtype != torch.float32 or mix.dim() != 4 or not mix.is_contiguous():
+        raise ValueError(f"countseg_head: mix must be contiguous float32 (N,h,w,ld) (got {tuple(mix.shape)} {mix.dtype})")
+    n, h, w, ld = mix.shape
+    dev = mix.device
+    if w_cls.dim() != 2:
+        raise ValueError("countseg_head: w_cls must be (C,P) float32")
+    c, p = w_cls.shape
+    if h * w > COUNTSEG_MAX_PIXELS:
+        raise ValueError(f"countseg_head: at most {COUNTSEG_MAX_PIXELS} pixels per map (got {h} x {w})")
+    for name, t, shape in (("b_mix", b_mix, (2 * p,)), ("w_cls", w_cls, (c, p)), ("b_cls", b_cls, (c,)), ("w_den", w_den, (c, p)),
+                           ("b_den", b_den, (c,))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"countseg_head: {name} must be {shape} contiguous float32 on {dev}")
+    conf = torch.empty((n, c), dtype=torch.float64, device=dev)
+    den = torch.empty((n, c), dtype=torch.float64, device=dev)
+    peaks = torch.empty((n, c), dtype=torch.int32, device=dev)
+    maps = torch.empty((n, 2 * c, h * w), dtype=torch.float64, device=dev) if want_maps else None
+    _lib.call("tise_countseg_head", _ptr(mix), ctypes.c_int64(ld), int(off), _ptr(b_mix), _ptr(w_cls), _ptr(b_cls), _ptr(w_den),
+              _ptr(b_den), ctypes.c_int64(n), h, w, p, c, _ptr(conf), _ptr(den), _ptr(peaks),
+              _ptr(maps) if want_maps else ctypes.c_void_p(None), _stream())
+    return (conf, den, peaks, maps) if want_maps else (conf, den, peaks)

@@ -15,7 +15,7 @@ directory holding `methods/` and `results/` it behaves like the reference script
 
 Added for the build: `--collect NAME` writes `methods/NAME.json` from the result files this package's metric
 scripts save (`fid_score.py --saved_file`, `inception_score.py --saved_file`, the O-IS / O-FID forms), with
-`--set KEY=VALUE` for metrics produced elsewhere (SOA, CA, PA, RP) -- the wiring the reference leaves to hand
+`--set KEY=VALUE` for metrics produced elsewhere (SOA, PA) -- the wiring the reference leaves to hand
 editing (README.md:437-441).  Host bookkeeping only: nothing here touches the GPU.
 """
 import argparse
@@ -98,6 +98,7 @@ _RESULT_PATTERNS = {
     "IS*": r"\[Inception Score\]\s*mean:\s*([-+0-9.eE]+)",             # inception_score.py (coco form)
     "O-IS": r"^O-IS:\s*([-+0-9.eE]+)",                                 # object_centric_inception_score.py
     "RP": r"^R-precision:\s*([-+0-9.eE]+)",                            # RP_coco.py:85-90 form
+    "CA": r"^CA = ([-+0-9.eE]+)",                                      # CA.py --result_file
 }
 
 
@@ -136,12 +137,12 @@ def main(argv=None):
     ap.add_argument("--collect", metavar="NAME", default=None, help="write methods/NAME.json from result files")
     ap.add_argument("--fid", default=None); ap.add_argument("--ofid", default=None)
     ap.add_argument("--is", dest="is_file", default=None); ap.add_argument("--ois", default=None)
-    ap.add_argument("--rp", default=None)
+    ap.add_argument("--rp", default=None); ap.add_argument("--ca", default=None)
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE")
     args = ap.parse_args(argv)
     if args.collect:
         files = {k: v for k, v in (("FID", args.fid), ("O-FID", args.ofid), ("IS*", args.is_file), ("O-IS", args.ois),
-                                   ("RP", args.rp)) if v}
+                                   ("RP", args.rp), ("CA", args.ca)) if v}
         extra = dict(kv.split("=", 1) for kv in args.set)
         print(collect(args.collect, files, extra, args.methods_dir))
         return

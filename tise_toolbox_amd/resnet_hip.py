@@ -143,20 +143,21 @@ class HipResNet50:
         conv(x, [(0, 64, y, 0, 0)])
         return y
 
-    def _chunk(self, u8):
+    def _chunk_map(self, u8):
         x = device.maxpool3s2p1_split(self.stem_forward(u8))
         for blk in self.blocks:
             x = blk(x)
+        return x
+
+    def _chunk(self, u8):
+        x = self._chunk_map(u8)
         n, h, w, c2 = x.shape
         out = torch.empty((n, c2 // 2), dtype=torch.float32, device=self.dev)
         _lib.call("tise_split_mean_nhwc", ctypes.c_void_p(x.data_ptr()), n, h * w, c2 // 2, ctypes.c_void_p(out.data_ptr()),
                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         return out
 
-    @torch.no_grad()
-    def features_from_u8(self, batch):
-        """(n, H, W, 3) uint8 device batch of one size, H and W >= 32 -> (n, 2048) fp32.  Raises FloatingPointError when an
-        activation left the fp16 range of the split format."""
+    def _check_batch(self, batch):
         if not isinstance(batch, torch.Tensor) or batch.dtype != torch.uint8 or batch.dim() != 4 or batch.shape[3] != 3:
             raise ValueError(f"HipResNet50 takes a (n, H, W, 3) uint8 batch (got {tuple(getattr(batch, 'shape', ()))} "
                              f"{getattr(batch, 'dtype', type(batch).__name__)})")
@@ -164,13 +165,40 @@ class HipResNet50:
             raise _lib.TiseLibraryError("HipResNet50 runs on MI355X only: the batch is not on a HIP device")
         n, h, w, _ = batch.shape
         resnet_model.check_size(h, w)
+        return n, h, w
+
+    def _guard(self, n):
+        if n and device.read_split_overflow():
+            raise FloatingPointError("ResNet-50 trunk: an activation exceeded the fp16 range of the split-precision format "
+                                     "(|v| > 65504); the result is not usable")
+
+    @torch.no_grad()
+    def features_from_u8(self, batch):
+        """(n, H, W, 3) uint8 device batch of one size, H and W >= 32 -> (n, 2048) fp32.  Raises FloatingPointError when an
+        activation left the fp16 range of the split format."""
+        n, h, w = self._check_batch(batch)
         out = torch.empty((n, self.out_dim), dtype=torch.float32, device=self.dev)
         step = images_per_chunk(h, w, self.budget)
         for at in range(0, n, step):
             out[at:at + step] = self._chunk(batch[at:at + step].contiguous())
-        if n and device.read_split_overflow():
-            raise FloatingPointError("ResNet-50 trunk: an activation exceeded the fp16 range of the split-precision format "
-                                     "(|v| > 65504); the result is not usable")
+        self._guard(n)
+        return out
+
+    @torch.no_grad()
+    def map_from_u8(self, batch):
+        """(n, H, W, 3) uint8 device batch of one size, H and W >= 32 -> the last map as a split tensor (n, h, w, 4096), (h, w) =
+        resnet_model.output_hw(H, W): features_from_u8 without the mean (the trunk used fully convolutionally: countseg_hip.py), with
+        its chunking, budget and guard."""
+        n, h, w = self._check_batch(batch)
+        oh, ow = resnet_model.output_hw(h, w)
+        step = images_per_chunk(h, w, self.budget)
+        if 0 < n <= step:                                                   # one chunk: its map is the result
+            out = self._chunk_map(batch.contiguous())
+        else:
+            out = torch.empty((n, oh, ow, 2 * self.out_dim), dtype=torch.float16, device=self.dev)
+            for at in range(0, n, step):
+                out[at:at + step] = self._chunk_map(batch[at:at + step].contiguous())
+        self._guard(n)
         return out
 
 

@@ -196,6 +196,10 @@ class ResNet50(nn.Module):
 
     def forward(self, img, amax=None):
         """``amax``: a list that receives the largest |activation| of every layer's output."""
+        return self.feature_map(img, amax).mean((2, 3))
+
+    def feature_map(self, img, amax=None):
+        """The last map, (n, 2048, h, w) with (h, w) = output_hw(H, W): the trunk used fully convolutionally (countseg_model.py)."""
         x = self.network_input(img)
         x = F.relu(self.bn1(self.conv1(x)))
         if amax is not None:
@@ -203,7 +207,7 @@ class ResNet50(nn.Module):
         x = F.max_pool2d(x, 3, 2, 1)
         for _, blk in self.blocks():
             x = blk(x, amax)
-        return x.mean((2, 3))
+        return x
 
 
 def load_file(path):

@@ -41,6 +41,8 @@ _KINDS = {
     "dinov2-vitl14": ("DINOv2 ViT-L/14", lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "dinov2_vitl14_pretrain.pth")]),
     # the trunk of FD-SwAV (fd_swav), under the name torch.hub's facebookresearch/swav caches the released file (from memory: UNPINNED)
     "swav-resnet50": ("SwAV ResNet-50 (800 epochs)", lambda: [os.path.join(_torch_home(), "hub", "checkpoints", "swav_800ep_pretrain.pth.tar")]),
+    # the counter of counting alignment (CA), at the relative path counting_alignment/CA.py:139 loads
+    "countseg": ("CountSeg ResNet-50 (coco14.pt)", lambda: [os.path.join("weights", "coco14.pt")]),
 }
 
 
