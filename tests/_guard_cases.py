@@ -387,7 +387,9 @@ def _cases():
 CASES = {c.name: c for c in _cases()}
 assert len(CASES) == len(_cases())
 
-# the instances tests/test_gpu_trunk_launches.py lists as deliberately outside the product, in instance_of's form
+# the instances tests/test_gpu_trunk_launches.py lists as outside the Inception trunk, in instance_of's form.  The set describes that
+# trunk and stays as it is; it is not "outside the product": ("rowwin", 2, 0, 6, "") and ("rowwin", 4, 0, 5, "") are reached by
+# ResNet-50 (32 x 32 images; 96 x 96 and up) and audited in tests/test_gpu_resnet_launches.py
 OUTSIDE = {("fast", 1, 0, "tap"), ("fast", 2, 0, "block"), ("fast", 2, 16, "tap"), ("rowwin", 2, 0, 6, ""), ("rowwin", 4, 0, 5, ""),
            ("poolin", 2, "VT"), ("pipe34", 32, "padded", "plain")} | {("glds", tn, 0) for tn in (1, 2, 3, 4, 5)}
 

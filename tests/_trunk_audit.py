@@ -1,4 +1,5 @@
-"""Launch recorder and fp64 references for tests/test_gpu_trunk_launches.py (helper, no tests).
+"""Launch recorder and fp64 references for tests/test_gpu_trunk_launches.py (the Inception trunk) and
+tests/test_gpu_resnet_launches.py (the ResNet-50 and CountSeg routes: ``ResNetRefs``, ``check_resnet_launch``); helper, no tests.
 
 While a ``SplitTrunk`` forward runs, ``Recorder`` intercepts ``SplitConv.__call__`` with the integer ``code`` it hands to
 ``tise_conv_split_f16`` and every other ``tise_*`` entry point the trunk reaches through ``_lib.call``, and keeps the
@@ -15,6 +16,7 @@ imported from conv_split.py for the same reason.
 Nothing here touches a device at import time.
 """
 import contextlib
+import ctypes
 
 import torch
 import torch.nn.functional as F
@@ -36,9 +38,20 @@ KNOWN = {
     "tise_split_mean_nhwc": ((0,), (4,)),
     "tise_split_mean_both_nhwc": ((0,), (4, 5)),
     "tise_split_tap_rows": ((0,), (6,)),
+    # the ResNet-50 and CountSeg routes (resnet_hip.py, countseg_hip.py through device.py); positions as in include/tise_hip.h
+    "tise_stem_conv7x7s2_split_u8_mfma": ((0, 1), (8,)),
+    "tise_resnet_input_split": ((0, 1), (5,)),
+    "tise_maxpool3s2p1_split_nhwc": ((0,), (7,)),
+    "tise_residual_relu_split_nhwc": ((0, 4, 7), (13,)),         # raw, then the one identity that is not NULL: split or fp32
+    "tise_countseg_head": ((0,), (13, 14, 15)),
 }
 TAP = "tise_split_tap_rows"      # the one launch that comes from device.py (device._ptr), not from trunk.py (trunk._p)
 STEMS = ("tise_stem_conv3x3s2_split", "tise_stem_conv3x3s2_split_u8", "tise_stem_conv3x3s2_split_u8_mfma")
+STEM7 = "tise_stem_conv7x7s2_split_u8_mfma"
+INPUT_SPLIT = "tise_resnet_input_split"
+RESIDUAL = "tise_residual_relu_split_nhwc"
+HEAD = "tise_countseg_head"
+GUARD_READ = "tise_split_overflow_check"   # no launch: the read-and-clear of the range guard (device.read_split_overflow); counted, passed on
 
 
 # ---------------------------------------------------------------------------------------------------- split layout
@@ -74,24 +87,28 @@ def raw_mask(C, c0, c1, split, device):
 
 def bits(t):
     """The tensor's bit patterns (uninitialised memory may hold NaNs, which never compare equal as numbers)."""
-    return t.contiguous().view({2: torch.int16, 4: torch.int32, 1: torch.uint8}[t.element_size()])
+    return t.contiguous().view({2: torch.int16, 4: torch.int32, 1: torch.uint8, 8: torch.int64}[t.element_size()])
 
 
 # ------------------------------------------------------------------------------------------------------- recording
 class Launch:
     """One kernel launch: ``name``, the cloned ``inputs``, ``dsts`` = [(before, after)] per distinct destination tensor,
     and for a convolution ``conv`` (the SplitConv), ``segs`` = [(c0, c1, destination index, off, mode)], ``kw``, ``code``
-    and ``args`` (the ConvArgs fields as passed); for the others ``ints`` = the call's integer arguments by position.  The
-    tap also keeps ``inputs_after``: its input as the launch left it."""
+    and ``args`` (the ConvArgs fields as passed); for the others ``ints`` = the call's integer arguments by position
+    (``ctypes.c_int64`` ones too), ``ptrs`` = its pointer arguments by position (None = NULL; an input that is NULL is None in
+    ``inputs``) and ``read_ptrs`` = every input pointer that is not NULL.  The tap also keeps ``inputs_after``: its input as
+    the launch left it; the residual launch keeps ``flag``: the range guard read (and cleared) right after it."""
 
     def __init__(self, name):
         self.name = name
         self.inputs, self.dsts = [], []
         self.conv = self.segs = self.kw = self.code = self.args = None
-        self.ints = {}
+        self.ints, self.ptrs = {}, {}
         self.in_ptr = None
+        self.read_ptrs = None
         self.dst_ptrs = []
         self.inputs_after = None
+        self.flag = None
 
     def __repr__(self):
         if self.conv is not None:
@@ -123,6 +140,7 @@ class Recorder:
 
     def __init__(self, sync=None):
         self.launches = []
+        self.guard_reads = 0
         self._stack, self._tensors = [], {}
         self._sync = sync or torch.cuda.synchronize
 
@@ -182,6 +200,9 @@ class Recorder:
                 fr["launch"] = L
                 rec.launches.append(L)
                 return orig_lib(name, *args)
+            if name == GUARD_READ:
+                rec.guard_reads += 1
+                return orig_lib(name, *args)
             if name not in KNOWN:
                 raise AssertionError(f"the trunk reached {name}, which the launch recorder does not know")
             ins, outs = KNOWN[name]
@@ -191,13 +212,19 @@ class Recorder:
                 t = rec._tensors.get(args[i].value)
                 assert t is not None, (name, i)
                 return t
-            L.inputs = [rec._clone(tensor(i)) for i in ins]
+            L.ptrs = {i: v.value for i, v in enumerate(args) if isinstance(v, ctypes.c_void_p)}
+            L.inputs = [rec._clone(tensor(i)) if L.ptrs[i] is not None else None for i in ins]
             dst = [tensor(i) for i in outs]
             before = [rec._clone(t) for t in dst]
-            L.ints = {i: v for i, v in enumerate(args) if isinstance(v, int)}
+            L.ints = {i: (v.value if isinstance(v, ctypes.c_int64) else v) for i, v in enumerate(args) if isinstance(v, (int, ctypes.c_int64))}
             L.in_ptr, L.dst_ptrs = args[ins[0]].value, [t.data_ptr() for t in dst]
+            L.read_ptrs = [L.ptrs[i] for i in ins if L.ptrs[i] is not None]
             r = orig_lib(name, *args)
             L.dsts = [(b, rec._clone(t)) for b, t in zip(before, dst)]
+            if name == RESIDUAL:                                  # its guard, by itself: the flag is clear, so reading it changes nothing
+                flag = ctypes.c_int(0)
+                orig_lib(GUARD_READ, ctypes.byref(flag), args[-1])
+                L.flag = bool(flag.value)
             if name == TAP:
                 L.inputs_after = [rec._clone(tensor(i)) for i in ins]
             rec.launches.append(L)
@@ -231,11 +258,12 @@ def _untouched(L, di, own):
     assert bool((same | own).all()), f"{L!r}: destination {di} changed outside the launch's own slice"
 
 
-def conv_reference(L):
+def conv_reference(L, wb=None):
     """fp64 NHWC (linear, relu(linear + bias), output scale) of a recorded convolution launch from the launch's own input;
-    the activated result is on the grid of the destinations (pooled for pool_output / pool_h)."""
+    the activated result is on the grid of the destinations (pooled for pool_output / pool_h).  ``wb``: the layer's original
+    fp64 (weight, bias) where the caller has them from the module itself (default: what keep_weights kept)."""
     c, kw = L.conv, L.kw
-    w, b = c._audit_wb
+    w, b = wb if wb is not None else c._audit_wb
     x = _nchw(merge64(L.inputs[0]))
     pin = kw.get("pooled_input")
     if pin == "v":
@@ -253,13 +281,18 @@ def conv_reference(L):
     return _nhwc(lin), _nhwc(act), scale
 
 
-def check_conv(L, fc=False):
-    """Returns the launch's largest error as a fraction of its output scale (asserted <= the tolerance)."""
+def check_conv(L, fc=False, raw=False, wb=None):
+    """Returns the launch's largest error as a fraction of its output scale (asserted <= the tolerance).  ``raw``: a launch
+    whose every segment is mode 1 and whose bias is its consumer's (a bottleneck's conv3 and downsample, CountSeg's mix):
+    conv2d(x, w) at CONV_TOL of max|conv2d(x, w)|, as tests/test_gpu_resnet_kernels.py compares it."""
     kw = L.kw
-    lin, act, scale = conv_reference(L)
+    lin, act, scale = conv_reference(L, wb)
     tol = CONV_TOL
     if fc:                                                        # raw logits: of the logit scale
         tol, scale = FC_TOL, lin.abs().max().item()
+    if raw:
+        assert all(sg[4] == 1 for sg in L.segs), f"{L!r}: a split segment in a launch checked as raw"
+        scale = lin.abs().max().item()
     pooled = bool(kw.get("pool_output") or kw.get("pool_h"))
     out_pad = kw.get("out_pad")
     n, gh, gw = act.shape[:3]
@@ -332,7 +365,10 @@ def check_pool(L):
         want = torch.relu(F.avg_pool2d(raw, 3, 1, 1, count_include_pad="excl" not in L.name) + L.inputs[1].double().view(1, -1, 1, 1))
     else:
         xin = _nchw(merge64(x)[..., x_off:x_off + C])
-        want = F.max_pool2d(xin, 3, 2) if "3s2" in L.name else F.max_pool2d(xin, 3, 1, 1)      # max_pool2d pads with -inf
+        if "3s2p1" in L.name:
+            want = F.max_pool2d(xin, 3, 2, 1)
+        else:
+            want = F.max_pool2d(xin, 3, 2) if "3s2" in L.name else F.max_pool2d(xin, 3, 1, 1)  # max_pool2d pads with -inf
     want = _nhwc(want)
     assert tuple(after.shape[:3]) == tuple(want.shape[:3])
     got = merge64(after)[..., out_off:out_off + C]
@@ -434,6 +470,214 @@ def check_launch(L, trunk):
     return "mean", check_mean(L)
 
 
+# ------------------------------------------------------------------------- the ResNet-50 and CountSeg routes
+def split_halves(x):
+    """fp32 (..., C) -> (hi, lo) fp16 of the split format: hi = fp16(x), lo = fp16((x - hi) * 2**11), both round-to-nearest-even."""
+    hi = x.half()
+    return hi, ((x - hi.float()) * 2048.0).half()
+
+
+def _bits_equal(got, want, what):
+    bad = bits(got) != bits(want)
+    assert not bool(bad.any()), f"{what}: {int(bad.sum())} of {bad.numel()} values differ (first at {tuple(int(v) for v in bad.nonzero()[0])})"
+
+
+class ResNetRefs:
+    """Where the ResNet-50 / CountSeg references take their parameters from: ``model.folded()`` (a resnet_model.ResNet50) and
+    the head's own module (a countseg_model.CountSeg) -- never the kernels' packed forms.  ``tower`` (the HipResNet50 under
+    audit) and ``counter`` (the HipCountSeg, or None) only say which SplitConv instance is which layer."""
+
+    def __init__(self, model, tower, dev, counter=None, head=None):
+        self.dev, self.tower, self.counter, self.head = dev, tower, counter, head
+        self.folded = {k: (w.to(dev), b.to(dev)) for k, (w, b) in model.folded().items()}      # fp32, as resnet_hip.py receives them
+        self.table = model.table.detach().float().to(dev)
+        self.blocks = [name for name, _ in model.blocks()]
+
+    def owners(self):
+        """[(layer name, SplitConv)] of the tower as it stands (the padded stem exists once that route has run)."""
+        t = self.tower
+        out = [("conv1", t._stem_padded)] if t._stem_padded is not None else []
+        for name, blk in zip(self.blocks, t.blocks):
+            out += [(f"{name}.conv1", blk.conv1), (f"{name}.conv2", blk.conv2), (f"{name}.conv3", blk.conv3)]
+            if blk.down is not None:
+                out.append((f"{name}.downsample.0", blk.down))
+        if self.counter is not None:
+            out.append(("mix", self.counter.mix))
+        return out
+
+    def layer_of(self, conv):
+        """(layer name, whether ``conv`` is that layer's ``_fallback``) of the SplitConv a launch came from."""
+        for name, c in self.owners():
+            if conv is c or conv is c._fallback:
+                return name, conv is not c
+        raise AssertionError("a convolution launch from a SplitConv that is no layer of the tower")
+
+    def wb(self, layer):
+        """fp64 (weight, bias) of the layer as its SplitConv received them: conv1 with 29 zero input channels, mix with a zero bias."""
+        if layer == "mix":
+            w = self.head.mix.weight.detach().double().to(self.dev)
+            return w, torch.zeros(w.shape[0], dtype=torch.float64, device=self.dev)
+        w, b = (t.double() for t in self.folded[layer])
+        if layer == "conv1":
+            w = torch.cat([w, torch.zeros((64, 29, 7, 7), dtype=torch.float64, device=self.dev)], 1)
+        return w, b
+
+
+def _table_values(u8, lut):
+    """(n, h, w, 3) uint8 and the (3, 256) table -> fp32 (n, h, w, 3)."""
+    return torch.stack([lut.view(3, 256)[ch][u8[..., ch].long()] for ch in range(3)], -1)
+
+
+def check_stem7(L, refs):
+    i = L.ints
+    n, h, wd = i[2], i[3], i[4]
+    u8, lut = L.inputs
+    assert u8.dtype == torch.uint8 and tuple(u8.shape) == (n, h, wd, 3) and lut.numel() == 768
+    _bits_equal(lut.reshape(-1), refs.table.reshape(-1), f"{L!r}: the table")
+    w, b = (t.double() for t in refs.folded["conv1"])
+    want = _nhwc(torch.relu(F.conv2d(_nchw(_table_values(u8, lut).double()), w, b, 2, 3)))
+    before, after = L.dsts[0]
+    assert tuple(after.shape) == (*want.shape[:3], 128), (L, after.shape, want.shape)
+    scale = want.abs().max().item()
+    err = (merge64(after) - want).abs().max().item()
+    assert err <= CONV_TOL * scale, f"{L!r}: error {err:.3e} > {CONV_TOL:g} x scale {scale:.3e}"
+    return err / scale
+
+
+def check_input_split(L, refs):
+    """tise_resnet_input_split: channels 0..2 the split of the table values, channels 3..31 +0 in both halves; bit for bit."""
+    i = L.ints
+    n, h, wd = i[2], i[3], i[4]
+    u8, lut = L.inputs
+    assert u8.dtype == torch.uint8 and tuple(u8.shape) == (n, h, wd, 3) and lut.numel() == 768
+    _bits_equal(lut.reshape(-1), refs.table.reshape(-1), f"{L!r}: the table")
+    x = torch.zeros((n, h, wd, 32), dtype=torch.float32, device=u8.device)
+    x[..., :3] = _table_values(u8, lut)
+    hi, lo = split_halves(x)
+    after = L.dsts[0][1]
+    assert tuple(after.shape) == (n, h, wd, 64) and after.dtype == torch.float16
+    ih, il = split_index(32, after.device)
+    _bits_equal(after[..., ih], hi, f"{L!r}: hi halves")
+    _bits_equal(after[..., il], lo, f"{L!r}: lo halves")
+    return 0.0
+
+
+def check_residual(L, refs, block):
+    """tise_residual_relu_split_nhwc of block number ``block``: fp32 torch operations in the kernel's order, (raw + bias) + u,
+    relu, split; u = the merged identity or id_raw + id_bias.  Bit for bit; the range guard is clear after the launch."""
+    i, p = L.ints, L.ptrs
+    raw_ld, raw_off, pixels, C, out_ld, out_off = i[1], i[2], i[11], i[12], i[14], i[15]
+    name = refs.blocks[block]
+    assert (p[4] is None) != (p[7] is None), f"{L!r}: exactly one identity"
+    assert (p[7] is not None) == (f"{name}.downsample.0" in refs.folded) == (p[10] is not None), f"{L!r}: the identity of {name}"
+    raw = L.inputs[0]
+    assert raw.dtype == torch.float32 and raw.numel() == pixels * raw_ld
+    t = raw.reshape(pixels, raw_ld)[:, raw_off:raw_off + C] + refs.folded[f"{name}.conv3"][1]
+    if p[4] is not None:
+        ids, id_ld, id_off = L.inputs[1], i[5], i[6]
+        assert ids.dtype == torch.float16 and ids.numel() == pixels * 2 * id_ld
+        u = merge64(ids.reshape(pixels, 2 * id_ld))[:, id_off:id_off + C].float()          # hi + lo 2^-11 is exact in fp32
+    else:
+        idr, id_ld, id_off = L.inputs[2], i[8], i[9]
+        assert idr.dtype == torch.float32 and idr.numel() == pixels * id_ld
+        u = idr.reshape(pixels, id_ld)[:, id_off:id_off + C] + refs.folded[f"{name}.downsample.0"][1]
+    hi, lo = split_halves(torch.relu(t + u))
+    before, after = L.dsts[0]
+    assert after.dtype == torch.float16 and after.numel() == pixels * 2 * out_ld and tuple(after.shape[:-1]) == tuple(raw.shape[:-1])
+    got = after.reshape(pixels, 2 * out_ld)
+    ih, il = split_index(out_ld, after.device)
+    _bits_equal(got[:, ih[out_off:out_off + C]], hi, f"{L!r} ({name}): hi halves")
+    _bits_equal(got[:, il[out_off:out_off + C]], lo, f"{L!r} ({name}): lo halves")
+    assert L.flag is False, f"{L!r} ({name}): the range guard is raised after the launch"
+    _untouched(L, 0, raw_mask(out_ld, out_off, out_off + C, True, after.device).view(*([1] * (after.dim() - 1)), -1))
+    return 0.0
+
+
+def check_head(L, refs):
+    """tise_countseg_head against tests/_countseg_ref.head on the launch's recorded fp32 map and the module's own parameters:
+    the confidences, the density means and the peak counts, bit for bit."""
+    import numpy as np
+    from tests import _countseg_ref as R
+    i = L.ints
+    ld, off, n, h, w, P, C = i[1], i[2], i[8], i[9], i[10], i[11], i[12]
+    assert L.ptrs[16] is None, f"{L!r}: the route asks for no maps"
+    mix = L.inputs[0]
+    assert mix.dtype == torch.float32 and tuple(mix.shape) == (n, h, w, ld) and off + 2 * P <= ld
+    m = refs.head
+    f32 = lambda t: t.detach().float().cpu().numpy()                                       # noqa: E731
+    assert (m.n_classes, m.width) == (C, P)
+    T = (mix.cpu().numpy()[..., off:off + 2 * P] + f32(m.mix.bias)).astype(np.float32)
+    conf, den, peaks, _ = R.head(T, f32(m.cls.weight).reshape(C, P), f32(m.cls.bias), f32(m.den.weight).reshape(C, P), f32(m.den.bias))
+    got = [d[1].cpu().numpy() for d in L.dsts]
+    assert got[0].shape == (n, C) and got[0].dtype == np.float64 and got[2].dtype == np.int32
+    assert np.array_equal(got[2], peaks), f"{L!r}: {int((got[2] != peaks).sum())} peak counts differ"
+    for g, r, what in ((got[0], conf, "confidences"), (got[1], den, "density means")):
+        bad = g.view(np.int64) != np.ascontiguousarray(r).view(np.int64)
+        assert not bad.any(), f"{L!r}: {int(bad.sum())} of {bad.size} {what} are not the restatement's bits (largest difference {np.abs(g - r).max():.3e})"
+    return 0.0
+
+
+def check_resnet_launch(L, refs, block=None):
+    """Dispatch on the launch's kind; returns (kind, figure).  ``block``: which bottleneck a residual launch ends."""
+    if L.conv is not None:
+        layer, _ = refs.layer_of(L.conv)
+        raw = layer == "mix" or layer.endswith((".conv3", ".downsample.0"))
+        assert raw == all(sg[4] == 1 for sg in L.segs), f"{L!r}: {layer} writes {'split' if raw else 'fp32'} segments"
+        return ("raw" if raw else "conv"), check_conv(L, raw=raw, wb=refs.wb(layer))
+    if L.name == STEM7:
+        return "stem", check_stem7(L, refs)
+    if L.name == INPUT_SPLIT:
+        return "input", check_input_split(L, refs)
+    if L.name == RESIDUAL:
+        return "residual", check_residual(L, refs, block)
+    if L.name == HEAD:
+        return "head", check_head(L, refs)
+    if "pool" in L.name:
+        return "pool", check_pool(L)
+    assert L.name == "tise_split_mean_nhwc", L.name
+    return "mean", check_mean(L)
+
+
+def module_convs(model, h, w):
+    """(Cin, Cout, kh, kw, sh, sw, ph, pw, OH, OW) of the 53 ``nn.Conv2d`` of a resnet_model.ResNet50 on an h x w image, in
+    launch order, by the size arithmetic alone: conv1, MaxPool2d(3, 2, 1), then per block conv1, conv2, conv3 and, where there
+    is one, the downsample convolution on the block's input."""
+    def member(c, h, w):
+        oh = (h + 2 * c.padding[0] - c.kernel_size[0]) // c.stride[0] + 1
+        ow = (w + 2 * c.padding[1] - c.kernel_size[1]) // c.stride[1] + 1
+        return (c.in_channels, c.out_channels, *c.kernel_size, *c.stride, *c.padding, oh, ow)
+    out = [member(model.conv1, h, w)]
+    h, w = out[-1][8:]
+    h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+    for _, blk in model.blocks():
+        out.append(member(blk.conv1, h, w))
+        out.append(member(blk.conv2, *out[-1][8:]))
+        out.append(member(blk.conv3, *out[-1][8:]))
+        if blk.downsample is not None:
+            out.append(member(blk.downsample[0], h, w))
+            assert out[-1][8:] == out[-2][8:]
+        h, w = out[-1][8:]
+    assert len(out) == sum(isinstance(m, torch.nn.Conv2d) for m in model.modules()) == 53
+    return out
+
+
+def resnet_dispatch(h, w):
+    """What conv_split.py's dispatch gives the 52 block convolutions of an h x w image, from pick_tn, rowwin_applies, rowwin_fits
+    and rowwin_divides alone (no device): ({(tn, window pieces): row-window launches}, {row width: launches that fall back to
+    the default kernel})."""
+    import collections
+    from tise_toolbox_amd import conv_split, resnet_model
+    rowwin, fallback = collections.Counter(), collections.Counter()
+    for cin, cout, kh, kw, sh, sw, ph, pw, oh, ow in module_convs(resnet_model.ResNet50(), h, w)[1:]:
+        tn = conv_split.pick_tn(cout)
+        if conv_split.rowwin_applies(cin, cout, kh, kw, (sh, sw), (ph, pw), tn):
+            if conv_split.rowwin_fits(ow, kw) and conv_split.rowwin_divides(ow, kw):
+                rowwin[(tn, rowwin_np(ow, kw))] += 1
+            else:
+                fallback[ow] += 1
+    return dict(rowwin), dict(fallback)
+
+
 # ------------------------------------------------------------------------------------- how the launches fit together
 def own_rows(L):
     """[(destination index, 1-D bool mask over the destination's raw row)]: the elements of a pixel's row the launch writes."""
@@ -451,6 +695,9 @@ def own_rows(L):
         i = L.ints
         out_ld, out_off = (i[9], i[10]) if "avgpool" in L.name else (i[8], i[9])
         return [(0, raw_mask(out_ld, out_off, out_off + i[6], True, dev))]
+    if L.name == RESIDUAL:
+        i = L.ints
+        return [(0, raw_mask(i[14], i[15], i[15] + i[12], True, dev))]
     return [(di, torch.ones(d[1].shape[-1], dtype=torch.bool, device=dev)) for di, d in enumerate(L.dsts)]
 
 
@@ -474,10 +721,13 @@ def check_assembly(launches):
             elif not bool(st[0][need].all()):
                 fails.append(f"launch {k}: tap {L!r} reads {int((~st[0][need]).sum())} raw row elements of channels "
                              f"[{i[4]}, {i[4] + i[5]}) that no earlier launch has written")
-        elif st is not None:
-            if not bool(st[0].all()) and not st[1]:
-                fails.append(f"launch {k}: {L!r} reads a tensor with {int((~st[0]).sum())} raw row elements no launch has written")
-            st[1] = True
+        else:                                                     # every tensor it reads (the residual launch: two)
+            for ptr in (L.read_ptrs or [L.in_ptr]):
+                st = state.get(ptr)
+                if st is not None:
+                    if not bool(st[0].all()) and not st[1]:
+                        fails.append(f"launch {k}: {L!r} reads a tensor with {int((~st[0]).sum())} raw row elements no launch has written")
+                    st[1] = True
         for di, own in own_rows(L):
             ptr = L.dst_ptrs[di]
             st = state.get(ptr)

@@ -71,7 +71,7 @@ def flag():
 # ================================================================================================ Part 1: convolutions
 def test_the_guard_cases_cover_every_instance_of_the_product_and_of_the_audits_outside_list():
     """The module's instance list is EXPECTED_INSTANCES of tests/test_gpu_trunk_launches.py plus the instances that file lists
-    as deliberately outside the product: a new instance there without a guard case here fails.  (Cases marked ``extra`` --
+    as outside the Inception trunk (two of them ResNet-50's): a new instance there without a guard case here fails.  (Cases marked ``extra`` --
     another Cin % 32 or destination of a template instance already on the list, the POOLH form at six window pieces -- come
     on top and are not on either list.)"""
     required = {c.key for c in G.CASES.values() if not c.extra}

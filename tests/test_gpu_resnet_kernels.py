@@ -1,5 +1,6 @@
 """GPU: the kernels ResNet-50 adds (csrc/resnet.hip, stem7_mfma_u8_kernel of csrc/conv_pipe.hip) at every layout edge, and the
-split-precision convolution at ResNet's shapes.
+split-precision convolution at ResNet's shapes; the stem also past the first iteration of its persistent tile loop (more tiles than
+the device has CUs).
 
 Stem (both routes) and convolutions: ``tests/_trunk_audit.CONV_TOL`` of the output scale against an fp64 convolution of the table
 values, the project's figure for every split convolution.  Residual add and pool: no tolerance, bit for bit against
@@ -100,6 +101,33 @@ def test_stem_mfma_against_fp64(dev, stem, n, h, w):
         assert torch.equal(bits16(alone), bits16(got[n - 1:]))
 
 
+@pytest.mark.parametrize("h,w,tiles_per_image,more", [(33, 47, 3, 2), (9, 13, 1, 3)])
+def test_stem_mfma_walks_more_tiles_than_there_are_cus(dev, stem, h, w, tiles_per_image, more):
+    """stem7_mfma_u8_kernel launches min(tiles, CU count) workgroups and each walks tiles ``gridDim.x`` apart: a batch with more
+    tiles than the device has CUs runs the second iteration of that loop -- the barrier at its top, the patch rewritten while other
+    waves finish their tile, ``continue`` for the waves past the last output row (33 x 47: 17 output rows, so the third tile of an
+    image has one live wave; 9 x 13: one tile per image with five).  Every other stem test stays under the CU count."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    n = cus // tiles_per_image + more
+    oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    assert ((oh + 7) // 8) * ((ow + 31) // 32) == tiles_per_image and n * tiles_per_image > cus
+    img = seeded_bytes(n, h, w, 9000 + 100 * h + w)
+    want = stem.reference(stem.seeded, img)
+    assert want.shape == (n, oh, ow, 64)
+    big = torch.full((n + 2, oh, ow, 128), SENT, dtype=torch.float16, device=dev)         # canaries: an image before and one after
+    got = stem.mfma(stem.seeded, img.to(dev), out=big[1:1 + n])
+    torch.cuda.synchronize()
+    assert bool((big[0] == SENT).all()) and bool((big[-1] == SENT).all())
+    scale = want.abs().max().item()
+    per_image = (merged64(got) - want).abs().flatten(1).amax(1)
+    err = per_image.max().item()
+    print(f"stem mfma {n}x{h}x{w}: {n * tiles_per_image} tiles on {cus} CUs, error / scale = {err / scale:.3e} "
+          f"(images whose tiles a second iteration computes: {per_image[cus // tiles_per_image:].max().item() / scale:.3e})")
+    assert err <= CONV_TOL * scale, (n, h, w, err, scale, int(per_image.argmax()))
+    alone = stem.mfma(stem.seeded, img[n - 1:].to(dev))                                   # the last image: a second-iteration tile
+    assert torch.equal(bits16(alone), bits16(got[n - 1:]))
+
+
 @pytest.mark.parametrize("n,h,w", STEM_SHAPES)
 def test_stem_padded_route_against_fp64(dev, stem, n, h, w):
     from tise_toolbox_amd import conv_split
@@ -168,7 +196,7 @@ def test_stem_entry_minimum(dev, stem):
 # --------------------------------------------------------------------------------------------- convolutions at ResNet's shapes
 #              cin, cout, k, stride, pad, mode
 CONV_LAYERS = [(256, 512, 1, 2, 0, 1), (128, 128, 3, 2, 1, 0), (512, 512, 3, 2, 1, 0), (64, 256, 1, 1, 0, 1), (512, 2048, 1, 1, 0, 1),
-               (32, 64, 7, 2, 3, 0)]
+               (32, 64, 7, 2, 3, 0), (64, 64, 3, 1, 1, 0), (128, 128, 3, 1, 1, 0), (256, 1024, 1, 2, 0, 1)]
 
 
 @pytest.fixture(scope="module")

@@ -72,14 +72,15 @@ TAP_SCALARS = dict(hw=289, C=768, c0=0, nc=7, ld=2048)
 TAP_BLOCK = 6
 CLASSES = {"torchvision": 1000, "inception-2015": 1008, "slim": 51}
 
-# Every kernel instance the dispatchers can launch for the product, read off csrc/conv_split.hip (tise_conv_split_f16,
+# Every kernel instance the dispatchers can launch for the Inception trunk, read off csrc/conv_split.hip (tise_conv_split_f16,
 # launch_rowwin_any, launch_poolin) and csrc/conv_pipe.hip (launch_regw32, launch_regw32_pool) with the tile widths
 # conv_split.pick_tn returns for the trunk's Couts (tests/_trunk_audit.py instance_of names them the same way):
 #   ("fast", tn, Cin % 32, K order) / ("rowwin", tn, Cin % 32, window pieces NP, POOLH) / ("poolin", TNW, taps) /
 #   ("pipe34", Cout, padding, destination)
-# Deliberately outside -- no trunk layer of a 299 x 299 input selects them: conv_split_fast_kernel<1> (pick_tn gives 1 to
-# Cout = 32 only: Conv2d_2a, which is configuration 34), its block-major form at tn 2, its paired-16-channel-tail steps
-# (the 48- and 80-channel inputs feed 5x5 / 3x3 stride-1 layers: row-window kernel), conv_split_rowwin_kernel<2, 6> and
+# Outside THIS trunk -- no layer of the Inception trunk on a 299 x 299 input selects them (two of them, conv_split_rowwin_kernel
+# <2, 6> and <4, 5>, are product instances all the same: ResNet-50 reaches them, and tests/test_gpu_resnet_launches.py audits them
+# there): conv_split_fast_kernel<1> (pick_tn gives 1 to Cout = 32 only: Conv2d_2a, which is configuration 34), its block-major
+# form at tn 2, its paired-16-channel-tail steps (the 48- and 80-channel inputs feed 5x5 / 3x3 stride-1 layers: row-window kernel), conv_split_rowwin_kernel<2, 6> and
 # <4, 5> (tn 2 rows are 35 wide: 5 pieces; tn 4 rows are 17 or 8 wide: 6 pieces), conv_poolin_kernel<2, VT> (the vertical-tap
 # consumer is Mixed_5b: 208+ couts), conv_regw32_kernel<32, padded>; and the tools' instances: every conv_split_glds_kernel
 # (the tests' reference kernel), the DBG / instrumented forms (nseg bits 0x700 / 0x800 / 0x1000).

@@ -153,7 +153,7 @@ class HipResNet50:
         x = self._chunk_map(u8)
         n, h, w, c2 = x.shape
         out = torch.empty((n, c2 // 2), dtype=torch.float32, device=self.dev)
-        _lib.call("tise_split_mean_nhwc", ctypes.c_void_p(x.data_ptr()), n, h * w, c2 // 2, ctypes.c_void_p(out.data_ptr()),
+        _lib.call("tise_split_mean_nhwc", device._ptr(x), n, h * w, c2 // 2, device._ptr(out),
                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         return out
 
